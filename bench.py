@@ -14,7 +14,11 @@ Rank 0 prints ONE JSON line.
 `python -m torch.distributed.run` BEFORE anything touches the GPU (the parent only waits for the launcher and exits with its
 code; it never initialises HIP, so no process that holds the GPU is ever replaced).
 
-Every performance figure in the line is measured by THIS run.  Fields beside the contract's:
+A plain run sets up, warms up, times the K steps and prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, `config`, `loss`, `device`; `collective` at N > 1).  `--dump-outputs DIR` writes what the last timed step computed
+(dump_outputs).  Everything below is measured only with `--full`.
+
+Every performance figure in the line is measured by THIS run.  Fields beside the contract's (`--full`):
   roofline       dominant kernel gemm_nt: HIP events around every 13th Linear call INSIDE the timed region.  `traffic` (HBM bytes per
                  launch from rocprofv3 PMC passes) cannot be taken inside a run: it comes from the committed profile of this same
                  command and is reported only while the kernel sources still hash to what that profile was taken on, else null.
@@ -60,7 +64,7 @@ def parse_args():
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--mode", default="train", choices=["train", "fwd"])
     ap.add_argument("--precision", default="fast", choices=["fast", "half"], help="operand format of the TIMED region (default: bf16 = the "
-                    "headline; half is reported in the `half` object of the default run anyway)")
+                    "headline; half is reported in the `half` object of a --full run anyway)")
     ap.add_argument("--drop-path", type=float, default=0.1)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-all-cores", action="store_true", help="also time the CPU baseline on ALL host cores (a 256-thread pool on a "
@@ -81,7 +85,16 @@ def parse_args():
     ap.add_argument("--dry-run", action="store_true", help="launch plumbing only: rendezvous, one all-reduce, rank 0 prints the world size "
                                                           "(no GPU work; runs over gloo on a CPU-only host -- tests/test_bench_launch.py)")
     ap.add_argument("--graph", type=int, default=-1, help="1: capture the whole step in a HIP graph and replay it (N=1 only); default eager")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline too: the live gemm_nt roofline and board power "
+                    "inside the timed region, from_profiles, the extras after it and cpu_baseline (--no-extras, --only-extras, --no-cpu-baseline, "
+                    "--no-live-profile, --breakdown and the --cpu-* options select among them); without it the run sets up, warms up, times "
+                    "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step handed its caller "
+                    "as DIR/<name>.npy (float32): loss, logits, grad_norm and a fixed seeded sample of the updated parameters (dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch(args):
@@ -445,6 +458,33 @@ def parity_vs_golden(T, dev, modes, loss_scale=4096.0):
     return res
 
 
+def dump_outputs(out_dir, outputs, model=None, per_tensor=4096, seed=0):
+    """--dump-outputs: the arrays the last timed step handed its caller, as float32 `out_dir/<name>.npy`, so that two builds can be
+    compared output for output on the same seeded inputs.  `outputs` maps names to tensors (loss, logits, grad_norm).  With a model,
+    `params_sample` holds the parameters after the step's update in named_parameters() order: every element of a tensor of at most
+    `per_tensor` elements, `per_tensor` elements at fixed seeded positions of a larger one (ViT-B: 162 tensors, 1.3 MB).  Returns
+    {name: shape}."""
+    import numpy as np
+    import torch
+    arrays = {k: (v.detach().float() if v.dim() else v.detach().float().reshape(1)).cpu().numpy() for k, v in outputs.items() if torch.is_tensor(v)}
+    if model is not None:
+        rng = np.random.default_rng(seed)
+        parts = []
+        with torch.no_grad():
+            for _, p in model.named_parameters():
+                flat = p.detach().reshape(-1)
+                if flat.numel() > per_tensor:
+                    idx = torch.from_numpy(np.sort(rng.integers(0, flat.numel(), per_tensor))).to(flat.device)
+                    flat = flat[idx]
+                parts.append(flat.float().cpu().numpy())
+        arrays["params_sample"] = np.concatenate(parts)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20, "--dump-outputs: more than 64 MB"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a.astype(np.float32))
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def main():
     args = parse_args()
     if args.cpu_baseline_child:
@@ -500,7 +540,7 @@ def main():
     model = T.create_model(args.model, pretrained=False, num_classes=2, all_frames=args.frames, tubelet_size=2,
                            final_reduction="fc_norm", drop_path_rate=args.drop_path if args.mode == "train" else 0.0,
                            init_scale=0.001, use_flash_attn=True).to(dev)
-    sd_cpu = {k: v.detach().cpu() for k, v in model.state_dict().items()} if rank == 0 else None
+    sd_cpu = {k: v.detach().cpu() for k, v in model.state_dict().items()} if (rank == 0 and args.full) else None  # (cpu_baseline's weights)
     D, L = model.embed_dim, model.get_num_layers()
     ntok = model.patch_embed.num_patches
     f_fwd, f_fb = flops_per_clip(ntok, D, L)
@@ -517,6 +557,7 @@ def main():
     lr_sched = E.cosine_scheduler(5e-4 * B * world / 256, 1e-6, 1, max(total_steps, 2), warmup_epochs=0)
 
     dp = opt = scaler = None
+    step_out = {}  # what the last step handed its caller (references, no copies): --dump-outputs
     if args.mode == "train":
         model.train()
         dp = DataParallel(model, bucket_mb=64.0, linear_schedule=None if args.linear_schedule == "auto" else args.linear_schedule,
@@ -532,9 +573,11 @@ def main():
         def step(it):
             for g in opt.param_groups:
                 g["lr"] = lr_sched[it] * g["lr_scale"]
-            loss = crit(dp(x), y)
-            scaler(loss, opt, parameters=params, update_grad=True)
+            logits = dp(x)
+            loss = crit(logits, y)
+            step_out["grad_norm"] = scaler(loss, opt, parameters=params, update_grad=True)
             dp.zero_grad()
+            step_out["logits"] = logits.detach()
             return loss
 
         use_graph = (args.graph == 1)  # measured: the step is not launch-bound (eager 61.8 ms vs graph 62.3 ms), so eager is the default
@@ -553,9 +596,11 @@ def main():
             scales = [g["lr_scale"] for g in opt.param_groups]
 
             def eager_body():
-                loss = crit(dp(x), y)
-                scaler(loss, opt, parameters=params, update_grad=True)
+                logits = dp(x)
+                loss = crit(logits, y)
+                step_out["grad_norm"] = scaler(loss, opt, parameters=params, update_grad=True)
                 dp.zero_grad()
+                step_out["logits"] = logits.detach()
                 return loss
 
             # warm-up AND capture on one stream: kernels.workspace is per (device, stream), so the scratch buffers the graph bakes in are
@@ -593,10 +638,10 @@ def main():
     if dp is not None and dp._timing is not None:
         dp._timing["steps"].clear()  # (the warm-up steps' records)
     prof = None
-    if rank == 0 and not args.no_live_profile:
+    if rank == 0 and args.full and not args.no_live_profile:
         prof = K.LaunchProfiler(only=["gemm_nt"], stride=13)
         K.set_profiler(prof)
-    power = PowerSampler().start() if rank == 0 else None  # (a thread that reads two sysfs files every 50 ms: no GPU work, no sync)
+    power = PowerSampler().start() if (rank == 0 and args.full) else None  # (a thread that reads two sysfs files every 50 ms: no GPU work, no sync)
     barrier()
     t0 = time.perf_counter()
     for it in range(args.steps):
@@ -634,6 +679,10 @@ def main():
             torch.distributed.barrier()
             torch.distributed.destroy_process_group()
         return
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, dict(step_out, loss=last) if args.mode == "train" else {"logits": last},
+                              model if args.mode == "train" else None)
 
     clips_per_s = B * world * args.steps / dt
     fl = f_fb if args.mode == "train" else f_fwd
@@ -656,17 +705,20 @@ def main():
     }
     if collective is not None:
         out["collective"] = collective
-    try:
-        out["power"] = power.summary(power_cards, seconds_per_step=dt / args.steps)
-        if out["power"].get("joules_per_step"):
-            out["power"]["picojoules_per_algorithmic_flop"] = round(out["power"]["joules_per_step"] / (B * fl) * 1e12, 3)
-    except Exception as e:  # noqa: BLE001
-        out["power"] = {"error": repr(e)}
-    fp = read_profiles()
-    out["from_profiles"] = fp
-    held = fp.get("held_clock_mhz", {})
-    if held.get("value") and held.get("current"):
-        out["from_profiles"]["frac_of_roofline_at_held_clock"] = round(out["frac_of_bf16_mfma_roofline"] * NOMINAL_CLOCK_MHZ / float(held["value"]), 4)
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    if args.full:
+        try:
+            out["power"] = power.summary(power_cards, seconds_per_step=dt / args.steps)
+            if out["power"].get("joules_per_step"):
+                out["power"]["picojoules_per_algorithmic_flop"] = round(out["power"]["joules_per_step"] / (B * fl) * 1e12, 3)
+        except Exception as e:  # noqa: BLE001
+            out["power"] = {"error": repr(e)}
+        fp = read_profiles()
+        out["from_profiles"] = fp
+        held = fp.get("held_clock_mhz", {})
+        if held.get("value") and held.get("current"):
+            out["from_profiles"]["frac_of_roofline_at_held_clock"] = round(out["frac_of_bf16_mfma_roofline"] * NOMINAL_CLOCK_MHZ / float(held["value"]), 4)
     if prof is not None:
         summ = prof.summary()
         g = summ.get("gemm_nt")
@@ -693,7 +745,7 @@ def main():
 
     want = set(filter(None, args.only_extras.split(","))) or {"roofline_all", "engine_loop", "fwd_only", "half", "precise", "mae_pretrain", "torch_route",
                                                                 "vit_small", "vit_large", "inference_b1", "power"}
-    extras = world == 1 and not args.no_extras and args.mode == "train" and args.graph != 1
+    extras = args.full and world == 1 and not args.no_extras and args.mode == "train" and args.graph != 1
     if args.precision != "fast":  # the other modes' objects compare against the bf16 headline: only the per-class table makes sense here
         want &= {"roofline_all"}
     it_next = args.warmup + args.steps
@@ -959,7 +1011,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             out["torch_route"] = {"error": repr(e)}
 
-    if world == 1 and not args.no_cpu_baseline and args.model == "vit_base_patch16_224":
+    if args.full and world == 1 and not args.no_cpu_baseline and args.model == "vit_base_patch16_224":
         try:
             out["cpu_baseline"] = cpu_baseline(sd_cpu, args.frames, all_cores=not args.no_cpu_all_cores)
         except Exception as e:  # noqa: BLE001

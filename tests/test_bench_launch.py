@@ -13,6 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _run(args, env_extra=None, timeout=240):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    if "--dry-run" in args:  # the launch plumbing over gloo on any host (RCCL would bind one GPU per rank: none on a CPU host, one on a 1-GPU box)
+        env["TAD_DIST_BACKEND"] = "gloo"
     env.update(env_extra or {})
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=timeout, env=env)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -90,3 +92,51 @@ def test_power_sampler_reads_hwmon_and_picks_the_loaded_card(tmp_path):
     assert "error" in empty.summary(empty.stop())
     share = bench.host_cpu_share()
     assert share["os_cpu_count"] >= share["usable"] >= 1
+
+
+def test_bench_steps_must_be_positive():
+    """`--steps` is the number of timed steps: zero of them cannot give `ms_per_step` (refused before anything is imported or launched)"""
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        r, lines = _run(["--gpus", "1"] + bad, timeout=60)
+        assert r.returncode == 2 and not lines and "--steps must be >= 1" in r.stderr
+
+
+def test_dump_outputs_writes_float32_arrays_and_a_fixed_parameter_sample(tmp_path):
+    """--dump-outputs: every array as float32 .npy, a scalar as shape (1,), small parameter tensors in full and large ones at the same
+    seeded positions in every run (so that two builds can be compared element for element)"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(100, 64), torch.nn.Linear(64, 3))  # 6400-element weight: sampled; the rest in full
+    outs = {"loss": torch.tensor(0.5, dtype=torch.float64), "logits": torch.randn(4, 3, dtype=torch.bfloat16), "grad_norm": torch.tensor(2.0)}
+    shapes = bench.dump_outputs(str(tmp_path / "a"), outs, m, per_tensor=4096)
+    assert shapes == {"loss": [1], "logits": [4, 3], "grad_norm": [1], "params_sample": [4096 + 64 + 192 + 3]}
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in shapes}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["loss"][0] == 0.5 and np.array_equal(got["logits"], outs["logits"].float().numpy())
+    p = got["params_sample"]
+    w0 = m[0].weight.detach().reshape(-1).numpy()
+    assert np.isin(p[:4096], w0).all() and np.array_equal(p[4096:], np.concatenate([m[0].bias.detach().numpy(), m[1].weight.detach().reshape(-1).numpy(),
+                                                                                       m[1].bias.detach().numpy()]))
+    bench.dump_outputs(str(tmp_path / "b"), {}, m, per_tensor=4096)
+    assert np.array_equal(np.load(tmp_path / "b" / "params_sample.npy"), p)
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_plain_bench_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --gpus 1` without --full: the headline fields and nothing measured beside them; --dump-outputs holds the last timed step's
+    loss (the line's `loss`), logits, gradient norm and updated parameters"""
+    import numpy as np
+    r, lines = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--dump-outputs", str(tmp_path / "out")], timeout=540)
+    assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stderr[-3000:])
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0 and out["higher_is_better"] is True
+    assert out["unit"] == "clips/sec" and out["dtype"] == "bf16" and out["metric"].startswith("clips/sec")
+    assert not {"roofline", "power", "from_profiles", "roofline_all", "half", "precise", "cpu_baseline"} & set(out)
+    arrays = {k: np.load(tmp_path / "out" / (k + ".npy")) for k in ("loss", "logits", "grad_norm", "params_sample")}
+    assert out["dump_outputs"]["arrays"] == {k: list(a.shape) for k, a in arrays.items()}
+    assert arrays["logits"].shape == (2, 2) and all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert abs(float(arrays["loss"][0]) - out["loss"]) <= 1e-6 * max(1.0, abs(out["loss"]))

@@ -26,7 +26,7 @@ echo "[collect_final] PMC passes done"
 python3 tools/summarize_profile.py --round "$R" --kt "$O/kt" --fetch "$O/fetch" --write "$O/write" --steps 13 --warmup 3 --out "$P" > "$O/summarize.log" 2>&1 || { tail -5 "$O/summarize.log"; exit 1; }
 cp "$P/${R}_summary.json" "$P/${R}_kernel_stats.txt" profiles/
 find "$O/kt" "$O/fetch" "$O/write" -name "*.csv" -size +8M -delete 2>/dev/null
-timeout -k 10 900 python3 bench.py > "$P/${R}_bench.json" 2> "$O/bench.err" || { echo "bench failed"; tail -5 "$O/bench.err"; exit 1; }
+timeout -k 10 900 python3 bench.py --full > "$P/${R}_bench.json" 2> "$O/bench.err" || { echo "bench failed"; tail -5 "$O/bench.err"; exit 1; }
 echo "[collect_final] bench done"
 if tools/pmc_attention.sh "$R" > "$O/pmc_attn.log" 2>&1; then cp "gpurun_out/${R}_pmc_attn/summary.txt" "$P/${R}_pmc_attention.txt"; else echo "pmc_attention failed"; tail -5 "$O/pmc_attn.log"; fi
 ls -la "$P"
