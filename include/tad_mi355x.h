@@ -311,6 +311,17 @@ int tad_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_a
                    const int32_t* group_step, float beta1, float beta2, float eps, const float* grad_scale,
                    float* sumsq_partials, tad_stream_t stream);
 
+/* Weight EMA over any number of f32 tensor pairs in ONE launch (timm.utils.ModelEma.update, engine_for_finetuning.py:98-99):
+ *   ema[i] = fl( fl(ema[i] * decay) + fl(model[i] * one_minus_decay) )        (no FMA contraction: bit-exact with the reference's
+ *   `ema_v * decay + (1. - decay) * model_v`, whose 1 - decay is taken in double; the caller passes both as floats).
+ * tensors (device, int64 [n_tensors][4]): {ema address, model address, numel, 0} per pair; numel >= 1, 4-byte aligned addresses
+ *   (float4 path where both are 16-byte aligned, scalar path otherwise).
+ * chunks (device, int32 [n_chunks][2]): {tensor index, chunk index within the tensor}, one workgroup per TAD_EMA_CHUNK elements;
+ *   every chunk of every tensor listed once.  The tables are host-built and reused while the addresses stay the same. */
+#define TAD_EMA_CHUNK 8192
+int tad_ema_update(const int64_t* tensors, int n_tensors, const int32_t* chunks, int n_chunks, float decay, float one_minus_decay,
+                   tad_stream_t stream);
+
 /* ---- MAE pre-training path: what modeling_pretrain.py / engine_for_pretraining.py add around the Block stack ----
  * Rows are D f32, D % 4 == 0.  idx arrays are int32 on the device. */
 /* out[r] = src[idx[r]], r < n_out: x[~mask].reshape(B,-1,C) (modeling_pretrain.py:98) with idx = b*N + visible token */

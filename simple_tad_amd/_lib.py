@@ -59,6 +59,7 @@ SIGNATURES = {
     "tad_transpose_bf16_batched": (_i, [_vp, _vp, _vp, _i, _vp]),
     "tad_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(_f), C.POINTER(_f), _i, C.POINTER(C.c_int32), _f, _f, _f, _vp, _vp,
                        _vp]),
+    "tad_ema_update": (_i, [_vp, _i, _vp, _i, _f, _f, _vp]),
     "tad_gather_rows_f32": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     "tad_scatter_rows_f32": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     "tad_mae_assemble": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -104,6 +105,7 @@ EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL = 0, 1, 2
 ABI_VERSION = 4
 ADAMW_CHUNK = 4096
 ADAMW_MAX_GROUPS = 128
+EMA_CHUNK = 8192
 POOL_SPLIT = 8
 
 _lib = None

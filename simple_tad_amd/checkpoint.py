@@ -65,3 +65,18 @@ def load_state_dict(model: torch.nn.Module, state_dict, prefix: str = '', ignore
     if unexpected:
         print("Weights from pretrained model not used in {}: {}".format(model.__class__.__name__, unexpected))
     return missing, unexpected
+
+
+# ---- weight EMA (timm.utils.ModelEma, see ema.py) in the reference's checkpoints
+def ema_state_dict(model_ema):
+    """what ``utils.save_model`` stores as ``checkpoint['model_ema']`` (utils.py:462-463): timm's ``get_state_dict(model_ema)``, the
+    state dict of the EMA module without a ``module.`` wrapper"""
+    ema = model_ema.ema
+    return (ema.module if hasattr(ema, 'module') else ema).state_dict()
+
+
+def load_checkpoint_for_ema(model_ema, obj):
+    """``utils._load_checkpoint_for_ema`` (utils.py:229-236) without its BytesIO round trip.  ``obj`` is a bare EMA state dict (what
+    ``auto_load_model`` passes: ``checkpoint['model_ema']``) or ``{'state_dict_ema': ...}``.  Deviation: both forms restore the
+    weights, where the reference's bare form is ignored by timm's loader (no ``'state_dict_ema'`` key) and resumes nothing."""
+    model_ema._load_checkpoint(obj)

@@ -310,8 +310,12 @@ def train_class_batch(model, samples, target, criterion):
 
 def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable, optimizer, device, epoch: int, loss_scaler,
                     max_norm: float = 0, start_steps=0, lr_schedule_values=None, wd_schedule_values=None,
-                    num_training_steps_per_epoch=None, update_freq=1, log=None):
-    """engine_for_finetuning.train_one_epoch (engine_for_finetuning.py:24-140) without mixup / EMA / DeepSpeed branches.
+                    num_training_steps_per_epoch=None, update_freq=1, log=None, model_ema=None):
+    """engine_for_finetuning.train_one_epoch (engine_for_finetuning.py:24-140) without mixup / DeepSpeed branches.
+    ``model_ema`` (an ``ema.ModelEma`` or anything with ``update(model)``) is updated after every completed optimizer step, i.e. on
+    the last micro-step of each ``update_freq`` group, as the reference does (:96-99) -- also after a step that the loss scaler
+    skipped on the device, where the average then moves toward the unchanged weights.  The update is queued on the stream behind
+    the optimizer step: no host sync.
     The loader yields (samples [B,3,T,H,W], targets [B], *rest).  Returns the per-step meter lists of THIS rank plus
     ``stats["averaged"]`` = the cross-rank epoch averages the reference returns (``{k: meter.global_avg}``)."""
     model.train(True)
@@ -344,6 +348,8 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable, op
         grad_norm = loss_scaler(loss, optimizer, clip_grad=max_norm if max_norm else None, parameters=params, update_grad=last)
         if last:
             zero()
+            if model_ema is not None:
+                model_ema.update(model)
         if device.type == "cuda":
             torch.cuda.synchronize()
         stats["loss"].append(loss_value)

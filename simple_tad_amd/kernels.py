@@ -754,6 +754,45 @@ def adamw_step(param, grad, exp_avg, exp_avg_sq, chunk_group, group_lr, group_wd
                                          _p(grad_scale), _p(sumsq_partials), _stream()), "tad_adamw_step")
 
 
+def ema_table(pairs):
+    """Host-side tables of ema_update: pairs = [(ema address, model address, numel)] of f32 tensors.  Returns (tensors int64
+    [n_tensors, 4], chunks int32 [n_chunks, 2]) as ONE int64 CPU tensor (tensors first, chunks behind them) and the two counts.
+    A pair whose addresses are misaligned by the same amount is split into a scalar head of up to 3 elements and a 16-byte aligned
+    body, so that a view starting at an odd element still takes the float4 path."""
+    rows = []
+    for e, m, n in pairs:
+        if n <= 0:
+            continue
+        if e % 4 or m % 4:
+            raise _lib.TadError("ema_table: f32 tensors must be 4-byte aligned")
+        h = ((16 - e % 16) % 16) // 4 if e % 16 == m % 16 else 0
+        h = min(h, n)
+        if h:
+            rows.append((e, m, h, 0))
+        if n > h:
+            rows.append((e + 4 * h, m + 4 * h, n - h, 0))
+    if not rows:
+        raise _lib.TadError("ema_table: no elements")
+    chunks = [(t, c) for t, r in enumerate(rows) for c in range((r[2] + _lib.EMA_CHUNK - 1) // _lib.EMA_CHUNK)]
+    import numpy as np
+    tens = np.asarray(rows, dtype=np.uint64).view(np.int64).reshape(-1)
+    chk = np.asarray(chunks, dtype=np.int32).reshape(-1)
+    if len(chunks) >= (1 << 31):
+        raise _lib.TadError("ema_table: too many chunks")
+    return torch.from_numpy(np.concatenate([tens, chk.view(np.int64)])), len(rows), len(chunks)
+
+
+def ema_update(table, n_tensors: int, n_chunks: int, decay: float, n_elements: int = 0):
+    """ema = ema * decay + (1 - decay) * model over every pair of ``table`` (a device copy of ema_table's buffer), ONE launch
+    (tad_ema_update).  ``1 - decay`` is taken in double here, as the reference's Python expression does."""
+    if not table.is_cuda or table.dtype != torch.int64 or not table.is_contiguous() or table.numel() != 4 * n_tensors + n_chunks:
+        raise _lib.TadError("ema_update: table must be the contiguous int64 device copy of ema_table()")
+    d = float(decay)
+    with _timed("ema", 0.0, 12.0 * n_elements):
+        check(_lib.load().tad_ema_update(table.data_ptr(), n_tensors, table.data_ptr() + 32 * n_tensors, n_chunks, d, 1.0 - d, _stream()),
+              "tad_ema_update")
+
+
 # ----------------------------------------------------------------------------- MAE pre-training path (SURVEY 8f-2)
 def _idx(t, name):
     if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous():
