@@ -322,6 +322,35 @@ int tad_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_a
 int tad_ema_update(const int64_t* tensors, int n_tensors, const int32_t* chunks, int n_chunks, float decay, float one_minus_decay,
                    tad_stream_t stream);
 
+/* Mixup / CutMix of the fine-tune loop on the device (mixup.py:159-218; applied at engine_for_finetuning.py:59-60 to the f32 clip batch).
+ * plan: int32 [B][TAD_MIXUP_PLAN_WORDS], one row per sample i (partner j = B-1-i):
+ *   {kind, w_self (f32 bits), w_other (f32 bits), t0, t1, y0, y1, x0, x1, lam (f32 bits), one_minus_lam (f32 bits), 0}
+ *   kind TAD_MIX_KEEP:  x[i] untouched (mixup.py:166 / :183 / :198, lam == 1)
+ *   kind TAD_MIX_BLEND: x[i] = fl( fl(x[i] * w_self) + fl(x[j] * w_other) )    (mixup.py:173, :191-192, :205-206; no FMA contraction)
+ *   kind TAD_MIX_PASTE: x[i][:, t0:t1, y0:y1, x0:x1] = x[j][same box]          (mixup.py:170, :187-188, :203; pair mode cuts T and H)
+ *   every right-hand side is the value BEFORE the call; lam / one_minus_lam are the soft target's coefficients of the sample.
+ * tad_mixup_plan_check: host-side check of a HOST copy of the table (kinds, finite coefficients, boxes inside the clip); no launch.
+ * tad_mixup_clips: x = contiguous f32 [B,C,T,H,W] on the device, B even, mixed in place in ONE launch (float4 accesses when x is
+ *   16-byte aligned and W % 4 == 0, scalar otherwise); plan on the device.  A box is cut to the clip on the device as well.
+ * tad_mixup_target: out f32 [B,num_classes] = mixup_target (mixup.py:22-27): fl( fl(y1 * lam) + fl(y2 * one_minus_lam) ) with
+ *   y1 / y2 the rows of labels[b] / labels[B-1-b] (int64) holding on_value at the label and off_value elsewhere. */
+#define TAD_MIXUP_PLAN_WORDS 12
+#define TAD_MIX_KEEP 0
+#define TAD_MIX_BLEND 1
+#define TAD_MIX_PASTE 2
+int tad_mixup_plan_check(const int32_t* plan_host, int B, int T, int H, int W);
+int tad_mixup_clips(float* x, const int32_t* plan, int B, int C, int T, int H, int W, tad_stream_t stream);
+int tad_mixup_target(const int32_t* plan, const int64_t* labels, float* out, int B, int num_classes, float on_value, float off_value,
+                     tad_stream_t stream);
+/* Soft-target cross entropy (timm.loss.SoftTargetCrossEntropy / LabelSmoothingCrossEntropy, the criteria of
+ * run_class_finetuning.py:467-473), forward and gradient in ONE launch, a wave per row of f32 logits [B,num_classes]:
+ *   loss[0]  = (1/B) sum_b sum_c -t[b][c] * log_softmax(logits[b])[c]
+ *   dlogits  = (softmax(logits[b]) * sum_c t[b][c] - t[b]) / B                 (the backward pass scales it by the incoming gradient)
+ * t = target (f32 [B,num_classes]) when given; else t[b][c] = smoothing / num_classes + (c == labels[b] ? 1 - smoothing : 0) from
+ * int64 labels.  Exactly one of target / labels is non-NULL; smoothing in [0, 1) (ignored with target). */
+int tad_soft_target_ce(const float* logits, const float* target, const int64_t* labels, float smoothing, float* loss, float* dlogits,
+                       int B, int num_classes, tad_stream_t stream);
+
 /* ---- MAE pre-training path: what modeling_pretrain.py / engine_for_pretraining.py add around the Block stack ----
  * Rows are D f32, D % 4 == 0.  idx arrays are int32 on the device. */
 /* out[r] = src[idx[r]], r < n_out: x[~mask].reshape(B,-1,C) (modeling_pretrain.py:98) with idx = b*N + visible token */

@@ -60,6 +60,10 @@ SIGNATURES = {
     "tad_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(_f), C.POINTER(_f), _i, C.POINTER(C.c_int32), _f, _f, _f, _vp, _vp,
                        _vp]),
     "tad_ema_update": (_i, [_vp, _i, _vp, _i, _f, _f, _vp]),
+    "tad_mixup_plan_check": (_i, [_vp, _i, _i, _i, _i]),
+    "tad_mixup_clips": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "tad_mixup_target": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp]),
+    "tad_soft_target_ce": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp]),
     "tad_gather_rows_f32": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     "tad_scatter_rows_f32": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     "tad_mae_assemble": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -106,6 +110,8 @@ ABI_VERSION = 4
 ADAMW_CHUNK = 4096
 ADAMW_MAX_GROUPS = 128
 EMA_CHUNK = 8192
+MIXUP_PLAN_WORDS = 12
+MIX_KEEP, MIX_BLEND, MIX_PASTE = 0, 1, 2
 POOL_SPLIT = 8
 
 _lib = None

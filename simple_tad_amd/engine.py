@@ -310,8 +310,11 @@ def train_class_batch(model, samples, target, criterion):
 
 def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable, optimizer, device, epoch: int, loss_scaler,
                     max_norm: float = 0, start_steps=0, lr_schedule_values=None, wd_schedule_values=None,
-                    num_training_steps_per_epoch=None, update_freq=1, log=None, model_ema=None):
-    """engine_for_finetuning.train_one_epoch (engine_for_finetuning.py:24-140) without mixup / DeepSpeed branches.
+                    num_training_steps_per_epoch=None, update_freq=1, log=None, model_ema=None, mixup_fn=None):
+    """engine_for_finetuning.train_one_epoch (engine_for_finetuning.py:24-140) without the DeepSpeed branches.
+    ``mixup_fn`` (a ``mixup.Mixup`` or anything with ``(samples, targets) -> (samples, soft_targets)``) is applied to every batch once it
+    is on the device (:59-60); the criterion then has to take soft targets (``loss.SoftTargetCrossEntropy``), and ``class_acc`` is
+    logged as ``None`` for the step, as the reference does (:104-107), so it does not appear in ``averaged``.
     ``model_ema`` (an ``ema.ModelEma`` or anything with ``update(model)``) is updated after every completed optimizer step, i.e. on
     the last micro-step of each ``update_freq`` group, as the reference does (:96-99) -- also after a step that the loss scaler
     skipped on the device, where the average then moves toward the unchanged weights.  The update is queued on the stream behind
@@ -338,6 +341,8 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable, op
                     group["weight_decay"] = wd_schedule_values[it]
         samples = samples.to(device, non_blocking=True)
         targets = targets.to(device, non_blocking=True)
+        if mixup_fn is not None:
+            samples, targets = mixup_fn(samples, targets)
         loss, output = train_class_batch(model, samples, targets, criterion)
         loss_value = loss.item()
         if not math.isfinite(loss_value):
@@ -353,7 +358,7 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable, op
         if device.type == "cuda":
             torch.cuda.synchronize()
         stats["loss"].append(loss_value)
-        stats["class_acc"].append((output.max(-1)[-1] == targets).float().mean().item())
+        stats["class_acc"].append(None if mixup_fn is not None else (output.max(-1)[-1] == targets).float().mean().item())
         stats["grad_norm"].append(None if grad_norm is None else float(grad_norm))
         stats["loss_scale"].append(loss_scaler.state_dict()["scale"])
         stats["lr"].append(max(g["lr"] for g in optimizer.param_groups))

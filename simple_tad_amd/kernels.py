@@ -793,6 +793,75 @@ def ema_update(table, n_tensors: int, n_chunks: int, decay: float, n_elements: i
               "tad_ema_update")
 
 
+# ----------------------------------------------------------------------------- Mixup / CutMix and the soft-target loss
+def mixup_plan_table(rows, T: int, H: int, W: int):
+    """Host-side plan table of mixup_clips / mixup_target: rows = one (kind, w_self, w_other, (t0, t1, y0, y1, x0, x1), lam,
+    one_minus_lam) per sample, coefficients already rounded to f32 by the caller.  Returns the int32 CPU tensor [B, MIXUP_PLAN_WORDS],
+    checked by tad_mixup_plan_check (kinds, finite coefficients, boxes inside the clip, even B); runs without a GPU."""
+    import numpy as np
+    tab = np.zeros((len(rows), _lib.MIXUP_PLAN_WORDS), dtype=np.int32)
+    fl = tab.view(np.float32)
+    for s, (kind, w_self, w_other, box, lam, oml) in enumerate(rows):
+        tab[s, 0] = kind
+        fl[s, 1], fl[s, 2] = w_self, w_other
+        tab[s, 3:9] = box
+        fl[s, 9], fl[s, 10] = lam, oml
+    check(_lib.load().tad_mixup_plan_check(tab.ctypes.data, len(rows), T, H, W), "tad_mixup_plan_check")
+    return torch.from_numpy(tab)
+
+
+def _req_plan(plan, B, name):
+    _req(plan, torch.int32, name)
+    if tuple(plan.shape) != (B, _lib.MIXUP_PLAN_WORDS):
+        raise _lib.TadError(f"{name}: expected the device copy of mixup_plan_table() for {B} samples, got {tuple(plan.shape)}")
+
+
+def mixup_clips(x, plan):
+    """Mix the contiguous f32 clip batch x [B,C,T,H,W] IN PLACE as the device plan table says (tad_mixup_clips, ONE launch, no
+    temporary); returns x.  The caller bumps x's version counter if autograd is to see the write."""
+    _req(x, torch.float32, "mixup_clips.x")
+    if x.dim() != 5:
+        raise _lib.TadError(f"mixup_clips.x: expected [B,C,T,H,W], got {tuple(x.shape)}")
+    B, Cc, T, H, W = x.shape
+    _req_plan(plan, B, "mixup_clips.plan")
+    with _timed("mixup", 0.0, 8.0 * x.numel()):
+        check(_lib.load().tad_mixup_clips(x.data_ptr(), plan.data_ptr(), B, Cc, T, H, W, _stream()), "tad_mixup_clips")
+    return x
+
+
+def mixup_target(plan, labels, num_classes: int, on_value: float, off_value: float):
+    """the soft targets [B, num_classes] f32 of the plan's per-sample lam (tad_mixup_target); labels int64 [B] on the device"""
+    _req(labels, torch.int64, "mixup_target.labels")
+    B = labels.numel()
+    _req_plan(plan, B, "mixup_target.plan")
+    out = torch.empty((B, int(num_classes)), dtype=torch.float32, device=labels.device)
+    check(_lib.load().tad_mixup_target(plan.data_ptr(), labels.data_ptr(), out.data_ptr(), B, int(num_classes), float(on_value),
+                                       float(off_value), _stream()), "tad_mixup_target")
+    return out
+
+
+def soft_target_ce(logits, target=None, labels=None, smoothing: float = 0.0):
+    """(loss [1], dlogits [B,classes]) of the batch-mean soft-target cross entropy over f32 logits, ONE launch (tad_soft_target_ce):
+    ``target`` f32 [B,classes], or int64 ``labels`` [B] smoothed on the fly."""
+    _req(logits, torch.float32, "soft_target_ce.logits")
+    if logits.dim() != 2:
+        raise _lib.TadError(f"soft_target_ce.logits: expected [B,classes], got {tuple(logits.shape)}")
+    B, ncls = logits.shape
+    if target is not None:
+        _req(target, torch.float32, "soft_target_ce.target")
+        if target.shape != logits.shape:
+            raise _lib.TadError(f"soft_target_ce.target: expected {tuple(logits.shape)}, got {tuple(target.shape)}")
+    if labels is not None:
+        _req(labels, torch.int64, "soft_target_ce.labels")
+        if tuple(labels.shape) != (B,):
+            raise _lib.TadError(f"soft_target_ce.labels: expected [{B}], got {tuple(labels.shape)}")
+    loss = torch.empty((1,), dtype=torch.float32, device=logits.device)
+    dlogits = torch.empty((B, ncls), dtype=torch.float32, device=logits.device)
+    check(_lib.load().tad_soft_target_ce(logits.data_ptr(), _p(target), _p(labels), float(smoothing), loss.data_ptr(), dlogits.data_ptr(),
+                                         B, ncls, _stream()), "tad_soft_target_ce")
+    return loss, dlogits
+
+
 # ----------------------------------------------------------------------------- MAE pre-training path (SURVEY 8f-2)
 def _idx(t, name):
     if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous():
