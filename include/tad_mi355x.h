@@ -235,8 +235,20 @@ int tad_attn_fwd(const uint16_t* qkv, void* out, int out_dtype, uint16_t* out_lo
  * first kernel leaves -rowsum(dout*out) in [0, BHN) and -lse/scale (-lse*log2(e) with q_prescaled) in [BHN, 2 BHN) for the second
  * one, which takes them as the initial values of its accumulators).  The q slot of dqkv is the gradient of the PLAIN q in either case. */
 /* Knob of the three attention kernels.  "dma_mode": 0 = production; 2 / 3 = timing-only ablations (wrong results) that only
- * ablation builds (TAD_BUILD_ABLATION=1) accept. */
+ * ablation builds (TAD_BUILD_ABLATION=1) accept.  "drop_skip": 1 (default; environment TAD_DROP_SKIP=0 starts it at 0) = the calls that
+ * follow a tad_attn_drop_scale fill the clips it marks as dropped instead of computing them; 0 = they compute every clip (A/B runs;
+ * every result the training step consumes is bit-identical either way). */
 int tad_attn_tuning(const char* key, int value);
+/* Stochastic depth (DropPath around the attention branch, modeling_finetune.py:159-163): hands the NEXT tad_attn_fwd / tad_attn_bwd
+ * call of the calling thread (either operand type; that call consumes the setting whatever it does with it) the per-clip scale
+ * rowscale [B] f32 (device memory; mask / keep_prob) by which the residual epilogue behind the attention multiplies the branch --
+ * the rowscale / rows_per_scale pair of tad_linear_fwd's TAD_EPI_BIAS_RESIDUAL, rows_per_scale = N.  A clip whose scale is exactly 0
+ * reaches the result neither forward (0 x branch) nor backward (its dout rows are exact zeros), so the kernels do not compute it: the
+ * forward writes zeros to its rows of out / out_lo and a finite placeholder to lse, the backward zeros to its rows of dqkv -- what
+ * the computation would have stored there in the backward's case, and values that only ever meet a zero factor in the forward's.
+ * The scale is read on the device (no host copy, no synchronisation); head_dim 64 with pre-scaled q, 16-bit output and no attention
+ * dropout takes the path, every other contract computes all clips as without the call.  NULL clears a pending setting. */
+int tad_attn_drop_scale(const float* rowscale, int rows_per_scale);
 size_t tad_attn_bwd_scratch_bytes(int B, int N, int H);
 /* Diagnostic, ablation builds only (see tad_linear_debug_stamps): while buf (device memory, 32 bytes per workgroup of the dK/dV grid
  * = ceil(N/128)*H*B workgroups) is set, every dK/dV workgroup records {s_memrealtime, s_memtime} at the start and at the end of its

@@ -87,12 +87,15 @@ __device__ __forceinline__ op16x8 pack8(const f32x16& a, int s2) {
 // and dP products get a fifth k-step, dQ a third (half-used) d tile.
 // (Round 4 measured the row fragments of a half tile requested as one batch of asm reads, as in the forward: the backward pair 846 ->
 // 866 us, with delta moved to the vector pipe to free the registers; not kept -- experiments/README.md.)
-template <int HD, bool QS, bool DROP, int DMA_MODE>
+// SKIP (both kernels; see attn_fwd.hip): the gradient rows dO of a clip whose residual scale clip_scale[b] is exactly 0 are exact zeros, and so
+// are the dq / dk / dv computed from them: a workgroup of such a clip stores zeros to its part of dqkv (the dQ kernel also to its rows of
+// delta) and returns.
+template <int HD, bool QS, bool DROP, int DMA_MODE, bool SKIP = false>
 __global__ __launch_bounds__(256, HD == 64 ? 3 : 2) void attn_bwd_dq_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ out,
                                                           const uint16_t* __restrict__ out_lo,
                                                           const uint16_t* __restrict__ dout, const float* __restrict__ lse,
                                                           float* __restrict__ delta, uint16_t* __restrict__ dqkv, int N, int H, int B,
-                                                          float scale, const Drop drop) {
+                                                          float scale, const Drop drop, const float* __restrict__ clip_scale) {
   static_assert(HD == 64 || HD == 80, "head dim");
   constexpr bool X = HD == 80;
   constexpr int NKS = HD / 16, NDT = X ? 3 : 2;
@@ -105,11 +108,23 @@ __global__ __launch_bounds__(256, HD == 64 ? 3 : 2) void attn_bwd_dq_kernel(cons
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nblk = (N + 127) / 128;  // 1-D XCD-aware grid: the blocks of one (batch, head) pair share an L2 (see attn_fwd.hip)
-  const int lin = xcd_remap(blockIdx.x, gridDim.x);
+  const int lin = SKIP ? xcd_remap_groups(blockIdx.x, gridDim.x, nblk) : xcd_remap(blockIdx.x, gridDim.x);  // (SKIP: clips differ in cost)
   const int head = (lin / nblk) % H, b = lin / nblk / H;
   const int q0 = (lin % nblk) * 128 + wave * 32;
   const int ql = lane & 31, h5 = lane >> 5;
   const int64_t tok = (int64_t)3 * H * HD;
+  if constexpr (SKIP) {
+    static_assert(HD == 64, "the fill writes rows of 64 dims");
+    if (clip_scale[b] == 0.f) {  // (workgroup-uniform)
+      zero_rows_32x64(dqkv + ((int64_t)b * N + q0) * tok + head * HD, tok, N - q0, lane);  // q slot
+      if (q0 + ql < N && h5 == 0) {
+        const int64_t idx = ((int64_t)b * H + head) * N + q0 + ql;
+        delta[idx] = 0.f;
+        delta[(int64_t)B * H * N + idx] = 0.f;
+      }
+      return;
+    }
+  }
   const uint16_t* base = qkv + (int64_t)b * N * tok + head * HD;
   const float c = scale * LOG2E;
 
@@ -330,10 +345,11 @@ __global__ __launch_bounds__(256, HD == 64 ? 3 : 2) void attn_bwd_dq_kernel(cons
 #ifndef TAD_DKV_ABL
 #define TAD_DKV_ABL 0  // timing experiments (experiments/README.md, round 4): 1 = a quarter of the row-constant LDS reads
 #endif
-template <int HD, bool QS, bool DROP, int DMA_MODE>
+template <int HD, bool QS, bool DROP, int DMA_MODE, bool SKIP = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout,
                                                            const float* __restrict__ rowc_g, uint16_t* __restrict__ dqkv, int N, int H, int B,
-                                                           float scale, unsigned long long* stamps, const Drop drop) {
+                                                           float scale, unsigned long long* stamps, const Drop drop,
+                                                           const float* __restrict__ clip_scale) {
   static_assert(HD == 64 || HD == 80, "head dim");
   constexpr bool X = HD == 80;   // dims 64..79 of the Q / dO tiles in side images of 32-byte rows (see attn_fwd.hip)
   constexpr int NKS = HD / 16, NDT = X ? 3 : 2;
@@ -347,11 +363,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nblk = (N + 127) / 128;  // 1-D XCD-aware grid (see attn_fwd.hip)
-  const int lin = xcd_remap(blockIdx.x, gridDim.x);
+  const int lin = SKIP ? xcd_remap_groups(blockIdx.x, gridDim.x, nblk) : xcd_remap(blockIdx.x, gridDim.x);  // (SKIP: clips differ in cost)
   const int head = (lin / nblk) % H, b = lin / nblk / H;
   const int key0 = (lin % nblk) * 128 + wave * 32;
   const int kl_ = lane & 31, h5 = lane >> 5;
   const int64_t tok = (int64_t)3 * H * BHD;
+  if constexpr (SKIP) {
+    static_assert(HD == 64, "the fill writes rows of 64 dims");
+    if (clip_scale[b] == 0.f) {  // (workgroup-uniform)
+      uint16_t* const okp = dqkv + ((int64_t)b * N + key0) * tok + (int64_t)H * BHD + head * BHD;  // k slot; v slot: + H * 64
+      zero_rows_32x64(okp, tok, N - key0, lane);
+      zero_rows_32x64(okp + (int64_t)H * BHD, tok, N - key0, lane);
+      return;
+    }
+  }
   const uint16_t* base = qkv + (int64_t)b * N * tok + head * BHD;
   const uint16_t* kbase = base + (int64_t)H * BHD;
   const uint16_t* vbase = base + (int64_t)2 * H * BHD;
@@ -707,9 +732,22 @@ namespace tad { namespace knobs {
 unsigned long long* attn_stamps = nullptr;
 int attn_dma_mode = getenv("TAD_ATTN_DMA_MODE") ? atoi(getenv("TAD_ATTN_DMA_MODE")) : 0;  // 2 / 3: timing-only ablations (ablation builds); shared with attn_fwd.hip
 int attn_fwd_q64 = getenv("TAD_ATTN_FWD_Q64") ? atoi(getenv("TAD_ATTN_FWD_Q64")) : 0;  // 1: the forward with 64 query rows per wave (attn_fwd_q64_kernel; experiment, round 6)
+int attn_drop_skip = getenv("TAD_DROP_SKIP") ? atoi(getenv("TAD_DROP_SKIP")) != 0 : 1;  // 0: clips dropped by stochastic depth are computed like the others (A/B runs)
+// what tad_attn_drop_scale left for the calling thread's next attention call
+static thread_local const float* drop_scale = nullptr;
+static thread_local int drop_scale_rows = 0;
+// The scale pointer for an attention call over sequences of N rows, or null (none set, or the knob is off); clears it.  *ok = false: it was
+// set with another rows_per_scale than N.
+const float* take_drop_scale(int N, bool* ok) {
+  const float* const rs = drop_scale;
+  *ok = !rs || drop_scale_rows == N;
+  drop_scale = nullptr;
+  return (*ok && attn_drop_skip) ? rs : nullptr;
+}
 #else
 extern unsigned long long* attn_stamps;
 extern int attn_dma_mode, attn_fwd_q64;
+const float* take_drop_scale(int N, bool* ok);
 #endif
 }}  // namespace tad::knobs
 using namespace tad::knobs;
@@ -731,8 +769,20 @@ extern "C" int tad_attn_tuning(const char* key, int value) {
     attn_fwd_q64 = value;
     return TAD_OK;
   }
+  if (!strcmp(key, "drop_skip")) {
+    TAD_REQUIRE(value == 0 || value == 1, "attn_tuning: drop_skip=%d not in {0, 1}", value);
+    attn_drop_skip = value;
+    return TAD_OK;
+  }
   set_error("attn_tuning: unknown key '%s'", key);
   return TAD_EINVAL;
+}
+
+extern "C" int tad_attn_drop_scale(const float* rowscale, int rows_per_scale) {
+  TAD_REQUIRE(!rowscale || rows_per_scale > 0, "attn_drop_scale: rows_per_scale must be positive");
+  drop_scale = rowscale;
+  drop_scale_rows = rowscale ? rows_per_scale : 0;
+  return TAD_OK;
 }
 
 // Diagnostic (ablation builds only, like tad_linear_debug_stamps): while buf (device memory, 32 bytes per workgroup of the dK/dV grid)
@@ -754,6 +804,9 @@ extern "C" size_t tad_attn_bwd_scratch_bytes(int B, int N, int H) {
 extern "C" int tad_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* out_lo, const uint16_t* dout, const float* lse,
                             uint16_t* dqkv, float* delta, int B, int N, int H, int d, float scale, int q_prescaled, float dropout_p,
                             uint32_t seed, tad_stream_t stream) {
+  bool rs_ok;
+  const float* const clip_scale = take_drop_scale(N, &rs_ok);  // (consumed by this call whatever route it takes)
+  TAD_REQUIRE(rs_ok, "attn_bwd: the scale set by tad_attn_drop_scale is one per clip: rows_per_scale must be N=%d", N);
   TAD_REQUIRE(qkv && out && dout && lse && dqkv && delta, "attn_bwd: null pointer");
   TAD_REQUIRE(d == 64 || d == 80, "attn_bwd: head_dim must be 64 or 80 (got %d)", d);
   const int BHD = d;
@@ -766,14 +819,22 @@ extern "C" int tad_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)(((N + 127) / 128) * H * B)), block(256);
   const int mode = attn_dma_mode;
+  // clips dropped by stochastic depth fill instead of compute: the production contract of the training step only (any other one computes them)
+  if (clip_scale && d == 64 && q_prescaled && dropout_p == 0.f && mode == 0) {
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<64, true, false, 0, true>), grid, block, 0, st, qkv, out, out_lo, dout, lse, delta, dqkv, N, H, B, scale, drop, clip_scale);
+    int rc = check_launch("attn_bwd_dq");
+    if (rc) return rc;
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, true, false, 0, true>), grid, block, 0, st, qkv, dout, delta, dqkv, N, H, B, scale, attn_stamps, drop, clip_scale);
+    return check_launch("attn_bwd_dkv");
+  }
 #define LAUNCH_BWD__(Q_, D_, M_)                                                                                             \
   {                                                                                                                          \
-    if (d == 64) hipLaunchKernelGGL((attn_bwd_dq_kernel<64, Q_, D_, M_>), grid, block, 0, st, qkv, out, out_lo, dout, lse, delta, dqkv, N, H, B, scale, drop);  \
-    else hipLaunchKernelGGL((attn_bwd_dq_kernel<80, Q_, D_, M_>), grid, block, 0, st, qkv, out, out_lo, dout, lse, delta, dqkv, N, H, B, scale, drop);  \
+    if (d == 64) hipLaunchKernelGGL((attn_bwd_dq_kernel<64, Q_, D_, M_>), grid, block, 0, st, qkv, out, out_lo, dout, lse, delta, dqkv, N, H, B, scale, drop, (const float*)nullptr);  \
+    else hipLaunchKernelGGL((attn_bwd_dq_kernel<80, Q_, D_, M_>), grid, block, 0, st, qkv, out, out_lo, dout, lse, delta, dqkv, N, H, B, scale, drop, (const float*)nullptr);  \
     int rc = check_launch("attn_bwd_dq");                                                                                    \
     if (rc) return rc;                                                                                                       \
-    if (d == 64) hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, Q_, D_, M_>), grid, block, 0, st, qkv, dout, delta, dqkv, N, H, B, scale, attn_stamps, drop);  \
-    else hipLaunchKernelGGL((attn_bwd_dkv_kernel<80, Q_, D_, M_>), grid, block, 0, st, qkv, dout, delta, dqkv, N, H, B, scale, attn_stamps, drop);  \
+    if (d == 64) hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, Q_, D_, M_>), grid, block, 0, st, qkv, dout, delta, dqkv, N, H, B, scale, attn_stamps, drop, (const float*)nullptr);  \
+    else hipLaunchKernelGGL((attn_bwd_dkv_kernel<80, Q_, D_, M_>), grid, block, 0, st, qkv, dout, delta, dqkv, N, H, B, scale, attn_stamps, drop, (const float*)nullptr);  \
     return check_launch("attn_bwd_dkv");                                                                                     \
   }
 #define LAUNCH_BWD_(Q_, M_) { if (dropout_p > 0.f) LAUNCH_BWD__(Q_, true, M_) else LAUNCH_BWD__(Q_, false, M_) }

@@ -99,10 +99,15 @@ __device__ __forceinline__ pv16x8 v_to_pv(const op16x8& v) { return v; }
 // HD: head dim 64, or 80 (the "huge" factories, modeling_finetune.py:390-398) handled as 64 + 16: the first 64 dims of a K / V tile
 // keep the 128-byte-row LDS image and everything built on it; dims 64..79 travel in a SIDE image of 32-byte rows (one more 1-KiB DMA
 // piece per wave and tile), add a fifth k-step to the score products and a third (half-used) d tile to the P V product.
-template <int HD, bool OUT_BF16, bool QS, bool DROP, int DMA_MODE>
+// SKIP: clip_scale [B] holds the per-clip scale the residual epilogue behind this attention multiplies the branch by (stochastic depth:
+// mask / keep_prob).  A workgroup of a clip whose scale is exactly 0 contributes nothing to the step: it writes zeros to out / out_lo and
+// SKIP_LSE to lse instead of computing, and returns.  A select on device data (wave-uniform: one scalar load), never a multiplication;
+// without SKIP the kernel does not look at clip_scale.
+constexpr float SKIP_LSE = 1e30f;  // finite, and exp(score - SKIP_LSE) = 0: a backward that does compute such a row gets P = 0, never inf * 0
+template <int HD, bool OUT_BF16, bool QS, bool DROP, int DMA_MODE, bool SKIP = false>
 __global__ __launch_bounds__(256, TAD_FWD_ROWSUM_VALU ? 4 : 1) void attn_fwd_kernel(const uint16_t* __restrict__ qkv, void* __restrict__ out,
                                                        uint16_t* __restrict__ out_lo, float* __restrict__ lse, int N, int H, int B,
-                                                       float scale, const Drop drop) {
+                                                       float scale, const Drop drop, const float* __restrict__ clip_scale) {
   constexpr bool VSUM = TAD_FWD_ROWSUM_VALU || DROP;  // row sums of P by vector adds instead of MFMAs
   static_assert(HD == 64 || HD == 80, "head dim");
   constexpr bool X = HD == 80;                                                   // 16 extra dims in the side images
@@ -117,12 +122,22 @@ __global__ __launch_bounds__(256, TAD_FWD_ROWSUM_VALU ? 4 : 1) void attn_fwd_ker
   // 8 XCDs every L2 fetched them again (rocprofv3 FETCH_SIZE: 5.9x the algorithmic bytes), so consecutive logical ids -- the
   // blocks of one pair -- are kept on one XCD
   const int nblk = (N + Q_BLOCK - 1) / Q_BLOCK;
-  const int lin = xcd_remap(blockIdx.x, gridDim.x);
+  const int lin = SKIP ? xcd_remap_groups(blockIdx.x, gridDim.x, nblk) : xcd_remap(blockIdx.x, gridDim.x);  // (SKIP: clips differ in cost)
   const int qblk = lin % nblk, pair = lin / nblk;
   const int head = pair % H, b = pair / H;
   const int q0 = qblk * Q_BLOCK + wave * Q_WAVE;
   const bool wave_live = q0 < N;  // wave-uniform
   const int ql = lane & 31, h5 = lane >> 5;
+  if constexpr (SKIP) {
+    static_assert(OUT_BF16 && HD == 64, "the fill writes 16-bit rows of 64 dims");
+    if (clip_scale[b] == 0.f) {  // (workgroup-uniform)
+      uint16_t* const o0 = (uint16_t*)out + (((int64_t)b * N + q0) * H + head) * HD;
+      zero_rows_32x64(o0, (int64_t)H * HD, N - q0, lane);
+      if (out_lo) zero_rows_32x64(out_lo + (o0 - (uint16_t*)out), (int64_t)H * HD, N - q0, lane);
+      if (q0 + ql < N && h5 == 0 && lse) lse[((int64_t)b * H + head) * N + q0 + ql] = SKIP_LSE;
+      return;
+    }
+  }
   const int64_t tok_stride = (int64_t)3 * H * HD;  // elements per token
   const uint16_t* base = qkv + (int64_t)b * N * tok_stride + head * HD;
   const uint16_t* kbase = base + (int64_t)H * HD;
@@ -704,10 +719,16 @@ TAD_NAMESPACE_END
 
 using namespace tad;
 
-namespace tad { namespace knobs { extern int attn_dma_mode, attn_fwd_q64; } }  // attn_bwd.hip (tad_attn_tuning)
+namespace tad { namespace knobs {  // attn_bwd.hip (tad_attn_tuning, tad_attn_drop_scale)
+extern int attn_dma_mode, attn_fwd_q64;
+const float* take_drop_scale(int N, bool* ok);
+} }
 
 extern "C" int tad_attn_fwd(const uint16_t* qkv, void* out, int out_dtype, uint16_t* out_lo, float* lse, int B, int N, int H, int d,
                             float scale, int q_prescaled, float dropout_p, uint32_t seed, tad_stream_t stream) {
+  bool rs_ok;
+  const float* const clip_scale = tad::knobs::take_drop_scale(N, &rs_ok);  // (consumed by this call whatever route it takes)
+  TAD_REQUIRE(rs_ok, "attn_fwd: the scale set by tad_attn_drop_scale is one per clip: rows_per_scale must be N=%d", N);
   TAD_REQUIRE(qkv && out, "attn_fwd: null pointer");
   TAD_REQUIRE(!out_lo || out_dtype == TAD_OP16, "attn_fwd: out_lo (the rounding residual) goes with a 16-bit output");
   TAD_REQUIRE(d == 64 || d == 80, "attn_fwd: head_dim must be 64 or 80 (got %d)", d);
@@ -729,7 +750,13 @@ extern "C" int tad_attn_fwd(const uint16_t* qkv, void* out, int out_dtype, uint1
     else hipLaunchKernelGGL((attn_fwd_q64_kernel<false>), grid, dim3(128), 0, (hipStream_t)stream, qkv, (uint16_t*)out, out_lo, lse, N, H, B);
     return check_launch("attn_fwd_q64");
   }
-#define LAUNCH_FWD___(H_, O_, Q_, D_, M_) hipLaunchKernelGGL((attn_fwd_kernel<H_, O_, Q_, D_, M_>), grid, block, 0, (hipStream_t)stream, qkv, out, out_lo, lse, N, H, B, scale, drop)
+  // clips dropped by stochastic depth fill instead of compute: the production contract of the training step only (any other one computes them)
+  if (clip_scale && d == 64 && q_prescaled && dropout_p == 0.f && out_dtype == TAD_OP16 && tad::knobs::attn_dma_mode == 0) {
+    hipLaunchKernelGGL((attn_fwd_kernel<64, true, true, false, 0, true>), grid, block, 0, (hipStream_t)stream, qkv, out, out_lo, lse, N, H, B, scale, drop,
+                       clip_scale);
+    return check_launch("attn_fwd");
+  }
+#define LAUNCH_FWD___(H_, O_, Q_, D_, M_) hipLaunchKernelGGL((attn_fwd_kernel<H_, O_, Q_, D_, M_>), grid, block, 0, (hipStream_t)stream, qkv, out, out_lo, lse, N, H, B, scale, drop, (const float*)nullptr)
 #define LAUNCH_FWD__(O_, Q_, D_, M_) { if (d == 64) LAUNCH_FWD___(64, O_, Q_, D_, M_); else LAUNCH_FWD___(80, O_, Q_, D_, M_); }
 #define LAUNCH_FWD_(O_, Q_, M_) { if (dropout_p > 0.f) LAUNCH_FWD__(O_, Q_, true, M_) else LAUNCH_FWD__(O_, Q_, false, M_) }
 #define LAUNCH_FWD(M_)                                                                                \

@@ -217,6 +217,16 @@ __device__ __forceinline__ void store_rows_via_lds(char* patch, const uint2 (&pk
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
 
+// The same 32 x 64 tile of 16-bit values filled with zeros (whole rows, 16 bytes per lane, eight lanes per 128-byte row; rows >= rows_valid
+// are not stored): what an attention workgroup of a clip that stochastic depth dropped writes instead of computing (attn_fwd.hip: SKIP).
+__device__ __forceinline__ void zero_rows_32x64(uint16_t* dst, int64_t row_stride, int rows_valid, int lane) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = 8 * i + (lane >> 3), ch = lane & 7;
+    if (row < rows_valid) *reinterpret_cast<uint4*>(dst + row * row_stride + ch * 8) = make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+
 // Attention dropout (nn.Dropout on the softmax matrix, modeling_finetune.py:99-101; flash_attention_class.py:59-61 passes dropout_p in
 // training): element (b, h, query, key) is kept iff hash(row, key, seed) >= p * 2^32, row = (b H + h) N + query, and kept
 // probabilities are scaled by 1 / (1 - p).  A counter-based hash instead of a stored N x N mask: every attention kernel (16-bit and
@@ -376,6 +386,18 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   const int xcd = bid & 7, idx = bid >> 3;
   const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
   return base + idx;
+}
+// The same for grids made of `npair` groups of `per` consecutive logical ids (attention: the query / key blocks of one (batch, head) pair, which
+// share their K / V or Q / dO tiles in an L2): a group still runs on ONE XCD, in order, but consecutive GROUPS are dealt round-robin over the
+// XCDs instead of an eighth of the grid each.  For kernels whose groups differ in cost by whole clips -- the workgroups of a clip that stochastic
+// depth dropped return at once (attn_fwd.hip: SKIP) -- an eighth of the grid per XCD is four whole clips of a 32-clip batch: the XCD of a dropped
+// clip went idle and the launch took as long as before.  Dealt by pair, every clip's heads are spread over all XCDs.  Needs npair % 8 == 0
+// (else: xcd_remap).
+__device__ __forceinline__ int xcd_remap_groups(int bid, int nwg, int per) {
+  const int npair = nwg / per;
+  if (npair & 7) return xcd_remap(bid, nwg);
+  const int xcd = bid & 7, idx = bid >> 3;
+  return ((idx / per) * 8 + xcd) * per + idx % per;
 }
 
 

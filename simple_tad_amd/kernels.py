@@ -637,10 +637,11 @@ def colsum_bf16(a, out=None):
 
 # ----------------------------------------------------------------------------- attention
 def attn_fwd(qkv, B: int, N: int, H: int, scale: float, out_dtype=None, want_lse=True, want_lo=False, q_prescaled=False, drop_p: float = 0.0,
-             seed: int = 0, d: int = 64):
+             seed: int = 0, d: int = 64, rowscale=None):
     """qkv [B*N, 3*H*d] bf16 or f16 (packed [B,N,3,H,d], d = 64 or 80) -> out [B*N, H*d], lse [B,H,N] f32.  want_lo: returns
     (out, lse, out_lo) with out_lo = what the 16-bit rounding of out dropped (for attn_bwd's delta).  q_prescaled: the q third already
-    carries scale * log2(e) (linear_fwd_qkv's q_prescale = q_prescale_of(scale))"""
+    carries scale * log2(e) (linear_fwd_qkv's q_prescale = q_prescale_of(scale)).  rowscale [B] f32 | None: the per-clip drop-path scale
+    of the residual behind this attention (tad_attn_drop_scale): clips with scale 0 are filled (out = 0), not computed"""
     op = _req16(qkv, "attn.qkv")
     out_dtype = _out16(out_dtype, op)
     if qkv.numel() != B * N * 3 * H * d:
@@ -649,9 +650,20 @@ def attn_fwd(qkv, B: int, N: int, H: int, scale: float, out_dtype=None, want_lse
     lse = torch.empty((B, H, N), dtype=torch.float32, device=qkv.device) if want_lse else None
     lo = torch.empty_like(out) if (want_lo and out.dtype in OP16_DTYPES) else None
     with _timed("attn_fwd", 4.0 * B * H * N * N * d, 2.0 * (4 + (lo is not None)) * B * N * H * d):
+        _attn_drop_scale(rowscale, B, N)
         check(_fn("tad_attn_fwd", op)(qkv.data_ptr(), out.data_ptr(), _dt(out), _p(lo), _p(lse), B, N, H, int(d), float(scale), int(bool(q_prescaled)),
                                       float(drop_p), int(seed) & 0xffffffff, _stream()), "tad_attn_fwd")
     return (out, lse, lo) if want_lo else (out, lse)
+
+
+def _attn_drop_scale(rowscale, B: int, N: int):
+    """tad_attn_drop_scale for the attention call that follows on this thread"""
+    if rowscale is None:
+        return
+    _req(rowscale, torch.float32, "attn.rowscale")
+    if rowscale.numel() != B:
+        raise _lib.TadError(f"attn: rowscale has {rowscale.numel()} elements, expected one per clip ({B})")
+    check(_lib.load().tad_attn_drop_scale(rowscale.data_ptr(), N), "tad_attn_drop_scale")
 
 
 def attn_tuning(**knobs):
@@ -661,8 +673,9 @@ def attn_tuning(**knobs):
 
 
 def attn_bwd(qkv, out, dout, lse, B: int, N: int, H: int, scale: float, out_lo=None, q_prescaled=False, drop_p: float = 0.0, seed: int = 0,
-             d: int = 64):
-    """dqkv; its q slot is the gradient of the PLAIN q whether or not the q of `qkv` is pre-scaled"""
+             d: int = 64, rowscale=None):
+    """dqkv; its q slot is the gradient of the PLAIN q whether or not the q of `qkv` is pre-scaled.  rowscale: as in attn_fwd (the dout rows
+    of a clip with scale 0 are zeros: so is its dqkv, stored without being computed)"""
     op = _req16(qkv, "attn_bwd.qkv")
     for t, n in ((out, "out"), (dout, "dout")) + (((out_lo, "out_lo"),) if out_lo is not None else ()):
         _req16(t, "attn_bwd." + n, like=op)
@@ -674,6 +687,7 @@ def attn_bwd(qkv, out, dout, lse, B: int, N: int, H: int, scale: float, out_lo=N
     dqkv = torch.empty_like(qkv)
     delta = torch.empty((_lib.load().tad_attn_bwd_scratch_bytes(B, N, H) // 4,), dtype=torch.float32, device=qkv.device)  # -rowsum(dout*out), -lse/scale
     with _timed("attn_bwd", 8.0 * B * H * N * N * d, 2.0 * (8 + (out_lo is not None)) * B * N * H * d):
+        _attn_drop_scale(rowscale, B, N)
         check(_fn("tad_attn_bwd", op)(qkv.data_ptr(), out.data_ptr(), _p(out_lo), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), delta.data_ptr(),
                                        B, N, H, int(d), float(scale), int(bool(q_prescaled)), float(drop_p), int(seed) & 0xffffffff, _stream()),
               "tad_attn_bwd")

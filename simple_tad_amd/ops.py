@@ -422,8 +422,9 @@ def set_attn_hd80_f32(on: bool):
     _attn_hd80_f32 = bool(on)
 
 
-def _attn_fwd_core(xn, qkv_w, q_bias, v_bias, B, N, H, scale, train, drop=(0.0, 0)):
-    """returns qkv, attention output, (lse, rounding residual of the output | None).  drop = (p, seed) of attention dropout."""
+def _attn_fwd_core(xn, qkv_w, q_bias, v_bias, B, N, H, scale, train, drop=(0.0, 0), rowscale=None):
+    """returns qkv, attention output, (lse, rounding residual of the output | None).  drop = (p, seed) of attention dropout.
+    rowscale: the per-clip drop-path scale [B] of the residual behind the branch (K.attn_fwd)."""
     qb = None if q_bias is None else _f32c(q_bias.detach())
     vb = None if v_bias is None else _f32c(v_bias.detach())
     hd = head_dim_of(qkv_w, H)
@@ -441,12 +442,12 @@ def _attn_fwd_core(xn, qkv_w, q_bias, v_bias, B, N, H, scale, train, drop=(0.0, 
     # the plain q; only tad_attn_fwd / tad_attn_bwd read it)
     qkv = K.linear_fwd_qkv(xn, w_bf16(qkv_w, train), qb, vb, out_dtype=None, q_prescale=K.q_prescale_of(scale) if _attn_q_prescale else 1.0)
     r = K.attn_fwd(qkv, B, N, H, scale, out_dtype=None, want_lse=train, want_lo=train and _attn_exact_delta, q_prescaled=_attn_q_prescale,
-                   drop_p=drop[0], seed=drop[1], d=hd)
+                   drop_p=drop[0], seed=drop[1], d=hd, rowscale=rowscale)
     return qkv, r[0], (r[1], r[2] if len(r) > 2 else None)
 
 
 def _attn_bwd_core(d_ao, xn, qkv, ao, lse, qkv_w, has_qkv_bias, B, N, H, scale, dx_dtype, qv_params=None, ao_lo=None, drop=(0.0, 0),
-                   q_prescaled=None, pair=None):
+                   q_prescaled=None, pair=None, rowscale=None):
     """returns dxn, dWqkv, dq_bias, dv_bias (None for what went into gradient sinks).  q_prescaled: the q contract of the forward
     that produced `qkv` (ctx.qpre).  pair = (dy, x, w) of ANOTHER bias-less weight gradient over the same rows with the same K that is due
     (the Block's proj: dy = the 16-bit gradient of its output, x = the attention output): a fifth value is returned then, that Linear's dW
@@ -459,7 +460,7 @@ def _attn_bwd_core(d_ao, xn, qkv, ao, lse, qkv_w, has_qkv_bias, B, N, H, scale, 
                                           seed=drop[1]))
     else:
         dqkv = K.attn_bwd(qkv, ao, d_ao, lse, B, N, H, scale, out_lo=ao_lo, q_prescaled=q_prescaled, drop_p=drop[0], seed=drop[1],
-                          d=head_dim_of(qkv_w, H))
+                          d=head_dim_of(qkv_w, H), rowscale=rowscale)
     dxn = K.linear_bwd_input(dqkv, wT_bf16(qkv_w, True), out_dtype=dx_dtype)
 
     def done(*r):  # (+ the pair's weight gradient by itself when it did not ride along)
@@ -619,7 +620,7 @@ class BlockFn(_Fn):
         x0 = _f32c(x).reshape(M, D)
         g1, b1, g2, b2 = _f32c(n1w), _f32c(n1b), _f32c(n2w), _f32c(n2b)
         xn1, mean1, rstd1 = K.layernorm_fwd(x0, g1, b1, eps, save_stats=train)
-        qkv, ao, (lse, ao_lo) = _attn_fwd_core(xn1, qkv_w, q_bias, v_bias, B, N, H, scale, train)
+        qkv, ao, (lse, ao_lo) = _attn_fwd_core(xn1, qkv_w, q_bias, v_bias, B, N, H, scale, train, rowscale=_f32c(dp1))
         ctx.qpre = _attn_q_prescale  # (the contract `qkv` was written under: read back by the backward)
         x1, _ = K.linear_fwd(ao, w_bf16(proj_w, train), _f32c(proj_b), out_dtype=torch.float32, epilogue=EPI_BIAS_RESIDUAL, residual=x0,
                              rowscale=_f32c(dp1), rows_per_scale=N)
@@ -672,7 +673,7 @@ class BlockFn(_Fn):
         d_ao = K.linear_bwd_input(gpb, wT_bf16(proj_w, True))
         # (the proj weight gradient rides with the qkv one: one launch for both, _attn_bwd_core)
         dxn1, dWqkv, dqb, dvb, dWp = _attn_bwd_core(d_ao, xn1, qkv, ao, lse, qkv_w, has_qb, B, N, H, scale, None, ctx.qv, ao_lo=ao_lo, q_prescaled=ctx.qpre,
-                                                     pair=(gpb, ao, proj_w))
+                                                     pair=(gpb, ao, proj_w), rowscale=dp1)
         prev = ctx.prev_link
         if prev is not None:
             gin, ginb, dg1, dbeta1, _ = layernorm_bwd_sunk(dxn1, x0, g1, mean1, rstd1, n1w, n1b, dres=gmid, want_bf16=True, rowscale=prev.dp2,
