@@ -309,7 +309,10 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 #ifdef TAD_OPND_F16
 // half pass: the values these epilogues read and write are rounded at 2^-12, so the polynomials are carried four / five degrees
-// further (|Phi error| <= 3.9e-7, gelu <= 1.9e-6 * max(1, |x|), |gelu' error| <= 6.0e-6: >= 40x below the half rounding again)
+// further (|Phi error| <= 3.9e-7, gelu <= 1.9e-6 * max(1, |x|), |gelu' error| <= 6.1e-6 -- 6.02e-6 is reached at a finite half value in the
+// f32 evaluation, tests/test_numeric_edges_cpu.py measures it: >= 40x below the half rounding again).  A NaN operand: fmed3 returns a
+// finite clamp bound for it, so gelu(NaN) = NaN * Phi = NaN, but gelu'(NaN) is FINITE -- the backward epilogue's product dy * gelu'(h)
+// carries a non-finite dy, not a non-finite h (tests/test_numeric_edges_gpu.py)
 constexpr float PHI_XMAX = 5.0f;
 constexpr float PHI_C[13] = {1.413638185e-01f, -7.029590887e-02f, 5.151792974e-02f, -4.045128240e-02f, 3.147675865e-02f, -2.321312828e-02f, 1.623608981e-02f, -1.130712491e-02f, 6.766527505e-03f, -2.526916729e-03f, 1.374596151e-03f, -1.676730979e-03f, 7.353763888e-04f};
 constexpr float DGELU_XMAX = 5.0f;

@@ -36,12 +36,20 @@ def eval32(mono, xmax, x):
     return np.float32(0.5) + xc * r
 
 
+# bf16 pass: (PHI 4.0, 8), (DGELU 4.5, 9); half pass (csrc/common.h, TAD_OPND_F16): (PHI 5.0, 12), (DGELU 5.0, 13)
+PASSES = (("bf16", "PHI", Phi, 4.0, 8), ("bf16", "DGELU", dgelu, 4.5, 9), ("f16", "PHI", Phi, 5.0, 12), ("f16", "DGELU", dgelu, 5.0, 13))
+
+
+def tables():
+    """{(pass, name): (xmax, coefficients in t, constant term first)} -- the arrays this script prints, for tests/test_numeric_edges_cpu.py"""
+    return {(p, name): (xmax, fit(fun, xmax, deg)) for p, name, fun, xmax, deg in PASSES}
+
+
 if __name__ == "__main__":
     rng = np.random.RandomState(0)
     xs = np.concatenate([np.linspace(-9, 9, 600001), rng.randn(300000) * 1.5])
-    # bf16 pass: (PHI 4.0, 8), (DGELU 4.5, 9); half pass (csrc/common.h, TAD_OPND_F16): (PHI 5.0, 12), (DGELU 5.0, 13)
-    for name, fun, xmax, deg in (("PHI", Phi, 4.0, 8), ("DGELU", dgelu, 4.5, 9), ("PHI", Phi, 5.0, 12), ("DGELU", dgelu, 5.0, 13)):
-        mono = fit(fun, xmax, deg)
+    for (_, name), (xmax, mono) in tables().items():
+        fun, deg = (Phi if name == "PHI" else dgelu), len(mono) - 1
         got = eval32(mono, xmax, xs).astype(np.float64)
         err = np.max(np.abs(got - fun(xs)))
         print(f"// {name}: XMAX {xmax}, degree {deg} in t; max |error| evaluated in f32 = {err:.2e}"
