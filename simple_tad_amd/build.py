@@ -23,9 +23,9 @@ SOURCES = ["capi.hip", "elementwise.hip", "patch_embed.hip", "layernorm.hip", "g
 # operands, exported as tad_*_f16 (csrc/common.h, csrc/opnd_f16_names.h; include/tad_mi355x.h "IEEE half operand twins").
 F16_SOURCES = ["elementwise.hip", "patch_embed.hip", "layernorm.hip", "gemm.hip", "gemm_w4.hip", "attn_fwd.hip", "attn_bwd.hip", "optim.hip"]
 # gemm_w4.hip (four waves of 128 x 128 outputs: 256 accumulator registers per lane) needs its accumulators in the AGPR half of the register
-# file: compiled without the vgpr-form switch below.  It includes gemm.hip for the kernel template.
+# file: compiled without the vgpr-form switch below.  It shares the kernel templates of gemm_kernels.h with gemm.hip.
 NO_VGPR_FORM = {"gemm_w4.hip"}
-EXTRA_DEPS = {"gemm_w4.hip": ["gemm.hip"]}
+EXTRA_DEPS = {"gemm.hip": ["gemm_kernels.h"], "gemm_w4.hip": ["gemm_kernels.h"]}
 # ema.hip and mixup.hip must round like torch (a product, a product, a sum: three roundings) and are compiled without FMA contraction.
 # A `#pragma clang fp contract(off)` is not enough: -ffp-contract=fast also lets the code generator fuse fmul + fadd by itself.
 NO_FP_CONTRACT = {"ema.hip", "mixup.hip"}

@@ -332,19 +332,6 @@ __global__ __launch_bounds__(256, HD == 64 ? 3 : 2) void attn_bwd_dq_kernel(cons
 #undef DMA_KV
 
 // ------------------------------------------------------------------------------------------------ dK, dV
-#ifndef TAD_DKV_STREAM
-#define TAD_DKV_STREAM 0  // 1: head_dim 64 streams the tile after next into the ring in two batches (see STREAM in attn_bwd_dkv_kernel).  Measured in
-                          // round 5 (tools/ab_attn.py, same results): backward pair 832.6 us without, 836.1 with -- the wait in front of the tile
-                          // barrier is wave skew, not DMA latency (the scheme that gave the four-wave weight-gradient GEMM 6 %); off
-#endif
-#ifndef TAD_DKV_ROWC_SGPR
-#define TAD_DKV_ROWC_SGPR 0  // (experiment) 1: the row constants (-lse, -delta: initial S / dP accumulators) of a half tile come from
-                             // SCALAR registers (s_load of the 2 x 32 values, requested one half tile ahead) + a move and a lane-half select per
-                             // accumulator register, instead of 8 of the 24 ds_read_b128 of a half tile.  Without dropout / head_dim 80.
-#endif
-#ifndef TAD_DKV_ABL
-#define TAD_DKV_ABL 0  // timing experiments (experiments/README.md, round 4): 1 = a quarter of the row-constant LDS reads
-#endif
 template <int HD, bool QS, bool DROP, int DMA_MODE, bool SKIP = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout,
                                                            const float* __restrict__ rowc_g, uint16_t* __restrict__ dqkv, int N, int H, int B,
@@ -439,25 +426,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __
     }                                                                                                      \
   }
 #define LOAD_QDO(buf, q0) { LOAD_Q_(buf, q0); LOAD_DO_RC_(buf, q0); }
-  // STREAM (head_dim 64): the Q / dO rows of a tile travel as TWO batches -- rows 0..31 (piece 0 of Q and of dO per wave) and rows 32..63
-  // (piece 1 of each, plus the row constants of the whole tile) -- and the tile after next streams into a ring slot as each half of it is
-  // released: rows 0..31 behind a barrier between the two half tiles, rows 32..63 behind the barrier at the end of the tile.  Every piece has
-  // at least one and a half tiles to land, and the one wait of a tile is counted (vmcnt(2): the batch requested half a tile ago stays in
-  // flight) instead of vmcnt(0) on a tile requested one tile ago.
-#define LOAD_HALF0_(buf, q0)                                                                                                   \
-  {                                                                                                                            \
-    char* ql_ = lds + (buf) * STAGE;                                                                                           \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_qkv, LDS_PTR(ql_ + wave * 1024), 16, dma_q[0] + (uint32_t)(q0) * q_step, 0, 0, 0);              \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_do, LDS_PTR(ql_ + TILE_BYTES + wave * 1024), 16, dma_do[0] + (uint32_t)(q0) * do_step, 0, 0, 0); \
-  }
-#define LOAD_HALF1_(buf, q0)                                                                                                   \
-  {                                                                                                                            \
-    char* ql_ = lds + (buf) * STAGE;                                                                                           \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_qkv, LDS_PTR(ql_ + (wave + 4) * 1024), 16, dma_q[1] + (uint32_t)(q0) * q_step, 0, 0, 0);              \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_do, LDS_PTR(ql_ + TILE_BYTES + (wave + 4) * 1024), 16, dma_do[1] + (uint32_t)(q0) * do_step, 0, 0, 0); \
-    if (wave < 2) /* wave-uniform */                                                                                           \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_rc, LDS_PTR(ql_ + 2 * TILE_BYTES + wave * 256), 4, rc_off + (uint32_t)(q0) * 4u, 0, 0, 0); \
-  }
 
   f32x16 dk[NDT], dv[NDT];  // (HD 80: of dk[2] / dv[2] only rows 0..15 = dims 64..79 mean something)
 #pragma unroll
@@ -483,23 +451,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __
   const uint32_t qtr_s = lds0 + (uint32_t)(SIDE_OFF + (4 * (lane >> 5) + ((lane & 15) >> 2)) * 32 + 8 * (lane & 3));
 
   const int nt = (N + 63) / 64;
-  constexpr bool STREAM = TAD_DKV_STREAM && !X && DMA_MODE == 0;
-  constexpr bool RC_SGPR = TAD_DKV_ROWC_SGPR && !X && !DROP && DMA_MODE == 0;
-  float rc_s[32], rc_d[32];  // (RC_SGPR) -lse / -delta of the 32 rows of the coming half tile, wave-uniform
-  const float* const rc_base = rowc_g + ((int64_t)b * H + head) * N;
-  auto rc_load = [&](int row0) {  // row0 .. row0 + 31 (clamped by the caller: rows >= N are neutralised in the ragged branch)
-    if constexpr (RC_SGPR) {
-      const int r0 = __builtin_amdgcn_readfirstlane(row0);
-#pragma unroll
-      for (int i = 0; i < 32; ++i) {
-        rc_s[i] = __builtin_nontemporal_load(rc_base + bhn + r0 + i);
-        rc_d[i] = __builtin_nontemporal_load(rc_base + r0 + i);
-      }
-    }
-  };
-  rc_load(0);
   LOAD_QDO(0, 0);
-  if (STREAM && 1 < nt) { LOAD_HALF0_(1, 64); LOAD_HALF1_(1, 64); }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   asm volatile("" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -518,18 +470,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __
     const bool more = t + 1 < nt;     // is there a tile to request during this one?
     constexpr int nbuf = BUF ^ 1;     // its ring slot ...
     const int nq0 = (t + 1) * 64;     // ... and first query row
-    if (more && DMA_MODE == 0 && !STREAM) LOAD_QDO(nbuf, nq0);
-    const bool more2 = t + 2 < nt;  // (STREAM) is there a tile after next to request into this slot?
+    if (more && DMA_MODE == 0) LOAD_QDO(nbuf, nq0);
     static_for<0, 2>([&](auto qtc) {
       constexpr int qt = decltype(qtc)::value;
-      if constexpr (STREAM && qt == 1) {
-        // every wave is done with rows 0..31 of this slot (their fragments were consumed by the first half tile's MFMAs): the tile
-        // after next starts to stream into them
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (more2) LOAD_HALF0_(BUF, (t + 2) * 64);
-      }
       if (!wave_live) return;  // (see the dQ kernel: waves whose 32 keys all lie past the sequence only stage tiles)
       constexpr int HT = qt * 32 * 128;  // byte offset of the half tile inside a tile
       if (t * 64 + 32 * qt >= N) return;  // half tile of query rows past the sequence: P = dS = 0 there anyway
@@ -538,16 +481,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __
       constexpr int NTR = X ? 12 : 8;    // transposed reads per batch
       f32x4 si[4], di[4];
       op16x8 qa[NKS], da[NKS];
-      if constexpr (!RC_SGPR)
       static_for<0, 4>([&](auto r4c) {
         constexpr int r4 = decltype(r4c)::value;
-        if constexpr (!(TAD_DKV_ABL & 1) || r4 == 0) {
-          si[r4] = lds_read_b128<f32x4, SO + (qt * 32 + 8 * r4) * 4>(rca);
-          di[r4] = lds_read_b128<f32x4, SO + 256 + (qt * 32 + 8 * r4) * 4>(rca);
-        } else {  // (timing experiment: one quarter of the row-constant reads, values wrong)
-          si[r4] = si[0];
-          di[r4] = di[0];
-        }
+        si[r4] = lds_read_b128<f32x4, SO + (qt * 32 + 8 * r4) * 4>(rca);
+        di[r4] = lds_read_b128<f32x4, SO + 256 + (qt * 32 + 8 * r4) * 4>(rca);
       });
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
@@ -582,7 +519,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __
   }
       if constexpr (DMA_MODE != 3 && !X) {
         TR_ISSUE(0);
-        if constexpr (!RC_SGPR) lds_wait<16>(si[0], si[1], si[2], si[3], di[0], di[1], di[2], di[3]);  // (the counter saturates at 15: this also covers the row fragments)
+        lds_wait<16>(si[0], si[1], si[2], si[3], di[0], di[1], di[2], di[3]);  // (the counter saturates at 15: this also covers the row fragments)
         lds_wait<NTR>(qa[0], qa[1], qa[2], qa[3], da[0], da[1], da[2], da[3]);
       } else {  // ablation (timing only): no transposed reads at all -- how much of the kernel is LDS read traffic?
         lds_wait<0>(si[0], si[1], si[2], si[3], di[0], di[1], di[2], di[3]);
@@ -590,20 +527,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __
         if constexpr (X) lds_wait<0>(qa[NKS - 1], da[NKS - 1]);
       }
       f32x16 s, dp;
-      if constexpr (RC_SGPR) {
-        // accumulator register r of lane half h5 <-> row (r & 3) + 8 (r >> 2) + 4 h5 of the half tile: one scalar per lane half
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          s[r] = h5 ? rc_s[(r & 3) + 8 * (r >> 2) + 4] : rc_s[(r & 3) + 8 * (r >> 2)];
-          dp[r] = h5 ? rc_d[(r & 3) + 8 * (r >> 2) + 4] : rc_d[(r & 3) + 8 * (r >> 2)];
-        }
-        // request the constants of the next half tile: they land behind this half tile's matrix work
-        const int nrow = min(t * 64 + 32 * qt + 32, N - 32);
-        rc_load(nrow);
-      } else {
 #pragma unroll
       for (int r = 0; r < 16; ++r) { s[r] = si[r >> 2][r & 3]; dp[r] = DROP ? 0.f : di[r >> 2][r & 3]; }
-      }
       if (t * 64 + 32 * qt + 32 > N) {  // ragged half tile (N % 32 != 0): rows >= N get exp2(c*(s - 3e30)) = 0 and delta = 0
         // (one lane value against 16 literals: written as `row0 + literal + 4 h5 >= N` the compiler computed the 16 row indices in
         // front of this branch, i.e. in every half tile)
@@ -657,19 +582,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __
 #undef TR_ISSUE
 #undef TR_MFMA
     });
-    if constexpr (STREAM) {
-      // the next tile has landed (its second batch was requested a whole tile ago; only the two pieces requested between the half tiles
-      // of this one may still be in flight); every wave is done with this slot: its rows 32..63 and row constants take the tile after next
-      if (more2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (more2) LOAD_HALF1_(BUF, (t + 2) * 64);
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
   };
   for (int t = 0; t < nt; t += 2) {
     dkv_tile(std::integral_constant<int, 0>{}, t);

@@ -18,35 +18,6 @@ constexpr int KV_TILE = 64; // keys per LDS tile
 constexpr int Q_WAVE = 32;  // query rows per wave
 constexpr int Q_BLOCK = 128;
 constexpr float RESCALE_THR = 8.0f;  // log2 units
-#ifndef TAD_FWD_ROWSUM_VALU
-#define TAD_FWD_ROWSUM_VALU 0  // 1: row sums of P as f32 adds of the unrounded exponentials + one half swap per tile, instead of 4 MFMAs
-#endif
-#ifndef TAD_FWD_PV_F16
-#define TAD_FWD_PV_F16 0  // (bf16 build only; experiment) 1: the P V product in IEEE half -- P in [0, 2^8] rounded to f16 (11 significant bits instead
-                          // of 8), the V fragments converted bf16 -> f16 in registers (exact while |v| < 65504; 3 vector instructions per pair)
-#endif
-#if defined(TAD_OPND_F16) && TAD_FWD_PV_F16
-#undef TAD_FWD_PV_F16
-#define TAD_FWD_PV_F16 0
-#endif
-#ifndef TAD_FWD_CNEG
-#define TAD_FWD_CNEG 0  // (experiment) 1 (pre-scaled q, no dropout, head_dim 64): the running row maximum is subtracted by the matrix pipe -- sixteen registers hold
-                        // -m_run and are the C operand of the first score product of every tile -- instead of one v_sub per score (32 of ~110 vector
-                        // instructions per tile); costs 16 registers
-#endif
-#ifndef TAD_FWD_PIPE
-#define TAD_FWD_PIPE 0  // (experiment) 1: the exponentials / 16-bit packing of key group g + 1 are placed between the P V matrix instructions of group g
-                        // (program order pinned by scheduling barriers), instead of all exponentials in front of all P V products
-#endif
-#ifndef TAD_FWD_STAGGER
-#define TAD_FWD_STAGGER 0  // (experiment) N: a wave sleeps (hardware wave slot & 3) x N x 256 cycles before the first tile (see the loop head)
-#endif
-#ifndef TAD_FWD_ABL
-#define TAD_FWD_ABL 0  // timing-only ablations of the forward tile body (experiments; WRONG results): bit 0 no exponentials, 1 no row
-                       // maximum, 2 no P V products / V reads / row sums, 3 no K Q^T products / K reads, 4 no DMA and no barrier in
-                       // the loop, 5 no V reads (P V products fed from the K fragments' registers)
-#endif
-
 
 __device__ __forceinline__ int swk(int key) { return (key >> 1) & 7; }
 __device__ __forceinline__ int swv(int key) { return ((key >> 1) & 1) << 2; }
@@ -62,32 +33,6 @@ __device__ __forceinline__ float half_swap_sum(float x) {
 }
 
 typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-#if TAD_FWD_PV_F16
-typedef __attribute__((ext_vector_type(8))) _Float16 pv16x8;
-typedef _Float16 pv16_t;
-#define PV_MFMA_32x32x16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
-#define PV_MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0)
-// eight bf16 -> eight f16: each 32-bit word holds two bf16; word << 16 / word & 0xffff0000 are their f32 images
-__device__ __forceinline__ pv16x8 v_to_pv(const op16x8& v) {
-  typedef __attribute__((ext_vector_type(4))) uint32_t w32x4;
-  const w32x4 w = __builtin_bit_cast(w32x4, v);
-  typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-  pv16x8 r;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const h2 t = __builtin_bit_cast(h2, __builtin_amdgcn_cvt_pkrtz(__uint_as_float(w[i] << 16), __uint_as_float(w[i] & 0xffff0000u)));  // (exact: 8 significant bits)
-    r[2 * i] = t[0];
-    r[2 * i + 1] = t[1];
-  }
-  return r;
-}
-#else
-typedef op16x8 pv16x8;
-typedef op16_t pv16_t;
-#define PV_MFMA_32x32x16(a, b, c) TAD_MFMA_32x32x16(a, b, c)
-#define PV_MFMA_16x16x32(a, b, c) TAD_MFMA_16x16x32(a, b, c)
-__device__ __forceinline__ pv16x8 v_to_pv(const op16x8& v) { return v; }
-#endif
 
 // DMA_MODE: see attn_bwd.hip (0: next tile's LDS-DMA pieces at the top of the tile; 2: timing-only ablation, ablation builds)
 // QS: the q third of qkv already carries the factor scale * log2(e) (tad_linear_fwd_qkv's q_prescale): the scores leave the matrix
@@ -105,10 +50,9 @@ __device__ __forceinline__ pv16x8 v_to_pv(const op16x8& v) { return v; }
 // without SKIP the kernel does not look at clip_scale.
 constexpr float SKIP_LSE = 1e30f;  // finite, and exp(score - SKIP_LSE) = 0: a backward that does compute such a row gets P = 0, never inf * 0
 template <int HD, bool OUT_BF16, bool QS, bool DROP, int DMA_MODE, bool SKIP = false>
-__global__ __launch_bounds__(256, TAD_FWD_ROWSUM_VALU ? 4 : 1) void attn_fwd_kernel(const uint16_t* __restrict__ qkv, void* __restrict__ out,
+__global__ __launch_bounds__(256, 1) void attn_fwd_kernel(const uint16_t* __restrict__ qkv, void* __restrict__ out,
                                                        uint16_t* __restrict__ out_lo, float* __restrict__ lse, int N, int H, int B,
                                                        float scale, const Drop drop, const float* __restrict__ clip_scale) {
-  constexpr bool VSUM = TAD_FWD_ROWSUM_VALU || DROP;  // row sums of P by vector adds instead of MFMAs
   static_assert(HD == 64 || HD == 80, "head dim");
   constexpr bool X = HD == 80;                                                   // 16 extra dims in the side images
   constexpr int NKS = HD / 16, NDT = X ? 3 : 2;                                  // k-steps of the score product, d tiles of the output
@@ -230,12 +174,12 @@ __global__ __launch_bounds__(256, TAD_FWD_ROWSUM_VALU ? 4 : 1) void attn_fwd_ker
   // The selector A has ones in rows 0 and 8 over kg {0, 2} and in rows 4 and 12 over kg {1, 3}; output register 0 of lane l is
   // D[4 (l>>4)][l & 15]: lanes 0-15 and 32-47 get the sum of query l & 15, lanes 16-31 and 48-63 that of query 16 + (l & 15) -- each
   // lane its own query (lane & 31), no cross-lane step.
-  pv16x8 sel;
+  op16x8 sel;
   {
     const int m = lane & 15, kg = lane >> 4;
     const bool on = ((m & 7) == 0 && (kg & 1) == 0) || ((m & 7) == 4 && (kg & 1) == 1);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) sel[e] = (pv16_t)(on ? 1.0f : 0.0f);
+    for (int e = 0; e < 8; ++e) sel[e] = (op16_t)(on ? 1.0f : 0.0f);
   }
 
   // One K/V tile of 64 keys out of LDS ring slot BUF (a literal: every LDS address below is then lane-constant + immediate).
@@ -250,44 +194,27 @@ __global__ __launch_bounds__(256, TAD_FWD_ROWSUM_VALU ? 4 : 1) void attn_fwd_ker
   // output registers cost 24-56 VGPRs (a wave per SIMD).  One body, one v_sub per score.
   const int nt = (N + KV_TILE - 1) / KV_TILE;
   const uint32_t drop_row = (uint32_t)((b * H + head) * N + min(q0 + ql, N - 1));  // (DROP) the lane's row of the keep mask
-  constexpr bool CNEG = TAD_FWD_CNEG && QS && !DROP && !X && !TAD_FWD_ABL;
-  float m_run = CNEG ? 0.f : -1e30f, l_run = 0.f;  // running row maximum (units of the scores as the matrix pipe delivers them), row sum of P
-  f32x16 negm;                        // (CNEG) -m_run in all sixteen registers: the C operand of a tile's first score products
-#pragma unroll
-  for (int r = 0; r < 16; ++r) negm[r] = 0.f;
+  float m_run = -1e30f, l_run = 0.f;  // running row maximum (units of the scores as the matrix pipe delivers them), row sum of P
   auto fwd_tile = [&](auto BUFC, const int T) {
     constexpr int BUF = decltype(BUFC)::value;
     const int kv0 = T * KV_TILE;
-    if (T + 1 < nt && DMA_MODE == 0 && !(TAD_FWD_ABL & 16)) DMA_TILE(BUF ^ 1, kv0 + KV_TILE);
+    if (T + 1 < nt && DMA_MODE == 0) DMA_TILE(BUF ^ 1, kv0 + KV_TILE);
     if (wave_live) {  // waves whose 32 query rows all lie past the sequence only help staging the tiles
       op16x8 kf[2][NKS];
       f32x16 s[2];
-      if constexpr (!(TAD_FWD_ABL & 8)) {
       static_for<0, 2 * NKS>([&](auto ic) {
         constexpr int i_ = decltype(ic)::value, kt = i_ / NKS, ks = i_ % NKS;
         kf[kt][ks] = lds_read_b128<op16x8, BUF * BUF_BYTES + kt * 32 * (ks < 4 ? 128 : 32)>(k_rd[ks]);
       });
-      if constexpr (!CNEG) {
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
-      }
       static_for<0, 2 * NKS>([&](auto ic) {
         constexpr int i_ = decltype(ic)::value, kt = i_ / NKS, ks = i_ % NKS;
         lds_wait<2 * NKS - 1 - i_>(kf[kt][ks]);
-        if constexpr (CNEG && ks == 0) s[kt] = TAD_MFMA_32x32x16(kf[kt][ks], qf[ks], negm);  // scores - m_run
-        else s[kt] = TAD_MFMA_32x32x16(kf[kt][ks], qf[ks], s[kt]);
+        s[kt] = TAD_MFMA_32x32x16(kf[kt][ks], qf[ks], s[kt]);
       });
-      } else {
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) s[kt][r] = o[kt][r] * 1e-3f + (float)T;  // (something live and data dependent)
-#pragma unroll
-          for (int ks = 0; ks < NKS; ++ks) kf[kt][ks] = qf[ks];
-        }
-      }
       if (kv0 + KV_TILE > N) {  // ragged last tile: mask keys >= N (one lane value against 32 literals: written with the key
                                 // index on the left the compiler computes all 32 indices in front of this branch)
         int lim = N - kv0 - 4 * h5;
@@ -299,37 +226,15 @@ __global__ __launch_bounds__(256, TAD_FWD_ROWSUM_VALU ? 4 : 1) void attn_fwd_ker
             if (kt * 32 + (r & 3) + 8 * (r >> 2) >= lim) s[kt][r] = -1e30f;
       }
       float mloc = s[0][0];
-      if constexpr (!(TAD_FWD_ABL & 2)) {
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, s[kt][r]);
-      }
       // deferred rescale: keep the old running max while the tile max exceeds it by < RESCALE_THR (log2 units): P may reach
       // 2^THR instead of 1 (harmless in f32 / 16 bits) and the O-wide multiply disappears from almost every tile.  The decision
       // precedes the exponentiation of this tile (textbook order).
       const float m_tile = half_swap_max(mloc);
       const float cq = QS ? 1.f : c;  // log2 units per score unit
-      if constexpr (CNEG) {
-        // m_tile is relative to m_run here.  The first tile always moves the reference to its own maximum (m_run starts at 0, not at -inf: -inf
-        // as a C operand would swallow the scores); later tiles only when they exceed it by the threshold
-        if (T == 0 || __any(m_tile > RESCALE_THR)) {
-          const float d = T == 0 ? m_tile : fmaxf(m_tile, 0.f);  // shift of the reference
-          const float alpha = fast_exp2(-d);
-          m_run += d;
-          l_run *= alpha;
-#pragma unroll
-          for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) negm[r] = -m_run;
-#pragma unroll
-          for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[kt][r] -= d;
-        }
-      } else
       if (__any((m_tile - m_run) * cq > RESCALE_THR)) {
         const float m_new = fmaxf(m_run, m_tile);
         const float alpha = fast_exp2((m_run - m_new) * cq);
@@ -341,41 +246,23 @@ __global__ __launch_bounds__(256, TAD_FWD_ROWSUM_VALU ? 4 : 1) void attn_fwd_ker
           for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
       }
       const float mc = m_run * c;  // (plain q only)
-      pv16x8 pf[2][2];
+      op16x8 pf[2][2];
       float psum[4] = {0.f, 0.f, 0.f, 0.f};
-      constexpr bool PIPE = TAD_FWD_PIPE && !X && !DROP && !TAD_FWD_ABL;
       // elements [j0, j1) of key group g_ = 2 kt + s2 (keys 16 g_ .. 16 g_ + 15): exponential, row-sum contribution, 16-bit P
       auto p_part = [&](auto gc, int j0, int j1) {
         constexpr int g_ = decltype(gc)::value, kt = g_ >> 1, s2 = g_ & 1;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           if (j < j0 || j >= j1) continue;
-          const float sh = CNEG ? s[kt][8 * s2 + j] : QS ? s[kt][8 * s2 + j] - m_run : fmaf(s[kt][8 * s2 + j], c, -mc);
-          const float pe = (TAD_FWD_ABL & 1) ? sh : fast_exp2(sh);
-          if (VSUM) psum[(j + 8 * s2) & 3] += pe;
-          if (DROP) pf[kt][s2][j] = (pv16_t)(drop_keep(drop, drop_row, (uint32_t)(kv0 + kt * 32 + acc_row(8 * s2 + j, h5))) ? pe * drop.inv_keep : 0.f);
-          else pf[kt][s2][j] = (pv16_t)pe;
+          const float sh = QS ? s[kt][8 * s2 + j] - m_run : fmaf(s[kt][8 * s2 + j], c, -mc);
+          const float pe = fast_exp2(sh);
+          if (DROP) psum[(j + 8 * s2) & 3] += pe;
+          if (DROP) pf[kt][s2][j] = (op16_t)(drop_keep(drop, drop_row, (uint32_t)(kv0 + kt * 32 + acc_row(8 * s2 + j, h5))) ? pe * drop.inv_keep : 0.f);
+          else pf[kt][s2][j] = (op16_t)pe;
         }
       };
-      if constexpr (PIPE) {
-        p_part(std::integral_constant<int, 0>{}, 0, 8);
-      } else {
-        static_for<0, 4>([&](auto gc) { p_part(gc, 0, 8); });
-      }
+      static_for<0, 4>([&](auto gc) { p_part(gc, 0, 8); });
       f32x4 rs = {0.f, 0.f, 0.f, 0.f};
-      if constexpr (TAD_FWD_ABL & 4) {
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2) asm volatile("" ::"v"(pf[kt][s2]));
-      } else if constexpr (TAD_FWD_ABL & 32) {
-        static_for<0, 4>([&](auto gc) {
-          constexpr int g_ = decltype(gc)::value;
-          rs = PV_MFMA_16x16x32(sel, pf[g_ >> 1][g_ & 1], rs);
-#pragma unroll
-          for (int dt = 0; dt < 2; ++dt) o[dt] = PV_MFMA_32x32x16(v_to_pv(kf[dt][g_]), pf[g_ >> 1][g_ & 1], o[dt]);
-        });
-      } else {
       // V^T fragments through the asm reads of common.h (the builtin made the compiler drain the DMA of the next tile here):
       // group g = 2 kt + s2 covers keys 16g .. 16g+15; the reads of group g+1 are issued before the MFMAs of group g
       s16x4 vlo[2][NDT], vhi[2][NDT];  // [group parity][dt]
@@ -395,49 +282,20 @@ __global__ __launch_bounds__(256, TAD_FWD_ROWSUM_VALU ? 4 : 1) void attn_fwd_ker
       static_for<0, 4>([&](auto gc) {
         constexpr int g_ = decltype(gc)::value, par = g_ & 1;
         if constexpr (g_ < 3) v_issue(std::integral_constant<int, g_ + 1>{}, std::integral_constant<int, par ^ 1>{});
-        if constexpr (PIPE) {
-          // group g's three matrix instructions with group g + 1's exponentials between them, in this order
-          __builtin_amdgcn_sched_barrier(0);
-          rs = PV_MFMA_16x16x32(sel, pf[g_ >> 1][g_ & 1], rs);
-          __builtin_amdgcn_sched_barrier(0);
-          if constexpr (g_ < 3) p_part(std::integral_constant<int, g_ + 1>{}, 0, 2);
-          lds_wait<(g_ < 3 ? 4 : 0)>(vlo[par][0], vhi[par][0], vlo[par][1], vhi[par][1]);
-          __builtin_amdgcn_sched_barrier(0);
-          o[0] = PV_MFMA_32x32x16(v_to_pv(join_tr(vlo[par][0], vhi[par][0])), pf[g_ >> 1][g_ & 1], o[0]);
-          __builtin_amdgcn_sched_barrier(0);
-          if constexpr (g_ < 3) p_part(std::integral_constant<int, g_ + 1>{}, 2, 5);
-          __builtin_amdgcn_sched_barrier(0);
-          o[1] = PV_MFMA_32x32x16(v_to_pv(join_tr(vlo[par][1], vhi[par][1])), pf[g_ >> 1][g_ & 1], o[1]);
-          __builtin_amdgcn_sched_barrier(0);
-          if constexpr (g_ < 3) p_part(std::integral_constant<int, g_ + 1>{}, 5, 8);
-          __builtin_amdgcn_sched_barrier(0);
-        } else {
-        if (!VSUM) rs = PV_MFMA_16x16x32(sel, pf[g_ >> 1][g_ & 1], rs);
+        if (!DROP) rs = TAD_MFMA_16x16x32(sel, pf[g_ >> 1][g_ & 1], rs);
         if constexpr (X) lds_wait<(g_ < 3 ? 6 : 0)>(vlo[par][0], vhi[par][0], vlo[par][1], vhi[par][1], vlo[par][NDT - 1], vhi[par][NDT - 1]);
         else lds_wait<(g_ < 3 ? 4 : 0)>(vlo[par][0], vhi[par][0], vlo[par][1], vhi[par][1]);
 #pragma unroll
-        for (int dt = 0; dt < NDT; ++dt) o[dt] = PV_MFMA_32x32x16(v_to_pv(join_tr(vlo[par][dt], vhi[par][dt])), pf[g_ >> 1][g_ & 1], o[dt]);
-        }
+        for (int dt = 0; dt < NDT; ++dt) o[dt] = TAD_MFMA_32x32x16(join_tr(vlo[par][dt], vhi[par][dt]), pf[g_ >> 1][g_ & 1], o[dt]);
       });
-      }
-      if (VSUM) l_run += half_swap_sum((psum[0] + psum[1]) + (psum[2] + psum[3]));
+      if (DROP) l_run += half_swap_sum((psum[0] + psum[1]) + (psum[2] + psum[3]));
       else l_run += rs[0];  // the lane's own query: see `sel`
     }
-    if constexpr (!(TAD_FWD_ABL & 16)) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
   };
 
   DMA_TILE(0, 0);
-#if TAD_FWD_STAGGER
-  {
-    // (experiment) the workgroups that share a CU start together and run identical tile bodies: are the waves of a SIMD phase-locked (all in their
-    // MFMA block, then all in their softmax)?  Delay a wave by (its hardware wave slot & 3) quarters of a tile body before the first barrier.
-    const uint32_t slot = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 4) & 3u;  // hwreg(HW_REG_HW_ID, 0, 4): wave slot in its SIMD
-    for (uint32_t i = 0; i < slot * (uint32_t)TAD_FWD_STAGGER; ++i) __builtin_amdgcn_s_sleep(4);  // 4 x 64 cycles
-  }
-#endif
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   for (int t = 0; t < nt; t += 2) {

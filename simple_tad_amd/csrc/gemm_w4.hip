@@ -1,10 +1,10 @@
-// The four-wave instantiations of gemm_nt_kernel (csrc/gemm.hip, "W4"): 256 x 256 tile, 2 x 2 waves of 128 x 128 outputs, one wave per
+// The four-wave instantiations of gemm_nt_kernel (csrc/gemm_kernels.h, "W4"): 256 x 256 tile, 2 x 2 waves of 128 x 128 outputs, one wave per
 // SIMD.  A wave's 256 accumulator registers only fit the AGPR half of gfx950's unified register file, so this translation unit is
 // compiled WITHOUT -mllvm -amdgpu-mfma-vgpr-form=1 (simple_tad_amd/build.py), which the rest of the library uses to keep its (at most 128)
-// accumulators in arch VGPRs.  The kernel template, its epilogues and the parameter block are those of gemm.hip; only the K loop differs.
-#define TAD_GEMM_W4_TU
-#include "gemm.hip"
-// (gemm.hip's TAD_NAMESPACE_BEGIN is still open here: the part of that file that closes it is skipped under TAD_GEMM_W4_TU)
+// accumulators in arch VGPRs.  The kernel template, its epilogues and the parameter block are those of gemm_kernels.h; only the K loop differs.
+#include "gemm_kernels.h"
+
+TAD_NAMESPACE_BEGIN
 
 // ------------------------------------------------------------------------------------------------------------------------------------
 // gemm_tn with four waves (weight gradients): slab[s][n][k] = sum over the rows m of split s of P[m][n] * Q[m][k], one 256 x 256 tile of
@@ -30,25 +30,9 @@ __device__ __forceinline__ void mfma_16x16x32_vgpr(f32x4& d, const op16x8& a, co
 #endif
 }
 
-// timing experiments (compile-time, wrong results): the loop without its LDS-DMA pieces / fragment reads / wait + barrier
-#ifndef TNW4_ABL_NO_DMA
-#define TNW4_ABL_NO_DMA 0
-#endif
-#ifndef TNW4_ABL_NO_READS
-#define TNW4_ABL_NO_READS 0
-#endif
-#ifndef TNW4_ABL_NO_SYNC
-#define TNW4_ABL_NO_SYNC 0
-#endif
-#ifndef TNW4_2BAR
-#define TNW4_2BAR 1  // 1: TWO barriers per reduction tile (top and half) and ONE LDS-DMA piece behind every fragment group of BOTH halves -- the
-                     // k-step-0 rows of a ring slot are released at the top of the tile, the k-step-1 rows at the half, so the tile after next
-                     // streams into them as they become free and every wait leaves a whole tile's pieces (16) in flight; 0: one barrier, the 16
-                     // pieces behind the groups of the second half, vmcnt(0)
-#endif
-#ifndef TNW4_DMA_GROUPS
-#define TNW4_DMA_GROUPS 8  // groups of the second half over which the 16 LDS-DMA pieces of a reduction tile are spread: 8, 4 or 2
-#endif
+// TWO barriers per reduction tile (top and half) and ONE LDS-DMA piece behind every fragment group of BOTH halves -- the k-step-0 rows of a
+// ring slot are released at the top of the tile, the k-step-1 rows at the half, so the tile after next streams into them as they become
+// free and every wait leaves a whole tile's pieces (16) in flight
 __global__ __launch_bounds__(256, 1) void gemm_tn_w4_kernel(const GemmTN p) {
   constexpr int NW = 4, BM = 256, BN = 256, PROW = BM * 2, QROW = BN * 2, P_BYTES = BK * PROW, Q_BYTES = BK * QROW, STAGE_BYTES = P_BYTES + Q_BYTES;
   static_assert(STAGE_BYTES == 65536 && PROW == 512, "slot toggle = bit 16 of the LDS address");
@@ -146,17 +130,15 @@ __global__ __launch_bounds__(256, 1) void gemm_tn_w4_kernel(const GemmTN p) {
     lds_wait<0>(ql[0][4], qh[0][4], ql[0][5], qh[0][5], ql[0][6], qh[0][6], ql[0][7], qh[0][7]);
     lds_wait<0>(pl[0][0], ph[0][0], pl[0][1], ph[0][1], pl[0][2], ph[0][2], pl[0][3], ph[0][3]);
     lds_wait<0>(pl[0][4], ph[0][4], pl[0][5], ph[0][5], pl[0][6], ph[0][6], pl[0][7], ph[0][7]);
-    if constexpr (TNW4_2BAR && !TNW4_ABL_NO_SYNC) {
-      // top of the tile: every wave holds this tile's k-step-0 fragments -> those rows of the slot are free; this tile's k-step-1 rows
-      // (requested two tiles ago, 16 younger pieces behind them) have landed
-      if constexpr (NEXT2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      block_barrier();
-    }
+    // top of the tile: every wave holds this tile's k-step-0 fragments -> those rows of the slot are free; this tile's k-step-1 rows
+    // (requested two tiles ago, 16 younger pieces behind them) have landed
+    if constexpr (NEXT2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    block_barrier();
     static_for<0, 8>([&](auto gc) {
       constexpr int i = decltype(gc)::value;
-      if constexpr (TNW4_2BAR && NEXT2 && !TNW4_ABL_NO_DMA) { TNW4_PIECE(slot, TNW4_K0IDX(i), t + 2); }
-      if constexpr (!TNW4_ABL_NO_READS) { TNW4_READ(1, 1, i); }
+      if constexpr (NEXT2) { TNW4_PIECE(slot, TNW4_K0IDX(i), t + 2); }
+      TNW4_READ(1, 1, i);
       const op16x8 pf = join_tr(pl[0][i], ph[0][i]);
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[i][j] = TAD_MFMA_16x16x32(join_tr(ql[0][j], qh[0][j]), pf, acc[i][j]);
@@ -174,29 +156,16 @@ __global__ __launch_bounds__(256, 1) void gemm_tn_w4_kernel(const GemmTN p) {
     lds_wait<0>(pl[1][0], ph[1][0], pl[1][1], ph[1][1], pl[1][2], ph[1][2], pl[1][3], ph[1][3]);
     lds_wait<0>(pl[1][4], ph[1][4], pl[1][5], ph[1][5], pl[1][6], ph[1][6], pl[1][7], ph[1][7]);
     if constexpr (NEXT) {
-      if constexpr (!TNW4_ABL_NO_SYNC) {
-        if constexpr (TNW4_2BAR && NEXT2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");  // (the next tile's k-step-0 rows; 16 younger pieces stay in flight)
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        block_barrier();
-      }
+      if constexpr (NEXT2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");  // (the next tile's k-step-0 rows; 16 younger pieces stay in flight)
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      block_barrier();
 #pragma unroll
       for (int i = 0; i < 8; ++i) { p_rd[i] ^= (uint32_t)STAGE_BYTES; q_rd[i] ^= (uint32_t)STAGE_BYTES; }
     }
     static_for<0, 8>([&](auto gc) {
       constexpr int i = decltype(gc)::value;
-      if constexpr (NEXT2) {
-        // the 16 pieces of the tile after next go out behind the first TNW4_DMA_GROUPS groups (the last piece is needed one half tile
-        // + one tile later: spread over all eight groups it had 0.9 us to land)
-        if constexpr (TNW4_2BAR) {
-          if constexpr (!TNW4_ABL_NO_DMA) { TNW4_PIECE(slot, TNW4_K1IDX(i), t + 2); }
-        } else if constexpr (i < TNW4_DMA_GROUPS && !TNW4_ABL_NO_DMA) {
-          static_for<0, 16 / TNW4_DMA_GROUPS>([&](auto pc) {
-            constexpr int piece = i * (16 / TNW4_DMA_GROUPS) + decltype(pc)::value;
-            TNW4_PIECE(slot, piece, t + 2);
-          });
-        }
-      }
-      if constexpr (NEXT && !TNW4_ABL_NO_READS) { TNW4_READ(0, 0, i); }
+      if constexpr (NEXT2) { TNW4_PIECE(slot, TNW4_K1IDX(i), t + 2); }
+      if constexpr (NEXT) { TNW4_READ(0, 0, i); }
       const op16x8 pf = join_tr(pl[1][i], ph[1][i]);
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[i][j] = TAD_MFMA_16x16x32(join_tr(ql[1][j], qh[1][j]), pf, acc[i][j]);

@@ -17,7 +17,7 @@
 
 TAD_NAMESPACE_BEGIN
 
-__device__ __forceinline__ int pe_sw(int row) { return ((row >> 1) & 7) ^ (((row >> 4) & 3) << 1); }  // = gemm.hip's sw_nt
+__device__ __forceinline__ int pe_sw(int row) { return ((row >> 1) & 7) ^ (((row >> 4) & 3) << 1); }  // = gemm_kernels.h's sw_nt
 
 struct PatchEmbedImplicit {
   const float* x;       // [B, C, T, H, W]
