@@ -363,6 +363,35 @@ int tad_mixup_target(const int32_t* plan, const int64_t* labels, float* out, int
 int tad_soft_target_ce(const float* logits, const float* target, const int64_t* labels, float smoothing, float* loss, float* dlogits,
                        int B, int num_classes, tad_stream_t stream);
 
+/* RandomErasing of the fine-tune recipe on the device (random_erasing.py:151-173, applied by the datasets to every normalised clip
+ * with --reprob 0.25 --remode pixel --recount 1, max_area 0.1, one box per clip shared by its frames).
+ * boxes: int32 [n_boxes][TAD_ERASE_BOX_WORDS], one row per box in the order the reference writes them:
+ *   {sample, mode, t0, t1, y0, y1, x0, x1}:  x[sample][:, t0:t1, y0:y1, x0:x1] = noise of `mode`
+ *   Where boxes of one sample overlap, an element ends with the value of the LAST row that covers it (the reference's write order):
+ *   a row leaves out every element that a later valid row of the same sample covers, so the result does not depend on the grid.
+ * Noise (the one definition; csrc/erasing.hip implements it, tests/erasing_recipe.py restates it in float64).  With uint32 arithmetic,
+ *   hash32(a, b, s) = fin(a * 0x9E3779B1 + b * 0x85EBCA77 + s),
+ *   fin(v): v ^= v >> 16; v *= 0x7FEB352D; v ^= v >> 15; v *= 0x846CA68B; v ^= v >> 16   (the hash of the attention dropout mask),
+ * and box = the row's index in the table, c = channel, t = frame, dy = y - y0, dx = x - x0 (y0, x0 after the cut to the clip):
+ *   k  = hash32(dy, dx, hash32(c, t, hash32(sample, box, seed)))         TAD_ERASE_PIXEL: one value per element
+ *   k  = hash32(0, 0, hash32(c, t, hash32(sample, box, seed)))           TAD_ERASE_RAND: one value per (box, frame, channel)
+ *   k2 = hash32(0, 0, k + 0x6A09E667)
+ *   u1 = ((k >> 8) + 1) * 2^-24 in (0, 1],  u2 = (k2 >> 8) * 2^-24 in [0, 1)
+ *   value = sqrtf(-2 * logf(u1)) * cospif(2 * u2)                        Box-Muller, the accurate f32 functions; |value| <= 5.77
+ *   TAD_ERASE_CONST: 0.0f.
+ *   A value depends on (seed, sample, box, c, t, dy, dx) alone: not on the grid, the vector width or the alignment of x.
+ * tad_erase_plan_check: host-side check of a HOST copy of the table (modes, 0 <= sample < B, boxes inside the clip); no launch.
+ * tad_erase_clips: x = contiguous f32 [B,C,T,H,W] on the device, erased in place in ONE launch that writes the elements inside the
+ *   boxes and reads nothing of x (16-byte stores on the aligned interior of a box row, 4-byte stores at its edges; same bits either
+ *   way); boxes on the device.  On the device a box is cut to the clip and a row with an unknown mode or sample is ignored. */
+#define TAD_ERASE_BOX_WORDS 8
+#define TAD_ERASE_CONST 0
+#define TAD_ERASE_RAND 1
+#define TAD_ERASE_PIXEL 2
+#define TAD_ERASE_MAX_BOXES 65535
+int tad_erase_plan_check(const int32_t* boxes_host, int n_boxes, int B, int T, int H, int W);
+int tad_erase_clips(float* x, const int32_t* boxes, int n_boxes, uint32_t seed, int B, int C, int T, int H, int W, tad_stream_t stream);
+
 /* ---- MAE pre-training path: what modeling_pretrain.py / engine_for_pretraining.py add around the Block stack ----
  * Rows are D f32, D % 4 == 0.  idx arrays are int32 on the device. */
 /* out[r] = src[idx[r]], r < n_out: x[~mask].reshape(B,-1,C) (modeling_pretrain.py:98) with idx = b*N + visible token */

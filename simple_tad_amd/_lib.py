@@ -65,6 +65,8 @@ SIGNATURES = {
     "tad_mixup_clips": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "tad_mixup_target": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp]),
     "tad_soft_target_ce": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp]),
+    "tad_erase_plan_check": (_i, [_vp, _i, _i, _i, _i, _i]),
+    "tad_erase_clips": (_i, [_vp, _vp, _i, C.c_uint32, _i, _i, _i, _i, _i, _vp]),
     "tad_gather_rows_f32": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     "tad_scatter_rows_f32": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     "tad_mae_assemble": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -113,6 +115,8 @@ ADAMW_MAX_GROUPS = 128
 EMA_CHUNK = 8192
 MIXUP_PLAN_WORDS = 12
 MIX_KEEP, MIX_BLEND, MIX_PASTE = 0, 1, 2
+ERASE_BOX_WORDS = 8
+ERASE_CONST, ERASE_RAND, ERASE_PIXEL = 0, 1, 2
 POOL_SPLIT = 8
 
 _lib = None

@@ -236,11 +236,13 @@ struct Drop {
   uint32_t thr, seed;
   float inv_keep;
 };
-__device__ __forceinline__ bool drop_keep(const Drop& d, uint32_t row, uint32_t key) {
-  uint32_t x = row * 0x9E3779B1u + key * 0x85EBCA77u + d.seed;
+// hash32(a, b, s): two counters and a seed / key word -> 32 well-mixed bits (two odd multipliers, then a multiply-xorshift finalizer)
+__host__ __device__ __forceinline__ uint32_t hash32(uint32_t a, uint32_t b, uint32_t s) {
+  uint32_t x = a * 0x9E3779B1u + b * 0x85EBCA77u + s;
   x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-  return x >= d.thr;
+  return x;
 }
+__device__ __forceinline__ bool drop_keep(const Drop& d, uint32_t row, uint32_t key) { return hash32(row, key, d.seed) >= d.thr; }
 inline bool make_drop(float p, uint32_t seed, Drop* d) {
   if (!(p >= 0.f && p < 1.f)) return false;
   d->thr = (uint32_t)((double)p * 4294967296.0);

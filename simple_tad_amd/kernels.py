@@ -854,6 +854,39 @@ def mixup_target(plan, labels, num_classes: int, on_value: float, off_value: flo
     return out
 
 
+def erase_box_table(boxes, B: int, T: int, H: int, W: int):
+    """Host-side box table of erase_clips: boxes = one (sample, mode, t0, t1, y0, y1, x0, x1) per box, in the order the reference
+    writes them (where boxes of a sample overlap the last one wins).  Returns the int32 CPU tensor [n, ERASE_BOX_WORDS], checked by
+    tad_erase_plan_check (modes, samples inside the batch, boxes inside the clip); runs without a GPU."""
+    import numpy as np
+    tab = np.zeros((len(boxes), _lib.ERASE_BOX_WORDS), dtype=np.int32)
+    for k, row in enumerate(boxes):
+        tab[k, :8] = row
+    if len(boxes):
+        check(_lib.load().tad_erase_plan_check(tab.ctypes.data, len(boxes), B, T, H, W), "tad_erase_plan_check")
+    return torch.from_numpy(tab)
+
+
+def erase_clips(x, boxes, seed: int):
+    """Erase the boxes of the device table ``boxes`` (a copy of erase_box_table()) from the contiguous f32 clip batch x [B,C,T,H,W] IN
+    PLACE (tad_erase_clips, ONE launch that only stores); ``seed`` keys the counter-based noise (include/tad_mi355x.h).  Returns x; an
+    empty table launches nothing.  The caller bumps x's version counter if autograd is to see the write."""
+    _req(x, torch.float32, "erase_clips.x")
+    if x.dim() != 5:
+        raise _lib.TadError(f"erase_clips.x: expected [B,C,T,H,W], got {tuple(x.shape)}")
+    _req(boxes, torch.int32, "erase_clips.boxes")
+    if boxes.dim() != 2 or boxes.shape[1] != _lib.ERASE_BOX_WORDS:
+        raise _lib.TadError(f"erase_clips.boxes: expected the device copy of erase_box_table(), got {tuple(boxes.shape)}")
+    B, Cc, T, H, W = x.shape
+    n = boxes.shape[0]
+    if n == 0:
+        return x
+    with _timed("erase", 0.0, 0.0):
+        check(_lib.load().tad_erase_clips(x.data_ptr(), boxes.data_ptr(), n, int(seed) & 0xffffffff, B, Cc, T, H, W, _stream()),
+              "tad_erase_clips")
+    return x
+
+
 def soft_target_ce(logits, target=None, labels=None, smoothing: float = 0.0):
     """(loss [1], dlogits [B,classes]) of the batch-mean soft-target cross entropy over f32 logits, ONE launch (tad_soft_target_ce):
     ``target`` f32 [B,classes], or int64 ``labels`` [B] smoothed on the fly."""
