@@ -392,6 +392,48 @@ int tad_soft_target_ce(const float* logits, const float* target, const int64_t* 
 int tad_erase_plan_check(const int32_t* boxes_host, int n_boxes, int B, int T, int H, int W);
 int tad_erase_clips(float* x, const int32_t* boxes, int n_boxes, uint32_t seed, int B, int C, int T, int H, int W, tad_stream_t stream);
 
+/* RandAugment of the fine-tune recipe on the device (rand_augment.py of the reference: --aa rand-m6-n3-mstd0.5-inc1, applied by the
+ * datasets to the PIL frames of every training clip), on uint8 frames [B,T,H,W,3], and the conversion to normalised f32 clips.
+ * table: int32 [n_layers][B][TAD_RANDAUG_ROW_WORDS], per layer one row per clip (every sample exactly once):
+ *   {sample, op, iarg, fill, bicubic_lo, bicubic_hi, farg, 0, a0 .. a5}
+ *   op      TAD_RA_*: COPY (the layer's coin failed, or the operator is the identity), the lookup-table operators (iarg: Posterize's
+ *           bits to keep 0..8, Solarize's threshold 0..256, SolarizeAdd's addend 0..255), the ImageEnhance operators (farg: the
+ *           factor, f32 bits) and AFFINE (Rotate, ShearX/Y, TranslateX/YRel: a0..a5 = the coefficients PIL's Image.transform(AFFINE)
+ *           receives, six doubles each as low word, high word; fill = R | G << 8 | B << 16 where no source pixel maps; bit t of
+ *           bicubic_lo / bicubic_hi (t >= 32) set = frame t is resampled BICUBIC, clear = BILINEAR).
+ *   All frames of a clip share op and argument; AutoContrast, Equalize and Contrast take their statistics per frame.
+ *   csrc/randaug.hip states each operator's arithmetic (PIL's: integers, C float for ImageEnhance, C double for the affine map).
+ * tad_randaug_plan_check: host-side check of a HOST copy of the table (n_words = its length, which must be n_layers * B * ROW_WORDS;
+ *   known ops, 0 <= sample < B once per layer, argument ranges, finite factors and coefficients); no launch.
+ * tad_randaug_apply: x -> out (two buffers of B*T*H*W*3 bytes, any alignment; x is only read), table on the device.  Per layer ONE
+ *   apply launch, preceded by ONE statistics launch iff bit `layer` of stats_layers is set (the caller sets it when a row of the layer is
+ *   AUTOCONTRAST, EQUALIZE or CONTRAST); layers alternate between out and a second buffer in the workspace (256-byte aligned,
+ *   tad_randaug_workspace_bytes).  n_layers == 0 copies.  On the device a row with an unknown op copies its clip; a row whose sample
+ *   is outside the batch is ignored, and a clip that no row of a layer names is left unwritten by that layer: its bytes in out are
+ *   undefined (tad_randaug_plan_check refuses such tables).
+ * tad_frames_to_clip: out f32 [B,3,T,H,W] = ((float)x / 255 - mean[c]) / std[c] of x uint8 [B,T,H,W,3], IEEE division and
+ *   subtraction in f32 (torchvision's ToTensor, the reference's tensor_normalize, permute: dota.py:308-316); mean / std: 3 host floats. */
+#define TAD_RANDAUG_ROW_WORDS 20
+#define TAD_RANDAUG_MAX_LAYERS 32
+#define TAD_RANDAUG_STAT_BYTES 1024
+#define TAD_RA_COPY 0
+#define TAD_RA_INVERT 1
+#define TAD_RA_POSTERIZE 2
+#define TAD_RA_SOLARIZE 3
+#define TAD_RA_SOLARIZE_ADD 4
+#define TAD_RA_AUTOCONTRAST 5
+#define TAD_RA_EQUALIZE 6
+#define TAD_RA_BRIGHTNESS 7
+#define TAD_RA_COLOR 8
+#define TAD_RA_CONTRAST 9
+#define TAD_RA_SHARPNESS 10
+#define TAD_RA_AFFINE 11
+int tad_randaug_plan_check(const int32_t* table_host, int64_t n_words, int n_layers, int B, int T);
+size_t tad_randaug_workspace_bytes(int n_layers, int B, int T, int H, int W);
+int tad_randaug_apply(const uint8_t* x, uint8_t* out, const int32_t* table, int n_layers, uint32_t stats_layers, void* workspace,
+                      size_t workspace_bytes, int B, int T, int H, int W, tad_stream_t stream);
+int tad_frames_to_clip(const uint8_t* x, float* out, const float* mean, const float* std_, int B, int T, int H, int W, tad_stream_t stream);
+
 /* ---- MAE pre-training path: what modeling_pretrain.py / engine_for_pretraining.py add around the Block stack ----
  * Rows are D f32, D % 4 == 0.  idx arrays are int32 on the device. */
 /* out[r] = src[idx[r]], r < n_out: x[~mask].reshape(B,-1,C) (modeling_pretrain.py:98) with idx = b*N + visible token */

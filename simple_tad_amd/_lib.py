@@ -67,6 +67,10 @@ SIGNATURES = {
     "tad_soft_target_ce": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp]),
     "tad_erase_plan_check": (_i, [_vp, _i, _i, _i, _i, _i]),
     "tad_erase_clips": (_i, [_vp, _vp, _i, C.c_uint32, _i, _i, _i, _i, _i, _vp]),
+    "tad_randaug_plan_check": (_i, [_vp, _i64, _i, _i, _i]),
+    "tad_randaug_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "tad_randaug_apply": (_i, [_vp, _vp, _vp, _i, C.c_uint32, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "tad_frames_to_clip": (_i, [_vp, _vp, C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _vp]),
     "tad_gather_rows_f32": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     "tad_scatter_rows_f32": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     "tad_mae_assemble": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -117,6 +121,11 @@ MIXUP_PLAN_WORDS = 12
 MIX_KEEP, MIX_BLEND, MIX_PASTE = 0, 1, 2
 ERASE_BOX_WORDS = 8
 ERASE_CONST, ERASE_RAND, ERASE_PIXEL = 0, 1, 2
+RANDAUG_ROW_WORDS = 20
+RANDAUG_MAX_LAYERS = 32
+(RA_COPY, RA_INVERT, RA_POSTERIZE, RA_SOLARIZE, RA_SOLARIZE_ADD, RA_AUTOCONTRAST, RA_EQUALIZE, RA_BRIGHTNESS, RA_COLOR, RA_CONTRAST,
+ RA_SHARPNESS, RA_AFFINE) = range(12)
+RA_STATS_OPS = (RA_AUTOCONTRAST, RA_EQUALIZE, RA_CONTRAST)
 POOL_SPLIT = 8
 
 _lib = None

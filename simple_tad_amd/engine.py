@@ -310,13 +310,18 @@ def train_class_batch(model, samples, target, criterion):
 
 def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable, optimizer, device, epoch: int, loss_scaler,
                     max_norm: float = 0, start_steps=0, lr_schedule_values=None, wd_schedule_values=None,
-                    num_training_steps_per_epoch=None, update_freq=1, log=None, model_ema=None, erase_fn=None, mixup_fn=None):
+                    num_training_steps_per_epoch=None, update_freq=1, log=None, model_ema=None, augment_fn=None, erase_fn=None, mixup_fn=None):
     """engine_for_finetuning.train_one_epoch (engine_for_finetuning.py:24-140) without the DeepSpeed branches.
     ``mixup_fn`` (a ``mixup.Mixup`` or anything with ``(samples, targets) -> (samples, soft_targets)``) is applied to every batch once it
     is on the device (:59-60); the criterion then has to take soft targets (``loss.SoftTargetCrossEntropy``), and ``class_acc`` is
     logged as ``None`` for the step, as the reference does (:104-107), so it does not appear in ``averaged``.
     ``erase_fn`` (a ``random_erasing.RandomErasing`` or anything with ``samples -> samples``) is applied before it, to the batch on the
     device: the reference erases in its dataset workers (dota.py:318-329), i.e. before the batch is mixed as well.
+    ``augment_fn`` (anything with ``samples -> samples``) is applied first of the three, right after the batch has reached the device
+    (the reference augments its PIL frames before it normalises and erases them, dota.py:299-316).  With a loader that yields uint8
+    frames [B,T,H,W,3] there are two routes: ``augment_fn=rand_augment.RandAugment`` alone -- uint8 out, which the model's uint8
+    input stage takes as it is -- or ``augment_fn=lambda x: frames_to_clip(randaug(x), mean, std)`` -- normalised f32 clips
+    [B,3,T,H,W] out, which ``erase_fn`` and ``mixup_fn`` then take, and after them the model.  With the default nothing changes.
     ``model_ema`` (an ``ema.ModelEma`` or anything with ``update(model)``) is updated after every completed optimizer step, i.e. on
     the last micro-step of each ``update_freq`` group, as the reference does (:96-99) -- also after a step that the loss scaler
     skipped on the device, where the average then moves toward the unchanged weights.  The update is queued on the stream behind
@@ -343,6 +348,8 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable, op
                     group["weight_decay"] = wd_schedule_values[it]
         samples = samples.to(device, non_blocking=True)
         targets = targets.to(device, non_blocking=True)
+        if augment_fn is not None:
+            samples = augment_fn(samples)
         if erase_fn is not None:
             samples = erase_fn(samples)
         if mixup_fn is not None:

@@ -887,6 +887,76 @@ def erase_clips(x, boxes, seed: int):
     return x
 
 
+# ----------------------------------------------------------------------------- RandAugment on uint8 frames
+def randaug_table(layers, B: int, T: int):
+    """Host-side table of randaug_apply: ``layers`` = per layer one row per clip, (sample, op, iarg, farg, coefficients (six Python
+    floats) or None, fill (r, g, b), bicubic mask (bit t: frame t is resampled BICUBIC)).  Returns (int32 CPU tensor
+    [n_layers, B, RANDAUG_ROW_WORDS], bit mask of the layers that need per-frame statistics), checked by tad_randaug_plan_check (known
+    ops, every sample once per layer, argument ranges, finite values); runs without a GPU."""
+    import numpy as np
+    tab = np.zeros((len(layers), B, _lib.RANDAUG_ROW_WORDS), dtype=np.int32)
+    stats = 0
+    for l, rows in enumerate(layers):
+        if len(rows) != B:
+            raise _lib.TadError(f"randaug_table: layer {l} has {len(rows)} rows for a batch of {B} clips")
+        for k, (sample, op, iarg, farg, coefs, fill, bicubic) in enumerate(rows):
+            row = tab[l, k]
+            row[0], row[1], row[2] = sample, op, iarg
+            u = row.view(np.uint32)
+            u[3] = (int(fill[0]) & 255) | (int(fill[1]) & 255) << 8 | (int(fill[2]) & 255) << 16
+            u[4], u[5] = int(bicubic) & 0xffffffff, (int(bicubic) >> 32) & 0xffffffff
+            row.view(np.float32)[6] = farg
+            if coefs is not None:
+                row[8:20] = np.asarray(coefs, dtype=np.float64).view(np.int32)
+            if op in _lib.RA_STATS_OPS:
+                stats |= 1 << l
+    check(_lib.load().tad_randaug_plan_check(tab.ctypes.data, tab.size, len(layers), B, T), "tad_randaug_plan_check")
+    return torch.from_numpy(tab), stats
+
+
+def _req_frames(x, name):
+    _req(x, torch.uint8, name)
+    if x.dim() != 5 or x.shape[-1] != 3 or x.numel() == 0:
+        raise _lib.TadError(f"{name}: expected uint8 frames [B,T,H,W,3], got {tuple(x.shape)}")
+
+
+def randaug_apply(x, table, stats_layers: int):
+    """Carry the device table ``table`` (a copy of randaug_table()'s, [n_layers, B, RANDAUG_ROW_WORDS]) out on the contiguous uint8
+    frames x [B,T,H,W,3] (tad_randaug_apply: per layer one apply launch, plus one statistics launch where ``stats_layers`` has the
+    layer's bit).  Returns a new tensor; x is only read."""
+    _req_frames(x, "randaug_apply.x")
+    B, T, H, W, _ = x.shape
+    _req(table, torch.int32, "randaug_apply.table")
+    if table.dim() != 3 or tuple(table.shape[1:]) != (B, _lib.RANDAUG_ROW_WORDS):
+        raise _lib.TadError(f"randaug_apply.table: expected the device copy of randaug_table() for {B} clips, got {tuple(table.shape)}")
+    L = table.shape[0]
+    lib = _lib.load()
+    out = torch.empty_like(x)
+    nbytes = lib.tad_randaug_workspace_bytes(L, B, T, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    with _timed("randaug", 0.0, 2.0 * L * x.numel()):
+        check(lib.tad_randaug_apply(x.data_ptr(), out.data_ptr(), table.data_ptr() if L else None, L, int(stats_layers) & 0xffffffff,
+                                    ws.data_ptr(), nbytes, B, T, H, W, _stream()), "tad_randaug_apply")
+    return out
+
+
+def frames_to_clip(x, mean, std, out=None):
+    """f32 clips [B,3,T,H,W] = ((float)x / 255 - mean[c]) / std[c] of the contiguous uint8 frames x [B,T,H,W,3] (tad_frames_to_clip,
+    ONE launch; IEEE division): torchvision's ToTensor, the reference's tensor_normalize and its permute, bit for bit."""
+    _req_frames(x, "frames_to_clip.x")
+    B, T, H, W, _ = x.shape
+    if out is None:
+        out = torch.empty((B, 3, T, H, W), dtype=torch.float32, device=x.device)
+    else:
+        _req(out, torch.float32, "frames_to_clip.out")
+        if tuple(out.shape) != (B, 3, T, H, W) or out.device != x.device:
+            raise _lib.TadError(f"frames_to_clip.out: expected {(B, 3, T, H, W)} on {x.device}, got {tuple(out.shape)} on {out.device}")
+    m, s = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    with _timed("frames_to_clip", 0.0, 13.0 * B * T * H * W):
+        check(_lib.load().tad_frames_to_clip(x.data_ptr(), out.data_ptr(), m, s, B, T, H, W, _stream()), "tad_frames_to_clip")
+    return out
+
+
 def soft_target_ce(logits, target=None, labels=None, smoothing: float = 0.0):
     """(loss [1], dlogits [B,classes]) of the batch-mean soft-target cross entropy over f32 logits, ONE launch (tad_soft_target_ce):
     ``target`` f32 [B,classes], or int64 ``labels`` [B] smoothed on the fly."""
