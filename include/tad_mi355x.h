@@ -199,6 +199,34 @@ int tad_linear_bwd_weight_pair(const uint16_t* dy1, const uint16_t* x1, float* d
 int tad_linear_tuning(const char* key, int value);
 /* Current value of a tad_linear_tuning knob (what a scoped change has to put back: simple_tad_amd.kernels.TuningScope). */
 int tad_linear_tuning_get(const char* key, int* value);
+/* What a Linear problem WOULD run as under the current knobs -- the launch plan the entry points above execute, as data.  Launches nothing
+ * and needs no device (without one the plan is made for 256 CUs, the MI355X's count): plans can be inspected, compared and tested on a
+ * build machine (simple_tad_amd.kernels.linear_plan; tests/test_linear_plan_cpu.py).  The problem is y [M,N] = x [M,K] w^T in the GEMM's own
+ * terms (tad_linear_bwd_input(M, N, K) is the problem (M, K, N)) with
+ *   epilogue        0 bias only, 1 bias + GELU, 2 bias + residual, 3 GELU backward (tad_linear_bwd_input with gelu_preact)
+ *   out_16bit       the output has the 16-bit operand format (else f32)
+ *   has_residual, res_mod         a residual operand is given; res_mod > 0: its row is taken modulo res_mod (tad_patch_embed_gemm's ntok)
+ *   has_rowscale, rows_per_scale  as tad_linear_fwd's;  colscale_cols: N / 3 for tad_linear_fwd_qkv with q_prescale != 1, else 0
+ *   ws_bytes        the split-K workspace on offer (0: none)
+ * Writes one row of TAD_LINEAR_PLAN_STEP_WORDS int32 per kernel launch, in launch order, and returns their number (> 0), TAD_ENOSPACE when
+ * there are more than `capacity` rows, or the error the entry point would refuse the shape with.  A row is
+ *   r0, rows        the rows of the problem the launch covers (taller problems than 32-bit operand offsets allow run as row ranges)
+ *   kernel          the tile configuration of tad_linear_tuning("variant") that is launched (1 2 3 4 5 7 8 9), or 10 = the split-K kernel
+ *   persistent, direct, grid, block, group_m    one workgroup per CU walks the tiles | stores straight from the MFMA layout | launch geometry | raster
+ *   sk_splits, sk_mode   split-K launches: shares per tile; 0 combine in the launch, 1 leave the partial tiles, 2 combine what a mode-1 launch left
+ *   epilogue        the epilogue instantiation: as above, or 4 = residual modulo res_mod */
+#define TAD_LINEAR_PLAN_STEP_WORDS 11
+int tad_linear_plan(int64_t M, int N, int K, int epilogue, int out_16bit, int has_residual, int res_mod, int has_rowscale,
+                    int rows_per_scale, int colscale_cols, size_t ws_bytes, int32_t* steps, int capacity);
+/* The same for the weight gradients: tad_linear_bwd_weight(M, N1, K) with N2 == 0, tad_linear_bwd_weight_pair(M, N1, N2, K) otherwise, given a
+ * workspace of ws_bytes.  One row of TAD_LINEAR_BWD_WEIGHT_PLAN_WORDS int32 per GEMM launch (a pair is ONE row when it fits one launch, else two):
+ *   N, tile_k       output rows of the launch (N1 + N2 for a pair launch); tile width along K (256 or 128)
+ *   tiles, tiles_k, splits, rows_per_split, kernel, grid, block    kernel: 0 four waves 256 x 256, 1 eight waves with the deep P ring ("tn_pdeep"),
+ *                   2 eight waves 256 x 256, 3 256 x 128
+ *   pair            1 = this launch computes both gradients
+ *   ws_lo, ws_hi    workspace the launch needs: ws_hi * 2^31 + ws_lo bytes (= tad_linear_bwd_weight_workspace_bytes(M, N, K)) */
+#define TAD_LINEAR_BWD_WEIGHT_PLAN_WORDS 12
+int tad_linear_bwd_weight_plan(int64_t M, int N1, int N2, int K, size_t ws_bytes, int32_t* launches, int capacity);
 /* Number of gemm_nt kernel launches issued so far by tad_linear_fwd* / tad_linear_bwd_input / tad_patch_embed_* (a call is one
  * launch, or two when the split-tail plan is taken): lets a profiler attribute event time to kernel launches. */
 long long tad_linear_kernel_launches(void);

@@ -34,6 +34,8 @@ SIGNATURES = {
     "tad_linear_workspace_bytes": (_sz, [_i64, _i, _i]),
     "tad_linear_tuning": (_i, [C.c_char_p, _i]),
     "tad_linear_tuning_get": (_i, [C.c_char_p, C.POINTER(_i)]),
+    "tad_linear_plan": (_i, [_i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _sz, C.POINTER(C.c_int32), _i]),
+    "tad_linear_bwd_weight_plan": (_i, [_i64, _i, _i, _i, _sz, C.POINTER(C.c_int32), _i]),
     "tad_linear_fwd_qkv": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _i64, _i, _i, _vp]),
     "tad_linear_bwd_weight_qkv": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _i64, _i, _i, _vp]),
     "tad_linear_bwd_weight_pair": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _i64, _i, _vp]),
@@ -114,6 +116,8 @@ for _bf, _h in F16_TWINS.items():
     SIGNATURES[_h] = SIGNATURES[_bf]
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL = 0, 1, 2
 ABI_VERSION = 4
+LINEAR_PLAN_FIELDS = ("r0", "rows", "kernel", "persistent", "direct", "grid", "block", "group_m", "sk_splits", "sk_mode", "epilogue")
+LINEAR_BWD_WEIGHT_PLAN_FIELDS = ("N", "tile_k", "tiles", "tiles_k", "splits", "rows_per_split", "kernel", "grid", "block", "pair", "ws_lo", "ws_hi")
 ADAMW_CHUNK = 4096
 ADAMW_MAX_GROUPS = 128
 EMA_CHUNK = 8192

@@ -19,6 +19,7 @@
 // stored straight from the MFMA layout instead.  DESIGN.md section 3 and docs/DESIGN_HISTORY.md section 3.1 have the measurements behind each choice.
 #pragma once
 #include "common.h"
+#include "gemm_plan.h"  // the epilogue kinds (EPI_*), BK, the plan steps
 
 TAD_NAMESPACE_BEGIN
 
@@ -30,8 +31,6 @@ int launch_reduce_dw(const float* partial, float* out, int splits, int64_t n, in
 int launch_reduce_dw_pair(const float* partial, float* outA, float* outB, int64_t nA, int splits, int64_t n, int accumulate, const float* partial2,
                           int rows2, int n2, float* out2a, float* out2b, int n2a, int c2b, hipStream_t st);
 
-// EPI_RESMOD = EPI_RESIDUAL with the residual row taken modulo res_mod ("+ pos_embed" of the patch embedding): a variant of its
-// own so that the integer division stays out of the Linear kernels
 // Ablation switches (TAD_GEMM_DEBUG, see GemmNT::debug) cost scalar branches inside the K loops: compiled in only with
 // -DTAD_GEMM_ABLATION (python -m simple_tad_amd.build reads TAD_BUILD_ABLATION=1); production builds see a constant 0.
 #ifdef TAD_GEMM_ABLATION
@@ -39,8 +38,6 @@ int launch_reduce_dw_pair(const float* partial, float* outA, float* outB, int64_
 #else
 #define DBG_BITS(p) 0
 #endif
-
-enum { EPI_PLAIN = 0, EPI_GELU = 1, EPI_RESIDUAL = 2, EPI_DGELU = 3, EPI_RESMOD = 4 };
 
 struct GemmNT {
   const uint16_t* A;  // [M,K]
@@ -82,7 +79,6 @@ int launch_gemm_nt_w4(const GemmNT& p, int grid_persist, hipStream_t st);  // cs
 struct GemmTN;
 int launch_gemm_tn_w4(const GemmTN& p, int grid, hipStream_t st);
 
-constexpr int BK = 64;             // K-tile depth (bf16 elements) -> 128-byte LDS rows
 constexpr int ROW_BYTES = BK * 2;  // 128
 
 // swizzle of the 16-byte chunk index (0..7) within a 128-byte LDS row

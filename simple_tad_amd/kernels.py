@@ -518,6 +518,39 @@ def linear_tuning_get(key: str) -> int:
     return int(v.value)
 
 
+def _plan_rows(call, fields, what):
+    cap = 8
+    while True:
+        buf = (C.c_int32 * (cap * len(fields)))()
+        n = call(buf, cap)
+        if n != -3:  # TAD_ENOSPACE: a problem cut into many row ranges
+            break
+        cap *= 8
+    if n < 0:
+        check(n, what)
+    return [dict(zip(fields, buf[i * len(fields):(i + 1) * len(fields)])) for i in range(n)]
+
+
+def linear_plan(M, N, K, epilogue=0, out_16bit=True, residual=False, res_mod=0, rowscale=False, rows_per_scale=1, colscale_cols=0, ws_bytes=0):
+    """The kernel launches the Linear y [M,N] = x [M,K] w^T would run as under the current knobs, in order: a list of dicts with the keys
+    _lib.LINEAR_PLAN_FIELDS (include/tad_mi355x.h: tad_linear_plan).  Launches nothing and needs no GPU.  epilogue: 0 bias, 1 GELU, 2 residual,
+    3 GELU backward; for linear_bwd_input(dy [M,N], wT [K,N]) the problem is (M, K, N)."""
+    lib = _lib.load()
+    return _plan_rows(lambda buf, cap: lib.tad_linear_plan(M, N, K, int(epilogue), int(out_16bit), int(residual), int(res_mod), int(rowscale), int(rows_per_scale),
+                                                           int(colscale_cols), int(ws_bytes), buf, cap), _lib.LINEAR_PLAN_FIELDS, "tad_linear_plan")
+
+
+def linear_bwd_weight_plan(M, N, K, N2=0, ws_bytes=0):
+    """The GEMM launches of linear_bwd_weight (N2 = 0) or linear_bwd_weight_pair (dW [N,K] and [N2,K]) given a workspace of ws_bytes: a list of
+    dicts with the keys _lib.LINEAR_BWD_WEIGHT_PLAN_FIELDS plus "ws_bytes" (include/tad_mi355x.h: tad_linear_bwd_weight_plan)"""
+    lib = _lib.load()
+    rows = _plan_rows(lambda buf, cap: lib.tad_linear_bwd_weight_plan(M, N, N2, K, int(ws_bytes), buf, cap), _lib.LINEAR_BWD_WEIGHT_PLAN_FIELDS,
+                      "tad_linear_bwd_weight_plan")
+    for r in rows:
+        r["ws_bytes"] = (r["ws_hi"] << 31) + r["ws_lo"]
+    return rows
+
+
 def linear_bwd_input(dy, wT, out_dtype=None, gelu_preact=None):
     """dy [M,N], wT [K,N] (both bf16 or both f16) -> dx [M,K]"""
     op = _req16(dy, "linear_bwd_input.dy")

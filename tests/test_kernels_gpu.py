@@ -828,6 +828,77 @@ def test_linear_splitk_tail_matches_the_single_launch_plans(K, M, N, Kd, mode, d
     assert float((y1[rows].double() - ref).abs().max() / ref.abs().max()) < (TOL if y1.dtype == torch.float32 else 2 * BF16_ULP)
 
 
+@pytest.mark.parametrize("mode", ["plain", "res"], ids=["plain_bf16", "residual_f32"])
+def test_linear_executor_runs_the_plan(K, mode):
+    """The launcher executes what kernels.linear_plan (csrc/gemm_plan.hip) says, at the smallest shape at which the split plan exists (32 whole row
+    panels + a ragged tail): under the defaults and the four plans of test_guarded_gpu.py the launch counter grows by exactly the number of steps
+    of the plan.  Outputs: bit-identical between all plans in every row that no split-K step covers, and between the two forms of the split-K
+    combine everywhere; the rows of a split-K tail differ from the unsplit plans only in the summation order over K (the tolerance of
+    test_linear_splitk_tail_matches_the_single_launch_plans)."""
+    from test_guarded_gpu import PLANS
+    M, N, Kd = 33 * 256 + 37, 2048, 512
+    g = torch.Generator().manual_seed(M + N)
+    x = dev(torch.randn(M, Kd, generator=g)).to(torch.bfloat16)
+    w = dev(torch.randn(N, Kd, generator=g) * 0.05).to(torch.bfloat16)
+    b = dev(torch.randn(N, generator=g) * 0.1)
+    res = dev(torch.randn(M, N, generator=g)) if mode == "res" else None
+    from simple_tad_amd import _lib
+    outs, split_rows = {}, {}
+    try:
+        for name, knobs in {"defaults": {}, **PLANS}.items():
+            K.linear_tuning(**{**K.LINEAR_TUNING_DEFAULTS, **knobs})
+            plan = K.linear_plan(M, N, Kd, epilogue=2 if mode == "res" else 0, out_16bit=mode != "res", residual=mode == "res",
+                                 ws_bytes=_lib.load().tad_linear_workspace_bytes(M, N, Kd))
+            n0 = K.linear_kernel_launches()
+            y = (K.linear_fwd(x, w, b, out_dtype=torch.float32, epilogue=K.EPI_BIAS_RESIDUAL, residual=res) if mode == "res" else K.linear_fwd(x, w, b))[0]
+            assert K.linear_kernel_launches() - n0 == len(plan), (name, plan)
+            ranges = sorted({(s["r0"], s["rows"]) for s in plan})
+            assert ranges[0][0] == 0 and sum(r for _, r in ranges) == M, plan  # the steps cover every row once
+            outs[name] = y.clone()
+            sk = {(s["r0"], s["rows"]) for s in plan if s["kernel"] == 10}
+            assert len(sk) == (1 if name.startswith("splitk") else 0), (name, plan)
+            split_rows[name] = next(iter(sk)) if sk else (M, 0)
+    finally:
+        K.linear_tuning(**K.LINEAR_TUNING_DEFAULTS)
+    y0 = outs["defaults"]
+    ref = x.double() @ w.double().t() + b.double() + (res.double() if mode == "res" else 0.0)
+    check(y0.float(), ref, tol=TOL if mode == "res" else BF16_ULP, what=f"linear defaults {mode}")
+    assert torch.equal(outs["splitk_deferred"], outs["splitk_in_launch"]), "the two forms of the split-K combine differ"
+    for name, y in outs.items():
+        r0, rows = split_rows[name]
+        assert torch.equal(y[:r0], y0[:r0]) and torch.equal(y[r0 + rows:], y0[r0 + rows:]), f"{name}: rows outside a split-K step differ from the default plan"
+        if rows:
+            a, c = y0[r0:r0 + rows].double(), y[r0:r0 + rows].double()
+            assert float((a - c).abs().max() / a.abs().max()) < (2e-5 if y0.dtype == torch.float32 else 2 * BF16_ULP), name
+
+
+@pytest.mark.parametrize("tn_pair", [0, 1])
+def test_linear_bwd_weight_runs_the_plan(K, tn_pair):
+    """the weight gradient alone and as a pair (one launch with tn_pair = 1, two with 0: linear_bwd_weight_plan says which) against the float64 product"""
+    M, N, Kd, N2 = 33 * 256 + 37, 512, 256, 256
+    g = torch.Generator().manual_seed(M + N + tn_pair)
+    dy, x = bf(torch.randn(M, N, generator=g)), bf(torch.randn(M, Kd, generator=g))
+    dy2, x2 = bf(torch.randn(M, N2, generator=g)), bf(torch.randn(M, Kd, generator=g))
+    d16 = lambda t: dev(t).to(torch.bfloat16)
+    from simple_tad_amd import _lib
+    need = max(_lib.load().tad_linear_bwd_weight_workspace_bytes(M, n, Kd) for n in (N, N2, N + N2))
+    try:
+        K.linear_tuning(**{**K.LINEAR_TUNING_DEFAULTS, "tn_pair": tn_pair})
+        single, pair = K.linear_bwd_weight_plan(M, N, Kd), K.linear_bwd_weight_plan(M, N, Kd, N2=N2, ws_bytes=need)
+        assert len(single) == 1 and single[0]["pair"] == 0 and single[0]["N"] == N and single[0]["grid"] == single[0]["tiles"] * single[0]["splits"]
+        assert [(r["N"], r["pair"]) for r in pair] == ([(N + N2, 1)] if tn_pair else [(N, 0), (N2, 0)]), pair
+        dW, db = K.linear_bwd_weight(d16(dy), d16(x))
+        dW1, dW2, db1 = (torch.empty(N, Kd, device="cuda"), torch.empty(N2, Kd, device="cuda"), torch.empty(N, device="cuda"))
+        K.linear_bwd_weight_pair(d16(dy), d16(x), dW1, db1, None, d16(dy2), d16(x2), dW2, False)
+    finally:
+        K.linear_tuning(**K.LINEAR_TUNING_DEFAULTS)
+    check(dW, dy.double().t() @ x.double(), what="linear dW")
+    check(db, dy.double().sum(0), what="linear db")
+    check(dW1, dy.double().t() @ x.double(), what="pair dW1")
+    check(db1, dy.double().sum(0), what="pair db1")
+    check(dW2, dy2.double().t() @ x2.double(), what="pair dW2")
+
+
 def test_linear_taller_than_the_32bit_epilogue_offsets(K):
     """VERDICT r01 robustness: an f32 output beyond 2 GiB (here 180 000 x 3072 x 4 B = 2.2 GB, ViT-B fc1 at B = 115) used to be refused;
     rows are independent, so the launcher runs row ranges that fit the 32-bit epilogue offsets.  Bit-identical to the same rows
