@@ -462,6 +462,38 @@ int tad_randaug_apply(const uint8_t* x, uint8_t* out, const int32_t* table, int 
                       size_t workspace_bytes, int B, int T, int H, int W, tad_stream_t stream);
 int tad_frames_to_clip(const uint8_t* x, float* out, const float* mean, const float* std_, int B, int T, int H, int W, tad_stream_t stream);
 
+/* The MAE pre-training crop on the device (transforms.py of the reference: GroupMultiScaleCrop = a multi-scale crop, then PIL's
+ * antialiased BILINEAR resize of every frame; DataAugmentationForVideoMAE chains Stack, ToTorchFormatTensor and GroupNormalize
+ * behind it), on uint8 frames [B,T,Hs,Ws,3]; all clips of a call share one source size.
+ * table: int32, three parts in this order:
+ *   rows    [B][TAD_MSC_ROW_WORDS], one per clip (every sample exactly once): {sample, x0, y0, w, h, hset, vset, 0}: the crop
+ *           x[sample][:, y0:y0+h, x0:x0+w] and the indices of its horizontal (w -> S_w) and vertical (h -> S_h) coefficient set
+ *   hsets   [n_hsets] slots of TAD_MSC_SET_HEAD + S_w * (2 + TAD_MSC_MAX_KSIZE) words
+ *   vsets   [n_vsets] slots of TAD_MSC_SET_HEAD + S_h * (2 + TAD_MSC_MAX_KSIZE) words
+ *   a set = {in, out, ksize, 0}, bounds[out][2] = (xmin, count), kk[out][ksize]; the rest of its slot is unused.  The host states the
+ *   sets as Pillow's precompute_coeffs and normalize_coeffs_8bpc do (doubles, rounded to 22-bit integers); one set per distinct
+ *   (crop extent -> output extent) of a call.  in <= 8 * out (filter scale <= 8, ksize <= 17).
+ * Arithmetic on the device, Pillow's, in int32: the horizontal pass gives a rounded byte, the vertical pass runs over those bytes;
+ *   each pass is ss = 1 << 21; ss += pixel * k over the `count` taps from xmin; byte = clip(ss >> 22, 0, 255).
+ * tad_multiscale_crop_workspace_bytes: the size of the table = of the workspace, which holds nothing else and is only read.
+ * tad_multiscale_crop_plan_check: host-side check of a HOST copy of the table (n_words = its length, which must be the sum of the
+ *   three parts; 0 <= sample < B exactly once; crops inside the source; set indices in range and sets stated for the crop's
+ *   extents; in <= 8 * out; 1 <= ksize <= TAD_MSC_MAX_KSIZE; 0 <= count <= ksize and xmin + count <= in); no launch.
+ * tad_multiscale_crop: ONE launch, no host synchronisation; x is only read.  out_f32 == 0: out = uint8 [B,T,S_h,S_w,3], any
+ *   alignment; mean / std_ are ignored.  out_f32 != 0: out = f32 [B,3,T,S_h,S_w] = ((float)byte / 255 - mean[c]) / std_[c], the
+ *   bits tad_frames_to_clip gives on the uint8 result; mean / std_: 3 host floats.  workspace = the table on the device.  On the
+ *   device a crop is cut to the source, a set index to the sets, bounds to the crop and to ksize, and a row whose sample is outside
+ *   the batch is ignored (a malformed table is never an address); a clip that no row names is left unwritten. */
+#define TAD_MSC_ROW_WORDS 8
+#define TAD_MSC_SET_HEAD 4
+#define TAD_MSC_MAX_KSIZE 17
+#define TAD_MSC_MAX_SETS 64
+size_t tad_multiscale_crop_workspace_bytes(int B, int n_hsets, int n_vsets, int S_h, int S_w);
+int tad_multiscale_crop_plan_check(const int32_t* table_host, int64_t n_words, int B, int n_hsets, int n_vsets, int Hs, int Ws, int S_h,
+                                   int S_w);
+int tad_multiscale_crop(const uint8_t* x, void* out, int out_f32, const float* mean, const float* std_, const void* workspace,
+                        size_t workspace_bytes, int B, int T, int Hs, int Ws, int S_h, int S_w, int n_hsets, int n_vsets, tad_stream_t stream);
+
 /* ---- MAE pre-training path: what modeling_pretrain.py / engine_for_pretraining.py add around the Block stack ----
  * Rows are D f32, D % 4 == 0.  idx arrays are int32 on the device. */
 /* out[r] = src[idx[r]], r < n_out: x[~mask].reshape(B,-1,C) (modeling_pretrain.py:98) with idx = b*N + visible token */

@@ -30,7 +30,9 @@ def reconstruction_target(videos: torch.Tensor, bool_masked_pos: torch.Tensor, p
 
 def train_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer, device: torch.device, epoch: int, loss_scaler,
                     max_norm: float = 0, patch_size: int = 16, normlize_target: bool = True, start_steps=0, lr_schedule_values=None,
-                    wd_schedule_values=None, tubelet_size: int = 2, log=None):
+                    wd_schedule_values=None, tubelet_size: int = 2, log=None, augment_fn=None):
+    """augment_fn: applied to ``batch[0]`` right after it has reached the device (uint8 frames [B,T,Hs,Ws,3] ->
+    ``transforms.DataAugmentationForVideoMAE``); where it returns a pair, the second item replaces ``batch[1]``, the masks."""
     model.train()
     dp = model if isinstance(model, DataParallel) else None
     inner = dp.module if dp is not None else model
@@ -46,9 +48,16 @@ def train_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer, de
                     group["lr"] = lr_schedule_values[it] * group.get("lr_scale", 1.0)
                 if wd_schedule_values is not None and group["weight_decay"] > 0:
                     group["weight_decay"] = wd_schedule_values[it]
-        videos, bool_masked_pos = batch[0], batch[1]
+        videos = batch[0].to(device, non_blocking=True)
+        bool_masked_pos = batch[1] if len(batch) > 1 else None
+        if augment_fn is not None:
+            augmented = augment_fn(videos)
+            videos, bool_masked_pos = augmented if isinstance(augmented, (tuple, list)) else (augmented, bool_masked_pos)
+        if bool_masked_pos is None:
+            raise ValueError("train_one_epoch: no masks for this step: the batch holds one item and augment_fn "
+                             + ("returned the clips alone" if augment_fn is not None else "is None")
+                             + " (pass (clips, masks) batches, or an augment_fn that returns (clips, masks))")
         num_masked = int(torch.as_tensor(bool_masked_pos)[0].sum())  # host-side count (the mask comes from the loader's generator)
-        videos = videos.to(device, non_blocking=True)
         bool_masked_pos = torch.as_tensor(bool_masked_pos).to(device, non_blocking=True).flatten(1).to(torch.bool)
         with torch.no_grad():
             labels = reconstruction_target(videos, bool_masked_pos, patch_size, tubelet_size, normlize_target, num_masked)

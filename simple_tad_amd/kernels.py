@@ -990,6 +990,67 @@ def frames_to_clip(x, mean, std, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- multi-scale crop + PIL BILINEAR resize of uint8 frames
+def multiscale_crop_table(rows, hsets, vsets, B: int, Hs: int, Ws: int, S_h: int, S_w: int):
+    """Host-side table of multiscale_crop (include/tad_mi355x.h): ``rows`` = one (sample, x0, y0, w, h, hset, vset) per clip;
+    ``hsets`` / ``vsets`` = coefficient sets (in, ksize, bounds [out][2], kk [out][ksize]) towards S_w / S_h outputs.  Returns the
+    int32 CPU tensor of tad_multiscale_crop_workspace_bytes / 4 words, checked by tad_multiscale_crop_plan_check (word counts, every
+    sample once, crops inside the source, counts <= ksize <= 17, set indices in range); runs without a GPU."""
+    import numpy as np
+    lib = _lib.load()
+    nh, nv = len(hsets), len(vsets)
+    if len(rows) != B or not (1 <= nh <= _lib.MSC_MAX_SETS and 1 <= nv <= _lib.MSC_MAX_SETS):
+        raise _lib.TadError(f"multiscale_crop_table: {len(rows)} rows for {B} clips, {nh} horizontal and {nv} vertical sets "
+                            f"(1 .. {_lib.MSC_MAX_SETS} each)")
+    tab = np.zeros(lib.tad_multiscale_crop_workspace_bytes(B, nh, nv, S_h, S_w) // 4, dtype=np.int32)
+    tab[:B * _lib.MSC_ROW_WORDS].reshape(B, _lib.MSC_ROW_WORDS)[:, :7] = np.asarray(rows, dtype=np.int64).reshape(B, 7)
+    at = B * _lib.MSC_ROW_WORDS
+    for sets, out in ((hsets, S_w), (vsets, S_h)):
+        slot = _lib.MSC_SET_HEAD + out * (2 + _lib.MSC_MAX_KSIZE)
+        for n_in, ksize, bounds, kk in sets:
+            bounds, kk = np.asarray(bounds, dtype=np.int32), np.asarray(kk, dtype=np.int32)
+            if not 1 <= ksize <= _lib.MSC_MAX_KSIZE or bounds.shape != (out, 2) or kk.shape != (out, ksize):
+                raise _lib.TadError(f"multiscale_crop_table: a set of ksize {ksize} (1 .. {_lib.MSC_MAX_KSIZE}) with bounds "
+                                    f"{bounds.shape} and kk {kk.shape} for {out} outputs")
+            tab[at:at + 3] = n_in, out, ksize
+            tab[at + _lib.MSC_SET_HEAD:at + _lib.MSC_SET_HEAD + 2 * out] = bounds.reshape(-1)
+            tab[at + _lib.MSC_SET_HEAD + 2 * out:at + _lib.MSC_SET_HEAD + (2 + ksize) * out] = kk.reshape(-1)
+            at += slot
+    check(lib.tad_multiscale_crop_plan_check(tab.ctypes.data, tab.size, B, nh, nv, Hs, Ws, S_h, S_w), "tad_multiscale_crop_plan_check")
+    return torch.from_numpy(tab)
+
+
+def multiscale_crop(x, table, n_hsets: int, n_vsets: int, S_h: int, S_w: int, mean=None, std=None, out=None):
+    """Crop and resize the contiguous uint8 frames x [B,T,Hs,Ws,3] as the device table ``table`` (a copy of multiscale_crop_table()'s:
+    the call's workspace, only read) says (tad_multiscale_crop, ONE launch).  Without ``mean`` / ``std``: uint8 [B,T,S_h,S_w,3];
+    with them: the normalised f32 clips [B,3,T,S_h,S_w], the bits frames_to_clip gives on the uint8 result.  x is only read."""
+    _req_frames(x, "multiscale_crop.x")
+    B, T, Hs, Ws, _ = x.shape
+    _req(table, torch.int32, "multiscale_crop.table")
+    lib = _lib.load()
+    nbytes = lib.tad_multiscale_crop_workspace_bytes(B, n_hsets, n_vsets, S_h, S_w)
+    if table.dim() != 1 or nbytes == 0 or table.numel() * 4 != nbytes or table.device != x.device:
+        raise _lib.TadError(f"multiscale_crop.table: expected the device copy of multiscale_crop_table() for {B} clips ({nbytes} bytes), "
+                            f"got {tuple(table.shape)} on {table.device}")
+    if (mean is None) != (std is None):
+        raise _lib.TadError("multiscale_crop: mean and std come together")
+    f32 = mean is not None
+    shape = (B, 3, T, S_h, S_w) if f32 else (B, T, S_h, S_w, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32 if f32 else torch.uint8, device=x.device)
+    else:
+        _req(out, torch.float32 if f32 else torch.uint8, "multiscale_crop.out")
+        if tuple(out.shape) != shape or out.device != x.device:
+            raise _lib.TadError(f"multiscale_crop.out: expected {shape} on {x.device}, got {tuple(out.shape)} on {out.device}")
+    m = s = None
+    if f32:
+        m, s = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    with _timed("multiscale_crop", 0.0, float(x.numel() + out.numel() * out.element_size())):
+        check(lib.tad_multiscale_crop(x.data_ptr(), out.data_ptr(), int(f32), m, s, table.data_ptr(), nbytes, B, T, Hs, Ws, S_h, S_w,
+                                      n_hsets, n_vsets, _stream()), "tad_multiscale_crop")
+    return out
+
+
 def soft_target_ce(logits, target=None, labels=None, smoothing: float = 0.0):
     """(loss [1], dlogits [B,classes]) of the batch-mean soft-target cross entropy over f32 logits, ONE launch (tad_soft_target_ce):
     ``target`` f32 [B,classes], or int64 ``labels`` [B] smoothed on the fly."""
