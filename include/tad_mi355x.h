@@ -390,6 +390,29 @@ int tad_mixup_target(const int32_t* plan, const int64_t* labels, float* out, int
  * int64 labels.  Exactly one of target / labels is non-NULL; smoothing in [0, 1) (ignored with target). */
 int tad_soft_target_ce(const float* logits, const float* target, const int64_t* labels, float smoothing, float* loss, float* dlogits,
                        int B, int num_classes, tad_stream_t stream);
+/* The losses of the frame fine-tuning recipe (run_frame_finetuning.py:571-586: utils.FocalLoss / FocalLoss2 / TemporalExponentialLoss /
+ * DoubleBCELoss / SmoothAPLoss), forward and gradient in ONE launch of one workgroup, a wave per row of f32 logits [B,num_classes]:
+ *   loss[0] = the criterion's value (mean reduction), dlogits [B,num_classes] = d loss / d logits (the backward pass scales it).
+ * With ce_b = logsumexp(logits[b]) - logits[b][labels[b]] and pt_b = exp(-ce_b):
+ *   TAD_FRAME_LOSS_FOCAL        mean_b multiplier * alpha * (1 - pt_b)^gamma * ce_b
+ *   TAD_FRAME_LOSS_FOCAL2       the same with class_alpha[labels[b]] (f32 [num_classes]; NULL: weight 1) in place of alpha
+ *   TAD_FRAME_LOSS_EXPONENTIAL  mean_b w_b * ce_b, w_b = min(1, t < 0 ? exp(alpha_pre * t) : t > 0 ? exp(-alpha_post * t) : 1), t = ttc[b]
+ *                               (f32 [B]; a NaN t gives weight 1, as the reference's masks do)
+ *   TAD_FRAME_LOSS_BCE2         mean_b sum_{c in 0,1} bce_with_logits(logits[b][c], soft[b][c])        (soft f32 [B,2]; num_classes == 2)
+ *   TAD_FRAME_LOSS_SMOOTHAP     (1 / max(P,1)) sum_{i: labels[i] == 1} sum_{j: labels[j] == 0} relu(p_j - p_i + delta), p = softmax(logits)[1],
+ *                               P = number of rows with label 1 (num_classes == 2; no positive row: loss 0 and dlogits 0)
+ * Each kind takes exactly its operands, the others NULL: labels (int64 [B]) for every kind but BCE2, soft for BCE2, ttc for EXPONENTIAL,
+ * class_alpha optionally for FOCAL2.  gamma >= 1 for the focal kinds (below 1 the derivative is unbounded at pt = 1); gamma, multiplier and
+ * delta finite and non-negative.  A label outside [0, num_classes) is the caller's error, as for tad_soft_target_ce: it is not checked,
+ * and under FOCAL2 it indexes class_alpha. */
+#define TAD_FRAME_LOSS_FOCAL 0
+#define TAD_FRAME_LOSS_FOCAL2 1
+#define TAD_FRAME_LOSS_EXPONENTIAL 2
+#define TAD_FRAME_LOSS_BCE2 3
+#define TAD_FRAME_LOSS_SMOOTHAP 4
+int tad_frame_loss(int kind, const float* logits, const int64_t* labels, const float* soft, const float* ttc, const float* class_alpha,
+                   float alpha, float gamma, float multiplier, float alpha_pre, float alpha_post, float delta, float* loss, float* dlogits,
+                   int B, int num_classes, tad_stream_t stream);
 
 /* RandomErasing of the fine-tune recipe on the device (random_erasing.py:151-173, applied by the datasets to every normalised clip
  * with --reprob 0.25 --remode pixel --recount 1, max_area 0.1, one box per clip shared by its frames).

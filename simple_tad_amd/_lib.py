@@ -67,6 +67,7 @@ SIGNATURES = {
     "tad_mixup_clips": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "tad_mixup_target": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp]),
     "tad_soft_target_ce": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp]),
+    "tad_frame_loss": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp, _i, _i, _vp]),
     "tad_erase_plan_check": (_i, [_vp, _i, _i, _i, _i, _i]),
     "tad_erase_clips": (_i, [_vp, _vp, _i, C.c_uint32, _i, _i, _i, _i, _i, _vp]),
     "tad_randaug_plan_check": (_i, [_vp, _i64, _i, _i, _i]),
@@ -126,6 +127,7 @@ ADAMW_MAX_GROUPS = 128
 EMA_CHUNK = 8192
 MIXUP_PLAN_WORDS = 12
 MIX_KEEP, MIX_BLEND, MIX_PASTE = 0, 1, 2
+FRAME_LOSS_KINDS = {"focal": 0, "focal2": 1, "exponential": 2, "2bce": 3, "smoothap": 4}
 ERASE_BOX_WORDS = 8
 ERASE_CONST, ERASE_RAND, ERASE_PIXEL = 0, 1, 2
 RANDAUG_ROW_WORDS = 20

@@ -308,10 +308,31 @@ def train_class_batch(model, samples, target, criterion):
     return loss, outputs
 
 
+def train_class_batch_ttc(model, samples, target, ttc, criterion):
+    """engine_for_frame_finetuning.py:33-36"""
+    outputs = model(samples)
+    loss = criterion(outputs, target, ttc)
+    return loss, outputs
+
+
+def _loss_inputs(batch, targets, device, with_ttc, smoothed_labels_for_loss):
+    """engine_for_frame_finetuning.py:114-120: (targets of the loss, ttc or None) from ``extra_info = batch[3]``"""
+    targets_loss = batch[3]["smoothed_labels"].to(device, non_blocking=True) if smoothed_labels_for_loss else targets
+    ttc = batch[3]["ttc"].to(device, non_blocking=True) if with_ttc else None
+    return targets_loss, ttc
+
+
 def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable, optimizer, device, epoch: int, loss_scaler,
                     max_norm: float = 0, start_steps=0, lr_schedule_values=None, wd_schedule_values=None,
-                    num_training_steps_per_epoch=None, update_freq=1, log=None, model_ema=None, augment_fn=None, erase_fn=None, mixup_fn=None):
+                    num_training_steps_per_epoch=None, update_freq=1, log=None, model_ema=None, with_ttc=False, smoothed_labels_for_loss=False,
+                    augment_fn=None, erase_fn=None, mixup_fn=None):
     """engine_for_finetuning.train_one_epoch (engine_for_finetuning.py:24-140) without the DeepSpeed branches.
+    ``with_ttc`` / ``smoothed_labels_for_loss`` are the two switches of engine_for_frame_finetuning.train_one_epoch (:49, :114-142), for
+    the criteria of ``loss.build_criterion``: the loader's fourth item, ``extra_info = batch[3]``, is then a dict with ``"ttc"`` (time to
+    the anomaly per sample, ``frame_targets.compute_time_vector``) and ``"smoothed_labels"`` ([B,2], ``frame_targets.smooth_labels``).
+    With ``smoothed_labels_for_loss`` the smoothed labels replace the targets FOR THE LOSS ONLY (``class_acc`` keeps the hard targets);
+    with ``with_ttc`` the criterion is called as ``criterion(outputs, targets_loss, ttc)``.  As in the reference, a ``mixup_fn`` does
+    not reach the loss targets once they are taken (:114-123).
     ``mixup_fn`` (a ``mixup.Mixup`` or anything with ``(samples, targets) -> (samples, soft_targets)``) is applied to every batch once it
     is on the device (:59-60); the criterion then has to take soft targets (``loss.SoftTargetCrossEntropy``), and ``class_acc`` is
     logged as ``None`` for the step, as the reference does (:104-107), so it does not appear in ``averaged``.
@@ -352,9 +373,16 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable, op
             samples = augment_fn(samples)
         if erase_fn is not None:
             samples = erase_fn(samples)
+        if with_ttc or smoothed_labels_for_loss:
+            targets_loss, ttc = _loss_inputs(batch, targets, device, with_ttc, smoothed_labels_for_loss)
         if mixup_fn is not None:
             samples, targets = mixup_fn(samples, targets)
-        loss, output = train_class_batch(model, samples, targets, criterion)
+        if with_ttc:
+            loss, output = train_class_batch_ttc(model, samples, targets_loss, ttc, criterion)
+        elif smoothed_labels_for_loss:
+            loss, output = train_class_batch(model, samples, targets_loss, criterion)
+        else:
+            loss, output = train_class_batch(model, samples, targets, criterion)
         loss_value = loss.item()
         if not math.isfinite(loss_value):
             print("Loss is {}, stopping training".format(loss_value))
@@ -402,18 +430,22 @@ def gather_predictions(tensors, world_size=None):
 
 
 @torch.no_grad()
-def validation_one_epoch(data_loader, model, device):
-    """engine_for_frame_finetuning.validation_one_epoch (:282-383) without the TTC / smoothed-label / plotting branches: eval-mode
-    forward over the loader, CE loss and top-1 per batch, predictions gathered across ranks, then ``metrics.calculate_metrics``."""
+def validation_one_epoch(data_loader, model, device, criterion=None, with_ttc=False, smoothed_labels_for_loss=False):
+    """engine_for_frame_finetuning.validation_one_epoch (:282-383) without the plotting branches: eval-mode forward over the loader,
+    loss and top-1 per batch, predictions gathered across ranks, then ``metrics.calculate_metrics``.  ``criterion`` (default: the
+    reference's ``CrossEntropyLoss``), ``with_ttc`` and ``smoothed_labels_for_loss`` mean what they mean in ``train_one_epoch``
+    (:302-318): the loss takes ``batch[3]["smoothed_labels"]`` / ``batch[3]["ttc"]``, accuracy and metrics the hard targets."""
     from . import metrics as M
-    criterion = torch.nn.CrossEntropyLoss()
+    if criterion is None:
+        criterion = torch.nn.CrossEntropyLoss()
     model.eval()
     preds, labels, losses, correct, seen = [], [], [], 0, 0
     for batch in data_loader:
         videos = batch[0].to(device, non_blocking=True)
         target = batch[1].to(device, non_blocking=True)
         output = model(videos)
-        losses.append(criterion(output, target).item())
+        targets_loss, ttc = _loss_inputs(batch, target, device, with_ttc, smoothed_labels_for_loss)
+        losses.append((criterion(output, targets_loss, ttc) if with_ttc else criterion(output, targets_loss)).item())
         correct += int((output.max(-1)[1] == target).sum())
         seen += videos.shape[0]
         preds.append(output.detach())

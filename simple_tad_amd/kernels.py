@@ -1073,6 +1073,31 @@ def soft_target_ce(logits, target=None, labels=None, smoothing: float = 0.0):
     return loss, dlogits
 
 
+def frame_loss(kind: str, logits, labels=None, soft=None, ttc=None, class_alpha=None, alpha: float = 1.0, gamma: float = 2.0,
+               multiplier: float = 1.0, alpha_pre: float = 0.1, alpha_post: float = 0.5, delta: float = 0.01):
+    """(loss [1], dlogits [B,classes]) of one of the frame fine-tuning losses over f32 logits, ONE launch (tad_frame_loss):
+    ``kind`` in focal | focal2 | exponential | 2bce | smoothap; int64 ``labels`` [B], f32 ``soft`` [B,2], f32 ``ttc`` [B], f32
+    ``class_alpha`` [classes] -- each kind takes exactly its own operands (include/tad_mi355x.h)."""
+    if kind not in _lib.FRAME_LOSS_KINDS:
+        raise _lib.TadError(f"frame_loss: unknown kind {kind!r} (one of {sorted(_lib.FRAME_LOSS_KINDS)})")
+    _req(logits, torch.float32, "frame_loss.logits")
+    if logits.dim() != 2:
+        raise _lib.TadError(f"frame_loss.logits: expected [B,classes], got {tuple(logits.shape)}")
+    B, ncls = logits.shape
+    for t, dtype, shape, name in ((labels, torch.int64, (B,), "labels"), (soft, torch.float32, (B, 2), "soft"), (ttc, torch.float32, (B,), "ttc"),
+                                  (class_alpha, torch.float32, (ncls,), "class_alpha")):
+        if t is not None:
+            _req(t, dtype, "frame_loss." + name)
+            if tuple(t.shape) != shape or t.device != logits.device:
+                raise _lib.TadError(f"frame_loss.{name}: expected {list(shape)} on {logits.device}, got {list(t.shape)} on {t.device}")
+    loss = torch.empty((1,), dtype=torch.float32, device=logits.device)
+    dlogits = torch.empty((B, ncls), dtype=torch.float32, device=logits.device)
+    check(_lib.load().tad_frame_loss(_lib.FRAME_LOSS_KINDS[kind], logits.data_ptr(), _p(labels), _p(soft), _p(ttc), _p(class_alpha), float(alpha),
+                                     float(gamma), float(multiplier), float(alpha_pre), float(alpha_post), float(delta), loss.data_ptr(),
+                                     dlogits.data_ptr(), B, ncls, _stream()), "tad_frame_loss")
+    return loss, dlogits
+
+
 # ----------------------------------------------------------------------------- MAE pre-training path (SURVEY 8f-2)
 def _idx(t, name):
     if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous():
