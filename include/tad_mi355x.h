@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define TAD_ABI_VERSION 4
+#define TAD_ABI_VERSION 5
 
 enum tad_status {
   TAD_OK = 0,
@@ -256,27 +256,48 @@ int tad_linear_bwd_weight(const uint16_t* dy, const uint16_t* x, float* dW, floa
  * flash_attn_varlen_qkvpacked_func, flash_attention_class.py:56-61): element (b, h, query, key) is kept iff
  * hash((b H + h) N + query, key, seed) >= dropout_p * 2^32 (csrc/common.h: drop_keep; oracle/vit_oracle.py:
  * attention_dropout_keep regenerates the mask) and kept probabilities are scaled by 1 / (1 - dropout_p); lse is that of the full
- * softmax.  tad_attn_bwd must be given the same dropout_p and seed.  0 = no dropout (evaluation). */
-int tad_attn_fwd(const uint16_t* qkv, void* out, int out_dtype, uint16_t* out_lo, float* lse, int B, int N, int H, int d,
-                 float scale, int q_prescaled, float dropout_p, uint32_t seed, tad_stream_t stream);
+ * softmax.  tad_attn_bwd must be given the same dropout_p and seed.  0 = no dropout (evaluation).
+ * clip_scale (nullable; tad_attn_fwd and tad_attn_bwd, either operand type): stochastic depth (DropPath around the attention branch,
+ * modeling_finetune.py:159-163).  [B] f32 in device memory, ONE scale per clip (mask / keep_prob): the scale by which the residual epilogue
+ * behind the attention multiplies the branch -- the rowscale of tad_linear_fwd's TAD_EPI_BIAS_RESIDUAL with rows_per_scale = N.  A clip whose
+ * scale is exactly 0 reaches the result neither forward (0 x branch) nor backward (its dout rows are exact zeros), so the kernels do not
+ * compute it: the forward writes zeros to its rows of out / out_lo and a finite placeholder to lse, the backward zeros to its rows of dqkv --
+ * what the computation would have stored there in the backward's case, and values that only ever meet a zero factor in the forward's.  The
+ * scale is read on the device (no host copy, no synchronisation).  head_dim 64 with pre-scaled q, 16-bit output and no attention dropout
+ * takes the path; every other contract, and every call without a clip_scale, computes all clips (which kernel a call takes: tad_attn_plan). */
+int tad_attn_fwd(const uint16_t* qkv, void* out, int out_dtype, uint16_t* out_lo, float* lse, const float* clip_scale, int B, int N, int H,
+                 int d, float scale, int q_prescaled, float dropout_p, uint32_t seed, tad_stream_t stream);
 /* dqkv [B,N,3,H,d] bf16 (fully overwritten).  delta: scratch of tad_attn_bwd_scratch_bytes(B, N, H) bytes = 2*B*H*N floats (the
  * first kernel leaves -rowsum(dout*out) in [0, BHN) and -lse/scale (-lse*log2(e) with q_prescaled) in [BHN, 2 BHN) for the second
  * one, which takes them as the initial values of its accumulators).  The q slot of dqkv is the gradient of the PLAIN q in either case. */
-/* Knob of the three attention kernels.  "dma_mode": 0 = production; 2 / 3 = timing-only ablations (wrong results) that only
- * ablation builds (TAD_BUILD_ABLATION=1) accept.  "drop_skip": 1 (default; environment TAD_DROP_SKIP=0 starts it at 0) = the calls that
- * follow a tad_attn_drop_scale fill the clips it marks as dropped instead of computing them; 0 = they compute every clip (A/B runs;
- * every result the training step consumes is bit-identical either way). */
+/* Knobs of the three attention kernels (one table, csrc/attn_plan.hip; the environment variable gives the initial value):
+ *   "dma_mode"   TAD_ATTN_DMA_MODE   0 = production; 2 / 3 = timing-only ablations (wrong results) that only ablation builds
+ *                                    (TAD_BUILD_ABLATION=1) accept
+ *   "fwd_q64"    TAD_ATTN_FWD_Q64    1 = the forward of the production contract runs with 64 query rows per wave (experiment, bit-identical);
+ *                                    0 (default)
+ *   "drop_skip"  TAD_DROP_SKIP       1 (default) = calls with a clip_scale fill the clips it marks as dropped instead of computing them;
+ *                                    0 = they compute every clip (A/B runs; every result the training step consumes is bit-identical either way) */
 int tad_attn_tuning(const char* key, int value);
-/* Stochastic depth (DropPath around the attention branch, modeling_finetune.py:159-163): hands the NEXT tad_attn_fwd / tad_attn_bwd
- * call of the calling thread (either operand type; that call consumes the setting whatever it does with it) the per-clip scale
- * rowscale [B] f32 (device memory; mask / keep_prob) by which the residual epilogue behind the attention multiplies the branch --
- * the rowscale / rows_per_scale pair of tad_linear_fwd's TAD_EPI_BIAS_RESIDUAL, rows_per_scale = N.  A clip whose scale is exactly 0
- * reaches the result neither forward (0 x branch) nor backward (its dout rows are exact zeros), so the kernels do not compute it: the
- * forward writes zeros to its rows of out / out_lo and a finite placeholder to lse, the backward zeros to its rows of dqkv -- what
- * the computation would have stored there in the backward's case, and values that only ever meet a zero factor in the forward's.
- * The scale is read on the device (no host copy, no synchronisation); head_dim 64 with pre-scaled q, 16-bit output and no attention
- * dropout takes the path, every other contract computes all clips as without the call.  NULL clears a pending setting. */
-int tad_attn_drop_scale(const float* rowscale, int rows_per_scale);
+/* Current value of a tad_attn_tuning knob (what a temporary change has to put back). */
+int tad_attn_tuning_get(const char* key, int* value);
+/* Which kernels a tad_attn_fwd (backward == 0) or tad_attn_bwd call WOULD launch under the current knobs -- the records the entry points
+ * execute, as data; both operand formats select alike.  Launches nothing and needs no device (simple_tad_amd.kernels.attn_plan;
+ * tests/test_attn_plan_cpu.py).  out_16bit: the forward's output has the 16-bit operand format (else f32); has_clip_scale / has_out_lo: the
+ * nullable operand is given (the backward ignores out_16bit and has_out_lo).  The rule:
+ *   forward   with "fwd_q64" on, head_dim 64 + pre-scaled q + no dropout + 16-bit output runs the 64-row kernel, whether or not there is a
+ *             clip scale; else a call with a clip scale, "drop_skip" on, "dma_mode" 0 and that same contract runs the general kernel with
+ *             SKIP (it fills dropped clips); every other call runs the general kernel for its (d, output type, q_prescaled, dropout > 0),
+ *             which never looks at a clip scale
+ *   backward  two launches, dQ then dK/dV, with the same arguments: SKIP under the forward's conditions except the output type, else general
+ * Writes one row of TAD_ATTN_PLAN_WORDS int32 per launch and returns their number (1 or 2), TAD_ENOSPACE when `capacity` is smaller, or the
+ * error the entry point would refuse the shape with.  A row is
+ *   kernel          0 attn_fwd_kernel, 1 attn_fwd_q64_kernel, 2 attn_bwd_dq_kernel, 3 attn_bwd_dkv_kernel
+ *   hd, out16, qs, drop, dma_mode, skip    the template arguments HD, OUT_BF16 (backward: 1), QS, DROP, DMA_MODE, SKIP
+ *   has_lo          HAS_LO of the 64-row kernel (0 elsewhere)
+ *   grid, block     ceil(N / 128) * H * B workgroups of 256 threads (128 for the 64-row kernel) */
+#define TAD_ATTN_PLAN_WORDS 10
+int tad_attn_plan(int backward, int B, int N, int H, int d, int out_16bit, int q_prescaled, float dropout_p, int has_clip_scale,
+                  int has_out_lo, int32_t* launches, int capacity);
 size_t tad_attn_bwd_scratch_bytes(int B, int N, int H);
 /* Diagnostic, ablation builds only (see tad_linear_debug_stamps): while buf (device memory, 32 bytes per workgroup of the dK/dV grid
  * = ceil(N/128)*H*B workgroups) is set, every dK/dV workgroup records {s_memrealtime, s_memtime} at the start and at the end of its
@@ -286,8 +307,8 @@ int tad_attn_debug_stamps(void* buf);
  * is what cancels against the dP the kernels recompute (without it the q / k gradients of near-uniform attention rows carry the
  * rounding of out amplified by |delta| / |dP - delta|). */
 int tad_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* out_lo, const uint16_t* dout, const float* lse,
-                 uint16_t* dqkv, float* delta, int B, int N, int H, int d, float scale, int q_prescaled, float dropout_p,
-                 uint32_t seed, tad_stream_t stream);
+                 const float* clip_scale, uint16_t* dqkv, float* delta, int B, int N, int H, int d, float scale, int q_prescaled,
+                 float dropout_p, uint32_t seed, tad_stream_t stream);
 
 /* ---- token mean-pool x.mean(1) (modeling_finetune.py:325-326) -------------------------
  * x [B,N,D] f32 -> y [B,D] f32.  ws: B*TAD_POOL_SPLIT*D floats. */
@@ -635,11 +656,11 @@ int tad_linear_bwd_weight_qkv_f16(const uint16_t* dy, const uint16_t* x, float* 
 int tad_linear_bwd_weight_pair_f16(const uint16_t* dy1, const uint16_t* x1, float* dW1, float* db1, float* db1b, int N1,
                                    const uint16_t* dy2, const uint16_t* x2, float* dW2, int N2, int accumulate, void* ws,
                                    size_t ws_bytes, int64_t M, int K, tad_stream_t stream);
-int tad_attn_fwd_f16(const uint16_t* qkv, void* out, int out_dtype, uint16_t* out_lo, float* lse, int B, int N, int H, int d,
-                     float scale, int q_prescaled, float dropout_p, uint32_t seed, tad_stream_t stream);
+int tad_attn_fwd_f16(const uint16_t* qkv, void* out, int out_dtype, uint16_t* out_lo, float* lse, const float* clip_scale, int B, int N,
+                     int H, int d, float scale, int q_prescaled, float dropout_p, uint32_t seed, tad_stream_t stream);
 int tad_attn_bwd_f16(const uint16_t* qkv, const uint16_t* out, const uint16_t* out_lo, const uint16_t* dout, const float* lse,
-                     uint16_t* dqkv, float* delta, int B, int N, int H, int d, float scale, int q_prescaled, float dropout_p,
-                     uint32_t seed, tad_stream_t stream);
+                     const float* clip_scale, uint16_t* dqkv, float* delta, int B, int N, int H, int d, float scale, int q_prescaled,
+                     float dropout_p, uint32_t seed, tad_stream_t stream);
 int tad_meanpool_bwd_f16(const float* dy, float* dx, uint16_t* dx_f16, int B, int N, int D, tad_stream_t stream);
 int tad_adamw_step_f16(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, uint16_t* param_f16,
                        const uint8_t* chunk_group, int64_t n, const float* group_lr, const float* group_wd, int n_groups,

@@ -44,12 +44,13 @@ SIGNATURES = {
     "tad_linear_bwd_input": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _sz, _i64, _i, _i, _vp]),
     "tad_linear_bwd_weight_workspace_bytes": (_sz, [_i64, _i, _i]),
     "tad_linear_bwd_weight": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _sz, _i64, _i, _i, _vp]),
-    "tad_attn_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _i, _f, C.c_uint32, _vp]),
+    "tad_attn_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _f, C.c_uint32, _vp]),
     "tad_attn_tuning": (_i, [C.c_char_p, _i]),
-    "tad_attn_drop_scale": (_i, [_vp, _i]),
+    "tad_attn_tuning_get": (_i, [C.c_char_p, C.POINTER(_i)]),
+    "tad_attn_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _f, _i, _i, C.POINTER(C.c_int32), _i]),
     "tad_attn_bwd_scratch_bytes": (_sz, [_i, _i, _i]),
     "tad_attn_debug_stamps": (_i, [_vp]),
-    "tad_attn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _f, C.c_uint32, _vp]),
+    "tad_attn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _f, C.c_uint32, _vp]),
     "tad_meanpool_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "tad_meanpool_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "tad_colsum_workspace_bytes": (_sz, [_i64, _i]),
@@ -119,8 +120,10 @@ F16_TWINS = {
 for _bf, _h in F16_TWINS.items():
     SIGNATURES[_h] = SIGNATURES[_bf]
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL = 0, 1, 2
-ABI_VERSION = 4
+ABI_VERSION = 5
 LINEAR_PLAN_FIELDS = ("r0", "rows", "kernel", "persistent", "direct", "grid", "block", "group_m", "sk_splits", "sk_mode", "epilogue")
+ATTN_PLAN_FIELDS = ("kernel", "hd", "out16", "qs", "drop", "dma_mode", "skip", "has_lo", "grid", "block")
+ATTN_FWD, ATTN_FWD_Q64, ATTN_BWD_DQ, ATTN_BWD_DKV = range(4)  # the "kernel" field
 LINEAR_BWD_WEIGHT_PLAN_FIELDS = ("N", "tile_k", "tiles", "tiles_k", "splits", "rows_per_split", "kernel", "grid", "block", "pair", "ws_lo", "ws_hi")
 ADAMW_CHUNK = 4096
 ADAMW_MAX_GROUPS = 128

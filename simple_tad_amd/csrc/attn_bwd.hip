@@ -16,10 +16,10 @@
 //
 // Tiles that are read both by rows (ds_read_b128) and transposed (ds_read_b64_tr_b16) use one LDS image with a
 // swizzle that is conflict-free for both (found by tools/lds_bank_sim.py).
-#include <stdlib.h>
-#include <string.h>
 #include <type_traits>
+#include <utility>
 #include "common.h"
+#include "attn_plan.h"
 
 TAD_NAMESPACE_BEGIN
 
@@ -640,126 +640,43 @@ TAD_NAMESPACE_END
 
 using namespace tad;
 
-// Process-wide state of the attention kernels: one copy for the library (defined by the bf16 pass, shared by the half pass).
-namespace tad { namespace knobs {
-#ifndef TAD_OPND_F16
-unsigned long long* attn_stamps = nullptr;
-int attn_dma_mode = getenv("TAD_ATTN_DMA_MODE") ? atoi(getenv("TAD_ATTN_DMA_MODE")) : 0;  // 2 / 3: timing-only ablations (ablation builds); shared with attn_fwd.hip
-int attn_fwd_q64 = getenv("TAD_ATTN_FWD_Q64") ? atoi(getenv("TAD_ATTN_FWD_Q64")) : 0;  // 1: the forward with 64 query rows per wave (attn_fwd_q64_kernel; experiment, round 6)
-int attn_drop_skip = getenv("TAD_DROP_SKIP") ? atoi(getenv("TAD_DROP_SKIP")) != 0 : 1;  // 0: clips dropped by stochastic depth are computed like the others (A/B runs)
-// what tad_attn_drop_scale left for the calling thread's next attention call
-static thread_local const float* drop_scale = nullptr;
-static thread_local int drop_scale_rows = 0;
-// The scale pointer for an attention call over sequences of N rows, or null (none set, or the knob is off); clears it.  *ok = false: it was
-// set with another rows_per_scale than N.
-const float* take_drop_scale(int N, bool* ok) {
-  const float* const rs = drop_scale;
-  *ok = !rs || drop_scale_rows == N;
-  drop_scale = nullptr;
-  return (*ok && attn_drop_skip) ? rs : nullptr;
-}
-#else
-extern unsigned long long* attn_stamps;
-extern int attn_dma_mode, attn_fwd_q64;
-const float* take_drop_scale(int N, bool* ok);
-#endif
-}}  // namespace tad::knobs
-using namespace tad::knobs;
-
-#ifndef TAD_OPND_F16
-extern "C" int tad_attn_tuning(const char* key, int value) {
-  TAD_REQUIRE(key, "attn_tuning: null key");
-  if (!strcmp(key, "dma_mode")) {
+// The instantiations of this pass, looked up by the fields of the selector's records (attn_plan.h)
+typedef void (*DqKernel)(const uint16_t*, const uint16_t*, const uint16_t*, const uint16_t*, const float*, float*, uint16_t*, int, int, int, float, const Drop,
+                         const float*);
+typedef void (*DkvKernel)(const uint16_t*, const uint16_t*, const float*, uint16_t*, int, int, int, float, unsigned long long*, const Drop, const float*);
 #ifdef TAD_GEMM_ABLATION
-    TAD_REQUIRE(value == 0 || value == 2 || value == 3, "attn_tuning: dma_mode=%d not in {0, 2, 3}", value);
+constexpr size_t BWD_GENERAL = 24;  // DMA_MODE 0, 2, 3
 #else
-    TAD_REQUIRE(value == 0, "attn_tuning: dma_mode=%d: only 0 outside ablation builds (2 / 3 are timing-only ablations)", value);
+constexpr size_t BWD_GENERAL = 8;
 #endif
-    attn_dma_mode = value;
-    return TAD_OK;
-  }
-  if (!strcmp(key, "fwd_q64")) {
-    TAD_REQUIRE(value == 0 || value == 1, "attn_tuning: fwd_q64=%d not in {0, 1}", value);
-    attn_fwd_q64 = value;
-    return TAD_OK;
-  }
-  if (!strcmp(key, "drop_skip")) {
-    TAD_REQUIRE(value == 0 || value == 1, "attn_tuning: drop_skip=%d not in {0, 1}", value);
-    attn_drop_skip = value;
-    return TAD_OK;
-  }
-  set_error("attn_tuning: unknown key '%s'", key);
-  return TAD_EINVAL;
+// general kernels (SKIP = 0), index = [DMA_MODE 0 2 3][HD == 80][QS][DROP]
+constexpr int bwd_dma_mode(size_t i) { return i < 8 ? 0 : (int)(i / 8) + 1; }
+static size_t bwd_index(const AttnLaunch& l) { return (size_t)((l.dma_mode ? l.dma_mode - 1 : 0) * 8 + (l.hd == 80) * 4 + l.qs * 2 + l.drop); }
+template <size_t... I>
+static DqKernel dq_kernel(const AttnLaunch& l, std::index_sequence<I...>) {
+  static const DqKernel general[] = {attn_bwd_dq_kernel<(I & 4) ? 80 : 64, (I & 2) != 0, (I & 1) != 0, bwd_dma_mode(I)>...};
+  return l.skip ? attn_bwd_dq_kernel<64, true, false, 0, true> : general[bwd_index(l)];
 }
-
-extern "C" int tad_attn_drop_scale(const float* rowscale, int rows_per_scale) {
-  TAD_REQUIRE(!rowscale || rows_per_scale > 0, "attn_drop_scale: rows_per_scale must be positive");
-  drop_scale = rowscale;
-  drop_scale_rows = rowscale ? rows_per_scale : 0;
-  return TAD_OK;
+template <size_t... I>
+static DkvKernel dkv_kernel(const AttnLaunch& l, std::index_sequence<I...>) {
+  static const DkvKernel general[] = {attn_bwd_dkv_kernel<(I & 4) ? 80 : 64, (I & 2) != 0, (I & 1) != 0, bwd_dma_mode(I)>...};
+  return l.skip ? attn_bwd_dkv_kernel<64, true, false, 0, true> : general[bwd_index(l)];
 }
-
-// Diagnostic (ablation builds only, like tad_linear_debug_stamps): while buf (device memory, 32 bytes per workgroup of the dK/dV grid)
-// is set, workgroup w records {s_memrealtime, s_memtime} at the start and at the end of its tile loop in buf[4w .. 4w+3].
-extern "C" int tad_attn_debug_stamps(void* buf) {
-#ifndef TAD_GEMM_ABLATION
-  if (buf) { set_error("attn_debug_stamps: needs an ablation build (TAD_BUILD_ABLATION=1 python -m simple_tad_amd.build --force)"); return TAD_EINVAL; }
-#endif
-  attn_stamps = (unsigned long long*)buf;
-  return TAD_OK;
-}
-
-extern "C" size_t tad_attn_bwd_scratch_bytes(int B, int N, int H) {
-  if (B <= 0 || N <= 0 || H <= 0) return 0;
-  return (size_t)2 * B * H * N * sizeof(float);
-}
-#endif
 
 extern "C" int tad_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* out_lo, const uint16_t* dout, const float* lse,
-                            uint16_t* dqkv, float* delta, int B, int N, int H, int d, float scale, int q_prescaled, float dropout_p,
-                            uint32_t seed, tad_stream_t stream) {
-  bool rs_ok;
-  const float* const clip_scale = take_drop_scale(N, &rs_ok);  // (consumed by this call whatever route it takes)
-  TAD_REQUIRE(rs_ok, "attn_bwd: the scale set by tad_attn_drop_scale is one per clip: rows_per_scale must be N=%d", N);
+                            const float* clip_scale, uint16_t* dqkv, float* delta, int B, int N, int H, int d, float scale, int q_prescaled,
+                            float dropout_p, uint32_t seed, tad_stream_t stream) {
   TAD_REQUIRE(qkv && out && dout && lse && dqkv && delta, "attn_bwd: null pointer");
-  TAD_REQUIRE(d == 64 || d == 80, "attn_bwd: head_dim must be 64 or 80 (got %d)", d);
-  const int BHD = d;
-  TAD_REQUIRE(B > 0 && N > 0 && H > 0 && H <= 65535 && B <= 65535, "attn_bwd: bad shape");
-  TAD_REQUIRE(scale > 0.f, "attn_bwd: scale must be positive");
+  AttnLaunch l[2];
+  if (const int rc = attn_plan_bwd(AttnCall{B, N, H, d, TAD_OP16, TAD_OP16, q_prescaled, scale, dropout_p, clip_scale != nullptr, out_lo != nullptr}, l)) return rc;
   Drop drop;
-  TAD_REQUIRE(make_drop(dropout_p, seed, &drop), "attn_bwd: dropout_p=%g outside [0, 1)", (double)dropout_p);
-  TAD_REQUIRE((int64_t)B * H * N * 8 < (1ll << 31), "attn_bwd: B*H*N too large for the row-constant descriptor");
-  TAD_REQUIRE((int64_t)B * N * 3 * H * BHD * 2 < (1ll << 32), "attn_bwd: qkv exceeds the 4 GiB buffer descriptor (B=%d N=%d H=%d)", B, N, H);
+  make_drop(dropout_p, seed, &drop);
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)(((N + 127) / 128) * H * B)), block(256);
-  const int mode = attn_dma_mode;
-  // clips dropped by stochastic depth fill instead of compute: the production contract of the training step only (any other one computes them)
-  if (clip_scale && d == 64 && q_prescaled && dropout_p == 0.f && mode == 0) {
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<64, true, false, 0, true>), grid, block, 0, st, qkv, out, out_lo, dout, lse, delta, dqkv, N, H, B, scale, drop, clip_scale);
-    int rc = check_launch("attn_bwd_dq");
-    if (rc) return rc;
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, true, false, 0, true>), grid, block, 0, st, qkv, dout, delta, dqkv, N, H, B, scale, attn_stamps, drop, clip_scale);
-    return check_launch("attn_bwd_dkv");
-  }
-#define LAUNCH_BWD__(Q_, D_, M_)                                                                                             \
-  {                                                                                                                          \
-    if (d == 64) hipLaunchKernelGGL((attn_bwd_dq_kernel<64, Q_, D_, M_>), grid, block, 0, st, qkv, out, out_lo, dout, lse, delta, dqkv, N, H, B, scale, drop, (const float*)nullptr);  \
-    else hipLaunchKernelGGL((attn_bwd_dq_kernel<80, Q_, D_, M_>), grid, block, 0, st, qkv, out, out_lo, dout, lse, delta, dqkv, N, H, B, scale, drop, (const float*)nullptr);  \
-    int rc = check_launch("attn_bwd_dq");                                                                                    \
-    if (rc) return rc;                                                                                                       \
-    if (d == 64) hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, Q_, D_, M_>), grid, block, 0, st, qkv, dout, delta, dqkv, N, H, B, scale, attn_stamps, drop, (const float*)nullptr);  \
-    else hipLaunchKernelGGL((attn_bwd_dkv_kernel<80, Q_, D_, M_>), grid, block, 0, st, qkv, dout, delta, dqkv, N, H, B, scale, attn_stamps, drop, (const float*)nullptr);  \
-    return check_launch("attn_bwd_dkv");                                                                                     \
-  }
-#define LAUNCH_BWD_(Q_, M_) { if (dropout_p > 0.f) LAUNCH_BWD__(Q_, true, M_) else LAUNCH_BWD__(Q_, false, M_) }
-#define LAUNCH_BWD(M_) { if (q_prescaled) LAUNCH_BWD_(true, M_) else LAUNCH_BWD_(false, M_) }
-#ifdef TAD_GEMM_ABLATION
-  if (mode == 2) LAUNCH_BWD(2)
-  if (mode == 3) LAUNCH_BWD(3)  // (dQ kernel: as mode 0; dK/dV kernel: no transposed LDS reads)
-#endif
-  (void)mode;
-  LAUNCH_BWD(0)
-#undef LAUNCH_BWD
-#undef LAUNCH_BWD_
-#undef LAUNCH_BWD__
+  const std::make_index_sequence<BWD_GENERAL> all;
+  hipLaunchKernelGGL(dq_kernel(l[0], all), dim3((unsigned)l[0].grid), dim3((unsigned)l[0].block), 0, st, qkv, out, out_lo, dout, lse, delta, dqkv, N, H, B, scale, drop,
+                     l[0].skip ? clip_scale : nullptr);
+  if (const int rc = check_launch(attn_kernel_name(l[0].kernel))) return rc;
+  hipLaunchKernelGGL(dkv_kernel(l[1], all), dim3((unsigned)l[1].grid), dim3((unsigned)l[1].block), 0, st, qkv, dout, delta, dqkv, N, H, B, scale, knobs::attn_stamps, drop,
+                     l[1].skip ? clip_scale : nullptr);
+  return check_launch(attn_kernel_name(l[1].kernel));
 }

@@ -10,7 +10,9 @@
 // after a pairwise bf16 pack, directly the B operand of the O^T += V^T * P^T MFMA (no LDS round trip for P).  V^T
 // fragments come from the row-major V tile with ds_read_b64_tr_b16 (inline asm with hand-counted waits: common.h).  Both LDS
 // images are XOR-swizzled so all reads are bank-conflict free (tools/lds_bank_sim.py).
+#include <utility>
 #include "common.h"
+#include "attn_plan.h"
 
 TAD_NAMESPACE_BEGIN
 
@@ -577,58 +579,33 @@ TAD_NAMESPACE_END
 
 using namespace tad;
 
-namespace tad { namespace knobs {  // attn_bwd.hip (tad_attn_tuning, tad_attn_drop_scale)
-extern int attn_dma_mode, attn_fwd_q64;
-const float* take_drop_scale(int N, bool* ok);
-} }
-
-extern "C" int tad_attn_fwd(const uint16_t* qkv, void* out, int out_dtype, uint16_t* out_lo, float* lse, int B, int N, int H, int d,
-                            float scale, int q_prescaled, float dropout_p, uint32_t seed, tad_stream_t stream) {
-  bool rs_ok;
-  const float* const clip_scale = tad::knobs::take_drop_scale(N, &rs_ok);  // (consumed by this call whatever route it takes)
-  TAD_REQUIRE(rs_ok, "attn_fwd: the scale set by tad_attn_drop_scale is one per clip: rows_per_scale must be N=%d", N);
-  TAD_REQUIRE(qkv && out, "attn_fwd: null pointer");
-  TAD_REQUIRE(!out_lo || out_dtype == TAD_OP16, "attn_fwd: out_lo (the rounding residual) goes with a 16-bit output");
-  TAD_REQUIRE(d == 64 || d == 80, "attn_fwd: head_dim must be 64 or 80 (got %d)", d);
-  const int HD = d;
-  TAD_REQUIRE(B > 0 && N > 0 && H > 0 && H <= 65535 && B <= 65535, "attn_fwd: bad shape B=%d N=%d H=%d", B, N, H);
-  TAD_REQUIRE(out_dtype == TAD_F32 || out_dtype == TAD_OP16, "attn_fwd: bad out_dtype %d", out_dtype);
-  TAD_REQUIRE(scale > 0.f, "attn_fwd: scale must be positive");
-  Drop drop;
-  TAD_REQUIRE(make_drop(dropout_p, seed, &drop), "attn_fwd: dropout_p=%g outside [0, 1)", (double)dropout_p);
-  TAD_REQUIRE(dropout_p == 0.f || (int64_t)B * H * N < (1ll << 32), "attn_fwd: B*H*N too large for the dropout mask's row index");
-  // the kernel addresses qkv through ONE buffer descriptor with 32-bit byte offsets (K/V staging by LDS-DMA)
-  TAD_REQUIRE((int64_t)B * N * 3 * H * HD * 2 < (1ll << 32), "attn_fwd: qkv of %lld bytes exceeds the 4 GiB buffer descriptor (B=%d N=%d H=%d)",
-              (long long)B * N * 3 * H * HD * 2, B, N, H);
-  TAD_REQUIRE((int64_t)((N + Q_BLOCK - 1) / Q_BLOCK) * H * B < (1ll << 31), "attn_fwd: grid too large");
-  const dim3 grid((unsigned)(((N + Q_BLOCK - 1) / Q_BLOCK) * H * B)), block(256);
-  // (experiment) sixty-four query rows per wave: attn_fwd_q64_kernel, same grid, 128 threads -- only the production contract of the training step
-  if (tad::knobs::attn_fwd_q64 && d == 64 && q_prescaled && dropout_p == 0.f && out_dtype == TAD_OP16) {
-    if (out_lo) hipLaunchKernelGGL((attn_fwd_q64_kernel<true>), grid, dim3(128), 0, (hipStream_t)stream, qkv, (uint16_t*)out, out_lo, lse, N, H, B);
-    else hipLaunchKernelGGL((attn_fwd_q64_kernel<false>), grid, dim3(128), 0, (hipStream_t)stream, qkv, (uint16_t*)out, out_lo, lse, N, H, B);
-    return check_launch("attn_fwd_q64");
-  }
-  // clips dropped by stochastic depth fill instead of compute: the production contract of the training step only (any other one computes them)
-  if (clip_scale && d == 64 && q_prescaled && dropout_p == 0.f && out_dtype == TAD_OP16 && tad::knobs::attn_dma_mode == 0) {
-    hipLaunchKernelGGL((attn_fwd_kernel<64, true, true, false, 0, true>), grid, block, 0, (hipStream_t)stream, qkv, out, out_lo, lse, N, H, B, scale, drop,
-                       clip_scale);
-    return check_launch("attn_fwd");
-  }
-#define LAUNCH_FWD___(H_, O_, Q_, D_, M_) hipLaunchKernelGGL((attn_fwd_kernel<H_, O_, Q_, D_, M_>), grid, block, 0, (hipStream_t)stream, qkv, out, out_lo, lse, N, H, B, scale, drop, (const float*)nullptr)
-#define LAUNCH_FWD__(O_, Q_, D_, M_) { if (d == 64) LAUNCH_FWD___(64, O_, Q_, D_, M_); else LAUNCH_FWD___(80, O_, Q_, D_, M_); }
-#define LAUNCH_FWD_(O_, Q_, M_) { if (dropout_p > 0.f) LAUNCH_FWD__(O_, Q_, true, M_) else LAUNCH_FWD__(O_, Q_, false, M_) }
-#define LAUNCH_FWD(M_)                                                                                \
-  {                                                                                                   \
-    if (out_dtype == TAD_OP16) { if (q_prescaled) LAUNCH_FWD_(true, true, M_) else LAUNCH_FWD_(true, false, M_) }    \
-    else { if (q_prescaled) LAUNCH_FWD_(false, true, M_) else LAUNCH_FWD_(false, false, M_) }         \
-    return check_launch("attn_fwd");                                                                  \
-  }
+// The instantiations of this pass, looked up by the fields of the selector's record (attn_plan.h)
+typedef void (*FwdKernel)(const uint16_t*, void*, uint16_t*, float*, int, int, int, float, const Drop, const float*);
 #ifdef TAD_GEMM_ABLATION
-  if (tad::knobs::attn_dma_mode == 2) LAUNCH_FWD(2)
+constexpr size_t FWD_GENERAL = 32;  // DMA_MODE 0, 2
+#else
+constexpr size_t FWD_GENERAL = 16;
 #endif
-  LAUNCH_FWD(0)
-#undef LAUNCH_FWD
-#undef LAUNCH_FWD_
-#undef LAUNCH_FWD__
-#undef LAUNCH_FWD___
+// general kernels (SKIP = 0), index = [DMA_MODE != 0][HD == 80][OUT_BF16][QS][DROP]
+template <size_t... I>
+static FwdKernel fwd_kernel(const AttnLaunch& l, std::index_sequence<I...>) {
+  static const FwdKernel general[] = {attn_fwd_kernel<(I & 8) ? 80 : 64, (I & 4) != 0, (I & 2) != 0, (I & 1) != 0, (I & 16) ? 2 : 0>...};
+  if (l.skip) return attn_fwd_kernel<64, true, true, false, 0, true>;
+  return general[(l.dma_mode != 0) * 16 + (l.hd == 80) * 8 + l.out16 * 4 + l.qs * 2 + l.drop];
+}
+
+extern "C" int tad_attn_fwd(const uint16_t* qkv, void* out, int out_dtype, uint16_t* out_lo, float* lse, const float* clip_scale, int B, int N, int H,
+                            int d, float scale, int q_prescaled, float dropout_p, uint32_t seed, tad_stream_t stream) {
+  TAD_REQUIRE(qkv && out, "attn_fwd: null pointer");
+  AttnLaunch l;
+  if (const int rc = attn_plan_fwd(AttnCall{B, N, H, d, out_dtype, TAD_OP16, q_prescaled, scale, dropout_p, clip_scale != nullptr, out_lo != nullptr}, &l)) return rc;
+  Drop drop;
+  make_drop(dropout_p, seed, &drop);
+  const dim3 grid((unsigned)l.grid), block((unsigned)l.block);
+  if (l.kernel == ATTN_FWD_Q64)
+    hipLaunchKernelGGL(l.has_lo ? attn_fwd_q64_kernel<true> : attn_fwd_q64_kernel<false>, grid, block, 0, (hipStream_t)stream, qkv, (uint16_t*)out, out_lo, lse, N, H, B);
+  else
+    hipLaunchKernelGGL(fwd_kernel(l, std::make_index_sequence<FWD_GENERAL>{}), grid, block, 0, (hipStream_t)stream, qkv, out, out_lo, lse, N, H, B, scale, drop,
+                       l.skip ? clip_scale : nullptr);
+  return check_launch(attn_kernel_name(l.kernel));
 }

@@ -1,10 +1,10 @@
 // Launch planner of the Linear GEMMs and the process-wide state that goes with it (see gemm_plan.h).  Host code only: compiled once, for
 // both operand formats.  The executors of the plans are in gemm.hip.
 #include <limits.h>
-#include <stdlib.h>
 #include <string.h>
 #include "common.h"
 #include "gemm_plan.h"
+#include "knob.h"
 
 namespace tad {
 
@@ -37,15 +37,6 @@ long long nt_launches = 0;
 using namespace knobs;
 
 namespace {
-enum { KNOB_BOOL = 1, KNOB_ENV_INVERTED = 2 };  // value stored as 0 / 1 | the environment variable switches the knob OFF
-struct Knob {
-  const char* key;  // tad_linear_tuning key (null: environment only)
-  int* v;
-  int lo, hi;  // legal values
-  const char* env;
-  int def;
-  int flags;
-};
 const Knob KNOBS[] = {
     {"debug", &gemm_debug, INT_MIN, INT_MAX, "TAD_GEMM_DEBUG", 0, 0},  // (settable, but no part of the documented defaults: timing experiments on ablation builds)
     {"persistent", &nt_persist, INT_MIN, INT_MAX, "TAD_GEMM_NO_PERSIST", 1, KNOB_BOOL | KNOB_ENV_INVERTED},
@@ -64,19 +55,7 @@ const Knob KNOBS[] = {
     {"tn_w4", &tn_w4, 0, 1, "TAD_GEMM_TN_W4", 1, 0},
     {"tn_pdeep", &tn_pdeep, 0, 1, "TAD_GEMM_TN_PDEEP", 0, 0},
 };
-const bool knobs_from_env = [] {
-  for (const Knob& k : KNOBS) {
-    const char* e = getenv(k.env);
-    if (k.flags & KNOB_ENV_INVERTED) *k.v = !(e ? atoi(e) : 0);
-    else *k.v = e ? atoi(e) : k.def;
-  }
-  return true;
-}();
-const Knob* find_knob(const char* key) {
-  for (const Knob& k : KNOBS)
-    if (k.key && !strcmp(k.key, key)) return &k;
-  return nullptr;
-}
+const bool knobs_initialised = knobs_from_env(KNOBS);
 }  // namespace
 
 // ---- the machine, named once
@@ -443,22 +422,11 @@ using namespace tad;
 extern "C" {
 
 int tad_linear_tuning(const char* key, int value) {
-  TAD_REQUIRE(key, "linear_tuning: null key");
-  const Knob* k = find_knob(key);
-  if (!k) { set_error("linear_tuning: unknown key '%s'", key); return TAD_EINVAL; }
-  TAD_REQUIRE(value >= k->lo && value <= k->hi, "linear_tuning: %s=%d not in %d..%d", key, value, k->lo, k->hi);
-  TAD_REQUIRE(!(k->v == &nt_variant && value == 6), "linear_tuning: variant=%d not one of 0..5, 7, 8, 9", value);
-  *k->v = (k->flags & KNOB_BOOL) ? value != 0 : value;
-  return TAD_OK;
+  TAD_REQUIRE(!(key && !strcmp(key, "variant") && value == 6), "linear_tuning: variant=%d not one of 0..5, 7, 8, 9", value);
+  return knob_set(KNOBS, "linear_tuning", key, value);
 }
 
-int tad_linear_tuning_get(const char* key, int* value) {
-  TAD_REQUIRE(key && value, "linear_tuning_get: null pointer");
-  const Knob* k = find_knob(key);
-  if (!k) { set_error("linear_tuning_get: unknown key '%s'", key); return TAD_EINVAL; }
-  *value = *k->v;
-  return TAD_OK;
-}
+int tad_linear_tuning_get(const char* key, int* value) { return knob_get(KNOBS, "linear_tuning_get", key, value); }
 
 long long tad_linear_kernel_launches(void) { return nt_launches; }
 

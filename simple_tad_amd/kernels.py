@@ -674,7 +674,7 @@ def attn_fwd(qkv, B: int, N: int, H: int, scale: float, out_dtype=None, want_lse
     """qkv [B*N, 3*H*d] bf16 or f16 (packed [B,N,3,H,d], d = 64 or 80) -> out [B*N, H*d], lse [B,H,N] f32.  want_lo: returns
     (out, lse, out_lo) with out_lo = what the 16-bit rounding of out dropped (for attn_bwd's delta).  q_prescaled: the q third already
     carries scale * log2(e) (linear_fwd_qkv's q_prescale = q_prescale_of(scale)).  rowscale [B] f32 | None: the per-clip drop-path scale
-    of the residual behind this attention (tad_attn_drop_scale): clips with scale 0 are filled (out = 0), not computed"""
+    of the residual behind this attention (tad_attn_fwd's clip_scale): clips with scale 0 are filled (out = 0), not computed"""
     op = _req16(qkv, "attn.qkv")
     out_dtype = _out16(out_dtype, op)
     if qkv.numel() != B * N * 3 * H * d:
@@ -682,27 +682,39 @@ def attn_fwd(qkv, B: int, N: int, H: int, scale: float, out_dtype=None, want_lse
     out = torch.empty((B * N, H * d), dtype=out_dtype, device=qkv.device)
     lse = torch.empty((B, H, N), dtype=torch.float32, device=qkv.device) if want_lse else None
     lo = torch.empty_like(out) if (want_lo and out.dtype in OP16_DTYPES) else None
+    _req_clip_scale(rowscale, B)
     with _timed("attn_fwd", 4.0 * B * H * N * N * d, 2.0 * (4 + (lo is not None)) * B * N * H * d):
-        _attn_drop_scale(rowscale, B, N)
-        check(_fn("tad_attn_fwd", op)(qkv.data_ptr(), out.data_ptr(), _dt(out), _p(lo), _p(lse), B, N, H, int(d), float(scale), int(bool(q_prescaled)),
-                                      float(drop_p), int(seed) & 0xffffffff, _stream()), "tad_attn_fwd")
+        check(_fn("tad_attn_fwd", op)(qkv.data_ptr(), out.data_ptr(), _dt(out), _p(lo), _p(lse), _p(rowscale), B, N, H, int(d), float(scale),
+                                      int(bool(q_prescaled)), float(drop_p), int(seed) & 0xffffffff, _stream()), "tad_attn_fwd")
     return (out, lse, lo) if want_lo else (out, lse)
 
 
-def _attn_drop_scale(rowscale, B: int, N: int):
-    """tad_attn_drop_scale for the attention call that follows on this thread"""
-    if rowscale is None:
-        return
-    _req(rowscale, torch.float32, "attn.rowscale")
-    if rowscale.numel() != B:
-        raise _lib.TadError(f"attn: rowscale has {rowscale.numel()} elements, expected one per clip ({B})")
-    check(_lib.load().tad_attn_drop_scale(rowscale.data_ptr(), N), "tad_attn_drop_scale")
+def _req_clip_scale(rowscale, B: int):
+    if rowscale is not None:
+        _req(rowscale, torch.float32, "attn.rowscale")
+        if rowscale.numel() != B:
+            raise _lib.TadError(f"attn: rowscale has {rowscale.numel()} elements, expected one per clip ({B})")
 
 
 def attn_tuning(**knobs):
     """Scheduling knobs of the attention kernels (include/tad_mi355x.h: tad_attn_tuning); timing only, never results."""
     for k, v in knobs.items():
         check(_lib.load().tad_attn_tuning(k.encode(), int(v)), f"tad_attn_tuning({k}={v})")
+
+
+def attn_tuning_get(key: str) -> int:
+    """current value of a tad_attn_tuning knob"""
+    v = C.c_int(0)
+    check(_lib.load().tad_attn_tuning_get(key.encode(), C.byref(v)), f"tad_attn_tuning_get({key})")
+    return int(v.value)
+
+
+def attn_plan(B: int, N: int, H: int, d: int = 64, backward=False, out_16bit=True, q_prescaled=False, drop_p: float = 0.0, rowscale=False, out_lo=False):
+    """The kernel launches attn_fwd (or, backward=True, attn_bwd: dQ then dK/dV) would make under the current knobs: a list of dicts with the keys
+    _lib.ATTN_PLAN_FIELDS (include/tad_mi355x.h: tad_attn_plan).  rowscale / out_lo (bool): the operand is given.  Launches nothing, needs no GPU."""
+    lib = _lib.load()
+    return _plan_rows(lambda buf, cap: lib.tad_attn_plan(int(bool(backward)), B, N, H, int(d), int(bool(out_16bit)), int(bool(q_prescaled)), float(drop_p),
+                                                         int(bool(rowscale)), int(bool(out_lo)), buf, cap), _lib.ATTN_PLAN_FIELDS, "tad_attn_plan")
 
 
 def attn_bwd(qkv, out, dout, lse, B: int, N: int, H: int, scale: float, out_lo=None, q_prescaled=False, drop_p: float = 0.0, seed: int = 0,
@@ -717,12 +729,12 @@ def attn_bwd(qkv, out, dout, lse, B: int, N: int, H: int, scale: float, out_lo=N
     _req(lse, torch.float32, "attn_bwd.lse")
     if qkv.numel() != B * N * 3 * H * d or lse.numel() != B * H * N:
         raise _lib.TadError("attn_bwd: qkv / lse element count mismatch")
+    _req_clip_scale(rowscale, B)
     dqkv = torch.empty_like(qkv)
     delta = torch.empty((_lib.load().tad_attn_bwd_scratch_bytes(B, N, H) // 4,), dtype=torch.float32, device=qkv.device)  # -rowsum(dout*out), -lse/scale
     with _timed("attn_bwd", 8.0 * B * H * N * N * d, 2.0 * (8 + (out_lo is not None)) * B * N * H * d):
-        _attn_drop_scale(rowscale, B, N)
-        check(_fn("tad_attn_bwd", op)(qkv.data_ptr(), out.data_ptr(), _p(out_lo), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), delta.data_ptr(),
-                                       B, N, H, int(d), float(scale), int(bool(q_prescaled)), float(drop_p), int(seed) & 0xffffffff, _stream()),
+        check(_fn("tad_attn_bwd", op)(qkv.data_ptr(), out.data_ptr(), _p(out_lo), dout.data_ptr(), lse.data_ptr(), _p(rowscale), dqkv.data_ptr(),
+                                       delta.data_ptr(), B, N, H, int(d), float(scale), int(bool(q_prescaled)), float(drop_p), int(seed) & 0xffffffff, _stream()),
               "tad_attn_bwd")
     return dqkv
 

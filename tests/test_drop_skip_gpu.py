@@ -1,5 +1,5 @@
-"""Stochastic depth: the attention kernels FILL the clips whose branch scale is 0 instead of computing them (tad_attn_drop_scale;
-csrc/attn_fwd.hip / attn_bwd.hip: SKIP).  The knob tad_attn_tuning("drop_skip", 0) computes every clip as before; every test here
+"""Stochastic depth: the attention kernels FILL the clips whose branch scale is 0 instead of computing them (the clip_scale argument of
+tad_attn_fwd / tad_attn_bwd; csrc/attn_fwd.hip / attn_bwd.hip: SKIP).  The knob tad_attn_tuning("drop_skip", 0) computes every clip as before; every test here
 compares the two BIT FOR BIT on what the training step consumes -- the fill is not allowed to change a single bit of the residual
 stream, of dqkv, or of any gradient.
 
@@ -39,9 +39,10 @@ def arena():
 
 @pytest.fixture
 def knob(K):
-    """knob(v): tad_attn_tuning(drop_skip=v); the default (1) is restored afterwards"""
+    """knob(v): tad_attn_tuning(drop_skip=v); the value found is restored afterwards"""
+    found = K.attn_tuning_get("drop_skip")
     yield lambda v: K.attn_tuning(drop_skip=v)
-    K.attn_tuning(drop_skip=1)
+    K.attn_tuning(drop_skip=found)
 
 
 def patterns(B):
@@ -78,6 +79,9 @@ def test_attention_fill_is_bit_identical_to_compute(K, knob, B, N, H, fmt):
         res = {}
         for on in (1, 0):
             knob(on)
+            # the records about to run: the fill kernels (SKIP) with the knob on, the general ones with it off
+            assert [r["skip"] for r in K.attn_plan(B, N, H, q_prescaled=True, rowscale=True, out_lo=True)] == [on]
+            assert [r["skip"] for r in K.attn_plan(B, N, H, q_prescaled=True, rowscale=True, out_lo=True, backward=True)] == [on, on]
             out, lse, lo = K.attn_fwd(qkv, B, N, H, scale, want_lo=True, q_prescaled=True, rowscale=rs)
             x1, _ = K.linear_fwd(out, wp, bp, out_dtype=torch.float32, epilogue=_lib.EPI_BIAS_RESIDUAL, residual=x0, rowscale=rs, rows_per_scale=N)
             dqkv = K.attn_bwd(qkv, out, d_ao, lse, B, N, H, scale, out_lo=lo, q_prescaled=True, rowscale=rs)

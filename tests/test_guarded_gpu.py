@@ -281,12 +281,13 @@ def test_attention_16bit(K, arena, B, N, H, d, prescaled, fmt, poison):
     kw = dict(q_prescaled=prescaled, d=d)
     out32, lse32 = guarded(K, arena, poison, lambda qkv: K.attn_fwd(qkv, B, N, H, scale, out_dtype=torch.float32, **kw), qkv=opnd.to(op))
     check(out32.reshape(B, N, -1), ref, tol=ATT_TOL, tol_max=ATT_TOL_MAX, what="attn fwd f32")
+    found = K.attn_tuning_get("fwd_q64")
     for q64 in ((0, 1) if d == 64 else (0,)):
         try:
             K.attn_tuning(fwd_q64=q64)
             out, lse, lo = guarded(K, arena, poison, lambda qkv: K.attn_fwd(qkv, B, N, H, scale, want_lo=True, **kw), qkv=opnd.to(op))
         finally:
-            K.attn_tuning(fwd_q64=0)
+            K.attn_tuning(fwd_q64=found)
         # (random inputs: the bound of tests/test_fuzz_gpu.py::test_attention_random_shapes for the 16-bit forward, 4e-3 + half an ulp, on both norms)
         check(out.float().reshape(B, N, -1), ref, tol=4e-3 + ULP16 / 2, what=f"attn fwd 16-bit (fwd_q64={q64})")
         assert same_bits(lse, lse32) and torch.equal(lo.float(), (out32 - out.float()).to(op).float()), "lse / out_lo"

@@ -24,6 +24,7 @@ BF16_ULP = 2.0 ** -8
 # tests/test_half_gpu.py, 6e-4).
 ATT_TOL = 2.5e-3
 ATT_TOL_MAX = 4.5e-3
+ATT_TOL_F16, ATT_TOL_MAX_F16 = 6e-4, 1.2e-3
 
 
 @pytest.fixture(scope="module")
@@ -314,13 +315,18 @@ def test_attention_fwd_q64_variant_is_bit_identical(K, B, N, H):
         qkv = bf(q4.reshape(B * N, -1))
     opnd, _ = prescaled_pair(qkv, B, N, H, scale, bf)
     qd = dev(opnd).to(torch.bfloat16)
+    from simple_tad_amd._lib import ATTN_FWD, ATTN_FWD_Q64
+    plan = lambda lo: K.attn_plan(B, N, H, q_prescaled=True, out_lo=lo)[0]  # noqa: E731
+    assert (plan(True)["kernel"], plan(True)["skip"]) == (ATTN_FWD, 0)
     ref = K.attn_fwd(qd, B, N, H, scale, want_lo=True, q_prescaled=True)
+    found = K.attn_tuning_get("fwd_q64")
     K.attn_tuning(fwd_q64=1)
     try:
+        assert [(plan(lo)["kernel"], plan(lo)["has_lo"], plan(lo)["block"]) for lo in (True, False)] == [(ATTN_FWD_Q64, 1, 128), (ATTN_FWD_Q64, 0, 128)]
         got = K.attn_fwd(qd, B, N, H, scale, want_lo=True, q_prescaled=True)
         got_nolo = K.attn_fwd(qd, B, N, H, scale, q_prescaled=True)
     finally:
-        K.attn_tuning(fwd_q64=0)
+        K.attn_tuning(fwd_q64=found)
     for a, b, nm in zip(ref, got, ("out", "lse", "out_lo")):
         assert torch.equal(a, b), nm
     assert torch.equal(got_nolo[0], ref[0]) and torch.equal(got_nolo[1], ref[1])
@@ -361,12 +367,17 @@ def test_attention_softmax_spike(K, prescaled):
 
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 @pytest.mark.parametrize("prescaled", [True, False], ids=["q_prescaled", "plain_q"])
-@pytest.mark.parametrize("B,N,H,p", [(2, 100, 2, 0.0), (1, 1568, 2, 0.0), (2, 8, 3, 0.0), (1, 129, 1, 0.0), (1, 393, 3, 0.0), (2, 200, 2, 0.25)])
+@pytest.mark.parametrize("B,N,H,p", [(2, 100, 2, 0.0), (1, 1568, 2, 0.0), (2, 8, 3, 0.0), (1, 129, 1, 0.0), (1, 393, 3, 0.0), (2, 200, 2, 0.25),
+                                     (2, 129, 2, 0.0), (2, 129, 2, 0.25)])
 def test_attention_head_dim_80_fwd_bwd(K, B, N, H, p, prescaled, fmt):
     """head_dim 80 (vit_huge: embed_dim 1280 / 16 heads, modeling_finetune.py:390-398) in the 16-bit MFMA attention kernels (round 4:
     dims 0..63 in the head_dim-64 LDS images, dims 64..79 in 32-byte-row side images, a fifth k-step and a third d tile): forward,
     lse and backward against the oracle, ragged N, both operand formats and q contracts, with and without attention dropout (the
-    oracle regenerates the keep mask).  Tolerances are those of the head_dim-64 tests."""
+    oracle regenerates the keep mask).  Tolerances are those of the head_dim-64 tests.  Every launch is first asserted (kernels.attn_plan) to be the
+    general record of the selector it is meant to be: together the cases visit each head_dim-80 record of the launchers' kernel tables
+    (output type x q contract x dropout, forward and backward, both formats), those at B=2, N=129, H=2 with one row in the second query
+    block, a clip boundary inside the grid and a head stride -- test_attention_every_general_kernel_of_the_selector does the same for head_dim 64."""
+    from simple_tad_amd._lib import ATTN_BWD_DKV, ATTN_BWD_DQ, ATTN_FWD
     d, seed = 80, 424242
     scale = d ** -0.5
     dt = torch.bfloat16 if fmt == "bf16" else torch.float16
@@ -380,19 +391,24 @@ def test_attention_head_dim_80_fwd_bwd(K, B, N, H, p, prescaled, fmt):
     ref = O.attention_core(qd, H, scale, drop_p=p, seed=seed) if p else O.attention_core(qd, H, scale)
     ref.backward(dout.double().reshape(B, N, -1))
     kw = dict(q_prescaled=prescaled, drop_p=p, seed=seed, d=d)
+    planned = dict(q_prescaled=prescaled, drop_p=p, d=d)
+    record = dict(hd=d, qs=int(prescaled), drop=int(p > 0), dma_mode=0, skip=0, has_lo=0, grid=-(-N // 128) * H * B, block=256)
     x = dev(opnd).to(dt)
+    assert K.attn_plan(B, N, H, out_16bit=False, **planned) == [dict(kernel=ATTN_FWD, out16=0, **record)]
     out32, lse = K.attn_fwd(x, B, N, H, scale, out_dtype=torch.float32, **kw)
     assert out32.shape == (B * N, H * d)
-    tol, tol_max = (ATT_TOL, ATT_TOL_MAX) if fmt == "bf16" else (6e-4, 1.2e-3)
+    tol, tol_max = (ATT_TOL, ATT_TOL_MAX) if fmt == "bf16" else (ATT_TOL_F16, ATT_TOL_MAX_F16)
     check(out32.reshape(B, N, -1), ref.detach(), tol=tol, tol_max=tol_max, what="attn80 fwd f32")
     q4 = qkv.double().reshape(B, N, 3, H, d)
     sc = torch.einsum("bnhd,bmhd->bhnm", q4[:, :, 0], q4[:, :, 1]) * scale
     assert (lse.cpu().double() - torch.logsumexp(sc, -1)).abs().max().item() < (1e-3 if N >= 64 else 2e-3)
+    assert K.attn_plan(B, N, H, out_16bit=True, out_lo=True, **planned) == [dict(kernel=ATTN_FWD, out16=1, **record)]
     out16, lse, lo = K.attn_fwd(x, B, N, H, scale, want_lo=True, **kw)
     ulp = BF16_ULP if fmt == "bf16" else 2 * tol
     check(out16.float().reshape(B, N, -1), ref.detach(), tol=ulp, what="attn80 fwd 16-bit")
     # out_lo is exactly what the rounding dropped (bit-exact against the f32 output of the same kernel family)
     assert torch.equal(lo.float(), (out32 - out16.float()).to(dt).float())
+    assert K.attn_plan(B, N, H, backward=True, out_lo=True, **planned) == [dict(kernel=k, out16=1, **record) for k in (ATTN_BWD_DQ, ATTN_BWD_DKV)]
     dqkv = K.attn_bwd(x, out16, dev(dout).to(dt), lse, B, N, H, scale, out_lo=lo, **kw)
     g, r = dqkv.float().cpu().reshape(B, N, 3, H, d), qd.grad.reshape(B, N, 3, H, d)
     for i, nm in enumerate("qkv"):
@@ -966,7 +982,7 @@ def test_attention_dropout_16bit_kernels_vs_oracle_with_the_injected_mask(K, fmt
     kw = dict(q_prescaled=prescaled, drop_p=p, seed=seed)
     x = dev(opnd).to(dt)
     out32, lse = K.attn_fwd(x, B, N, H, scale, out_dtype=torch.float32, **kw)
-    tol, tol_max = (ATT_TOL, ATT_TOL_MAX) if fmt == "bf16" else (6e-4, 1.2e-3)
+    tol, tol_max = (ATT_TOL, ATT_TOL_MAX) if fmt == "bf16" else (ATT_TOL_F16, ATT_TOL_MAX_F16)
     check(out32.reshape(B, N, -1), ref, tol=tol, tol_max=tol_max, what="attn dropout fwd")
     q4 = qkv.double().reshape(B, N, 3, H, 64)
     sc = torch.einsum("bnhd,bmhd->bhnm", q4[:, :, 0], q4[:, :, 1]) * scale
@@ -981,6 +997,55 @@ def test_attention_dropout_16bit_kernels_vs_oracle_with_the_injected_mask(K, fmt
     out2, _ = K.attn_fwd(x, B, N, H, scale, out_dtype=torch.float32, q_prescaled=prescaled, drop_p=p, seed=seed + 1)
     assert not torch.equal(out32, out0) and not torch.equal(out32, out2)
     check(out0.reshape(B, N, -1), O.attention_core(qkv.double().reshape(B, N, -1), H, scale), tol=tol, tol_max=tol_max, what="attn p=0")
+
+
+@pytest.mark.parametrize("fmt", ["bf16", "f16"])
+@pytest.mark.parametrize("p", [0.0, 0.25], ids=["no_dropout", "dropout"])
+@pytest.mark.parametrize("prescaled", [True, False], ids=["q_prescaled", "plain_q"])
+def test_attention_every_general_kernel_of_the_selector(K, prescaled, p, fmt):
+    """The launchers look their kernel up in a table indexed by the fields of the selector's record (csrc/attn_plan.h): a table wired with two
+    fields swapped still passes tests that only visit the production contract.  So every general head_dim-64 record -- forward: output type x q
+    contract x dropout, backward: q contract x dropout, both formats -- is planned, asserted to be the record it is meant to be, run once at a
+    shape with one row in the second query block, a clip boundary inside the grid and a head stride, and compared with the fp64 oracle (which
+    regenerates the keep mask).  The head_dim-80 records are visited the same way, at the same shape, by the cases of
+    test_attention_head_dim_80_fwd_bwd, which already ran every one of them.  Tolerances: those of the attention tests above."""
+    from simple_tad_amd._lib import ATTN_BWD_DKV, ATTN_BWD_DQ, ATTN_FWD
+    B, N, H, d, seed = 2, 129, 2, 64, 97531
+    scale = d ** -0.5
+    dt = torch.bfloat16 if fmt == "bf16" else torch.float16
+    rnd = lambda t: t.to(dt).float()  # noqa: E731
+    qkv = rnd(R.tensor_for(f"attsel.qkv{d}", (B * N, 3 * H * d), scale=1.0))
+    dout = rnd(R.tensor_for(f"attsel.do{d}", (B * N, H * d)))
+    opnd = qkv
+    if prescaled:
+        opnd, qkv = prescaled_pair(qkv, B, N, H, scale, rnd, d=d)
+    qd = qkv.double().reshape(B, N, -1).requires_grad_()
+    ref = O.attention_core(qd, H, scale, drop_p=p, seed=seed) if p else O.attention_core(qd, H, scale)
+    ref.backward(dout.double().reshape(B, N, -1))
+    kw = dict(q_prescaled=prescaled, drop_p=p, d=d)
+    record = dict(hd=d, qs=int(prescaled), drop=int(p > 0), dma_mode=0, skip=0, has_lo=0, grid=2 * H * B, block=256)
+    x = dev(opnd).to(dt)
+    tol, tol_max = (ATT_TOL, ATT_TOL_MAX) if fmt == "bf16" else (ATT_TOL_F16, ATT_TOL_MAX_F16)
+    ulp = BF16_ULP if fmt == "bf16" else 2 * tol
+
+    def held(a, b, what, **bound):  # every figure is printed before it is asserted
+        print(f"{what}: max-rel {relmax(a, b):.3e} l2-rel {rell2(a, b):.3e} (bound {bound})")
+        check(a, b, what=what, **bound)
+    assert K.attn_plan(B, N, H, out_16bit=False, **kw) == [dict(kernel=ATTN_FWD, out16=0, **record)]
+    out32, lse = K.attn_fwd(x, B, N, H, scale, out_dtype=torch.float32, seed=seed, **kw)
+    held(out32.reshape(B, N, -1), ref.detach(), "fwd f32", tol=tol, tol_max=tol_max)
+    q4 = qkv.double().reshape(B, N, 3, H, d)
+    sc = torch.einsum("bnhd,bmhd->bhnm", q4[:, :, 0], q4[:, :, 1]) * scale
+    assert (lse.cpu().double() - torch.logsumexp(sc, -1)).abs().max().item() < 1e-3
+    assert K.attn_plan(B, N, H, out_16bit=True, out_lo=True, **kw) == [dict(kernel=ATTN_FWD, out16=1, **record)]
+    out16, lse16, lo = K.attn_fwd(x, B, N, H, scale, want_lo=True, seed=seed, **kw)
+    held(out16.float().reshape(B, N, -1), ref.detach(), "fwd 16-bit", tol=ulp)
+    assert torch.equal(lse16, lse) and torch.equal(lo.float(), (out32 - out16.float()).to(dt).float())
+    assert K.attn_plan(B, N, H, backward=True, out_lo=True, **kw) == [dict(kernel=k, out16=1, **record) for k in (ATTN_BWD_DQ, ATTN_BWD_DKV)]
+    dqkv = K.attn_bwd(x, out16, dev(dout).to(dt), lse, B, N, H, scale, out_lo=lo, seed=seed, **kw)
+    g, r = dqkv.float().cpu().reshape(B, N, 3, H, d), qd.grad.reshape(B, N, 3, H, d)
+    for i, nm in enumerate("qkv"):
+        held(g[:, :, i], r[:, :, i], f"d{nm}", tol=2 * ulp)
 
 
 def test_attention_dropout_in_the_model_is_reproducible_and_off_in_eval():

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Interleaved A/B of the attention entry points of several builds of the library in ONE process (cdna_hip_programming.md rule 24):
-    python tools/ab_attn.py name=path[:abi3] ...  [--rounds 7] [--iters 10]
+    python tools/ab_attn.py name=path[:abi3|:abi4] ...  [--rounds 7] [--iters 10]
 Every library is loaded by path with ctypes (RTLD_LOCAL), so equally named symbols do not meet.  `:abi3` marks a round-3 library
-(tad_attn_fwd / tad_attn_bwd without the q_prescaled argument; it gets the plain qkv).  Random data, ViT-B shapes (B 32, H 12, N 1568)."""
+(tad_attn_fwd / tad_attn_bwd without the q_prescaled argument; it gets the plain qkv), `:abi4` one from before the clip_scale argument
+(ABI 5; the runs here pass a null scale).  Random data, ViT-B shapes (B 32, H 12, N 1568)."""
 import argparse
 import ctypes as C
 import statistics
@@ -40,8 +41,8 @@ vp, i, f = C.c_void_p, C.c_int, C.c_float
 
 def bind(spec):
     name, path = spec.split("=", 1)
-    abi3 = path.endswith(":abi3")
-    path = path[:-5] if abi3 else path
+    abi3, abi4 = path.endswith(":abi3"), path.endswith(":abi4")
+    path = path[:-5] if abi3 or abi4 else path
     lib = C.CDLL(path)
     if abi3:
         lib.tad_attn_fwd.argtypes = [vp, vp, i, vp, vp, i, i, i, i, f, vp]
@@ -50,10 +51,11 @@ def bind(spec):
         bwd = lambda: lib.tad_attn_bwd(qkv.data_ptr(), out.data_ptr(), lo.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(),  # noqa: E731
                                        delta.data_ptr(), B, N, H, 64, 0.125, st)
     else:
-        lib.tad_attn_fwd.argtypes = [vp, vp, i, vp, vp, i, i, i, i, f, i, f, C.c_uint32, vp]
-        lib.tad_attn_bwd.argtypes = [vp] * 7 + [i, i, i, i, f, i, f, C.c_uint32, vp]
-        fwd = lambda: lib.tad_attn_fwd(qkv_p.data_ptr(), out.data_ptr(), 1, lo.data_ptr(), lse.data_ptr(), B, N, H, 64, 0.125, 1, 0.0, 0, st)  # noqa: E731
-        bwd = lambda: lib.tad_attn_bwd(qkv_p.data_ptr(), out.data_ptr(), lo.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(),  # noqa: E731
+        clip = () if abi4 else (None,)  # ABI 5: the nullable clip_scale behind lse
+        lib.tad_attn_fwd.argtypes = [vp, vp, i, vp, vp] + [vp] * len(clip) + [i, i, i, i, f, i, f, C.c_uint32, vp]
+        lib.tad_attn_bwd.argtypes = [vp] * (7 + len(clip)) + [i, i, i, i, f, i, f, C.c_uint32, vp]
+        fwd = lambda: lib.tad_attn_fwd(qkv_p.data_ptr(), out.data_ptr(), 1, lo.data_ptr(), lse.data_ptr(), *clip, B, N, H, 64, 0.125, 1, 0.0, 0, st)  # noqa: E731
+        bwd = lambda: lib.tad_attn_bwd(qkv_p.data_ptr(), out.data_ptr(), lo.data_ptr(), dout.data_ptr(), lse.data_ptr(), *clip, dqkv.data_ptr(),  # noqa: E731
                                        delta.data_ptr(), B, N, H, 64, 0.125, 1, 0.0, 0, st)
     return name, fwd, bwd
 
