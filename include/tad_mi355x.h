@@ -538,6 +538,47 @@ int tad_multiscale_crop_plan_check(const int32_t* table_host, int64_t n_words, i
 int tad_multiscale_crop(const uint8_t* x, void* out, int out_f32, const float* mean, const float* std_, const void* workspace,
                         size_t workspace_bytes, int B, int T, int Hs, int Ws, int S_h, int S_w, int n_hsets, int n_vsets, tad_stream_t stream);
 
+/* The spatial sampling of the class fine-tuning recipe on the device (kinetics.py / ssv2.py of the reference: spatial_sampling, i.e.
+ * video_transforms.random_resized_crop, random_resized_crop_with_shift, or random_short_side_scale_jitter + random_crop, then
+ * horizontal_flip; with spatial_idx 0 / 1 / 2 the jitter + uniform_crop).  Every route is: a window of the source frame, a bilinear
+ * resize of the window (torch.nn.functional.interpolate, mode="bilinear", align_corners=False, no antialiasing) to a grid, an S x S
+ * window of that grid, an optional horizontal flip.  x is the f32 clips [B,3,T,H,W] or the uint8 frames [B,T,H,W,3]; out is the f32
+ * clips [B,3,T,S,S]; all clips of a call share one source size.
+ * table: int32 [B * T][TAD_SS_ROW_WORDS], one row per (clip, frame), every frame exactly once:
+ *   {sample, i, j, h, w, rh, rw, oy, ox, flip, scale_y, scale_x}
+ *   sample   clip * T + frame
+ *   i, j     origin (row, column) of the source window; h, w its extent: x[clip][.., frame, i:i+h, j:j+w]
+ *   rh, rw   the grid the window is resized to
+ *   oy, ox   origin of the S x S output inside that grid: output (y, x) is grid (oy + y, ox + x)
+ *   flip     1: output column x holds column S - 1 - x of the unflipped result
+ *   scale_y, scale_x   f32 bit patterns of (float)h / (float)rh and (float)w / (float)rw, stated by the host (the device never divides
+ *            for a coordinate)
+ *   Crop + resize to S x S: window = the box, grid = S x S, offset 0.  Resize of the whole frame + crop: window = the frame, grid = the
+ *   resized frame, offset = the crop's.
+ * Arithmetic on the device -- the contract: per axis, in f32, every product, sum and difference rounded on its own (no contraction),
+ *   with d the index in the resized grid and n_in the window's extent along the axis:
+ *     src = max(scale * (d + 0.5f) - 0.5f, 0)
+ *     i0  = min((int)src, n_in - 1);   i1 = min(i0 + 1, n_in - 1)
+ *     l1  = src - (float)i0;           l0 = 1 - l1
+ *   value = l0y * (l0x * a + l1x * b) + l1y * (l0x * c + l1x * d), evaluated in that order, with a = (i0y, i0x), b = (i0y, i1x),
+ *   c = (i1y, i0x), d = (i1y, i1x) of the window.  From uint8 frames each of the four taps first becomes
+ *   ((float)byte / 255 - mean[c]) / std_[c], tad_frames_to_clip's value: the result has the bits of the f32 route on
+ *   tad_frames_to_clip(x).
+ * tad_spatial_sample_workspace_bytes: the size of the table = of the workspace, which holds nothing else and is only read.
+ * tad_spatial_sample_plan_check: host-side check of a HOST copy of the table (n_words = its length, which must be B * T *
+ *   TAD_SS_ROW_WORDS; 0 <= sample < B * T exactly once; source windows inside the H x W source; output windows inside the resized
+ *   grid; flip 0 or 1; scales positive and finite); no launch.
+ * tad_spatial_sample: ONE launch, no host synchronisation; x is only read.  x_u8 == 0: x = f32 clips, mean / std_ are ignored;
+ *   x_u8 != 0: x = uint8 frames (any alignment), mean / std_: 3 host floats.  out: 4-byte aligned (16-byte stores are used where the
+ *   address allows them).  workspace = the table on the device.  On the device a source window is cut to the source, the tap indices
+ *   to the window whatever the scales and offsets hold, and a row whose sample is outside the batch is ignored (a malformed table is
+ *   never an address); a frame that no row names is left unwritten. */
+#define TAD_SS_ROW_WORDS 12
+size_t tad_spatial_sample_workspace_bytes(int B, int T);
+int tad_spatial_sample_plan_check(const int32_t* table_host, int64_t n_words, int B, int T, int H, int W, int S);
+int tad_spatial_sample(const void* x, int x_u8, float* out, const float* mean, const float* std_, const void* workspace,
+                       size_t workspace_bytes, int B, int T, int H, int W, int S, tad_stream_t stream);
+
 /* ---- MAE pre-training path: what modeling_pretrain.py / engine_for_pretraining.py add around the Block stack ----
  * Rows are D f32, D % 4 == 0.  idx arrays are int32 on the device. */
 /* out[r] = src[idx[r]], r < n_out: x[~mask].reshape(B,-1,C) (modeling_pretrain.py:98) with idx = b*N + visible token */

@@ -78,6 +78,9 @@ SIGNATURES = {
     "tad_multiscale_crop_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "tad_multiscale_crop_plan_check": (_i, [_vp, _i64, _i, _i, _i, _i, _i, _i, _i]),
     "tad_multiscale_crop": (_i, [_vp, _vp, _i, C.POINTER(_f), C.POINTER(_f), _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "tad_spatial_sample_workspace_bytes": (_sz, [_i, _i]),
+    "tad_spatial_sample_plan_check": (_i, [_vp, _i64, _i, _i, _i, _i, _i]),
+    "tad_spatial_sample": (_i, [_vp, _i, _vp, C.POINTER(_f), C.POINTER(_f), _vp, _sz, _i, _i, _i, _i, _i, _vp]),
     "tad_gather_rows_f32": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     "tad_scatter_rows_f32": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     "tad_mae_assemble": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -139,6 +142,7 @@ RANDAUG_MAX_LAYERS = 32
  RA_SHARPNESS, RA_AFFINE) = range(12)
 RA_STATS_OPS = (RA_AUTOCONTRAST, RA_EQUALIZE, RA_CONTRAST)
 MSC_ROW_WORDS, MSC_SET_HEAD, MSC_MAX_KSIZE, MSC_MAX_SETS = 8, 4, 17, 64
+SS_ROW_WORDS = 12
 POOL_SPLIT = 8
 
 _lib = None

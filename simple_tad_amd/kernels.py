@@ -1063,6 +1063,70 @@ def multiscale_crop(x, table, n_hsets: int, n_vsets: int, S_h: int, S_w: int, me
     return out
 
 
+# ----------------------------------------------------------------------------- fine-tune spatial sampling: window, bilinear resize, crop, flip
+def spatial_sample_table(rows, B: int, T: int, H: int, W: int, S: int):
+    """Host-side table of spatial_sample (include/tad_mi355x.h): ``rows`` = one (sample, i, j, h, w, rh, rw, oy, ox, flip) per (clip,
+    frame), sample = clip * T + frame.  The axis scales are stated here, as f32 quotients ``float32(h) / float32(rh)`` and
+    ``float32(w) / float32(rw)``.  Returns the int32 CPU tensor [B * T, SS_ROW_WORDS], checked by tad_spatial_sample_plan_check (word
+    count, every frame once, windows inside the source and inside the resized grid, positive finite scales); runs without a GPU."""
+    import numpy as np
+    n = B * T
+    if len(rows) != n:
+        raise _lib.TadError(f"spatial_sample_table: {len(rows)} rows for {B} clips of {T} frames")
+    tab = np.zeros((n, _lib.SS_ROW_WORDS), dtype=np.int32)
+    if n:
+        r = np.asarray(rows, dtype=np.int64).reshape(n, 10)
+        if (np.abs(r) >= 2 ** 31).any():
+            raise _lib.TadError("spatial_sample_table: a row does not fit 32 bits")
+        tab[:, :10] = r
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tab[:, 10] = (r[:, 3].astype(np.float32) / r[:, 5].astype(np.float32)).view(np.int32)
+            tab[:, 11] = (r[:, 4].astype(np.float32) / r[:, 6].astype(np.float32)).view(np.int32)
+    check(_lib.load().tad_spatial_sample_plan_check(tab.ctypes.data, tab.size, B, T, H, W, S), "tad_spatial_sample_plan_check")
+    return torch.from_numpy(tab)
+
+
+def spatial_sample(x, table, S: int, mean=None, std=None, out=None):
+    """Carry the device table ``table`` (a copy of spatial_sample_table()'s: the call's workspace, only read) out on the contiguous f32
+    clips x [B,3,T,H,W] or, with ``mean`` / ``std``, on the contiguous uint8 frames x [B,T,H,W,3] (tad_spatial_sample, ONE launch).
+    Returns the f32 clips [B,3,T,S,S]; from uint8 frames they have the bits of the f32 route on frames_to_clip(x).  x is only read."""
+    if (mean is None) != (std is None):
+        raise _lib.TadError("spatial_sample: mean and std come together")
+    u8 = isinstance(x, torch.Tensor) and x.dtype == torch.uint8
+    if u8:
+        _req_frames(x, "spatial_sample.x")
+        if mean is None:
+            raise _lib.TadError("spatial_sample: uint8 frames need mean and std")
+        B, T, H, W, _ = x.shape
+    else:
+        _req(x, torch.float32, "spatial_sample.x")
+        if x.dim() != 5 or x.shape[1] != 3 or x.numel() == 0:
+            raise _lib.TadError(f"spatial_sample.x: expected f32 clips [B,3,T,H,W] or uint8 frames [B,T,H,W,3], got {tuple(x.shape)}")
+        if mean is not None:
+            raise _lib.TadError("spatial_sample: f32 clips are normalised already; mean and std go with uint8 frames")
+        B, _, T, H, W = x.shape
+    _req(table, torch.int32, "spatial_sample.table")
+    lib = _lib.load()
+    nbytes = lib.tad_spatial_sample_workspace_bytes(B, T)
+    if tuple(table.shape) != (B * T, _lib.SS_ROW_WORDS) or nbytes == 0 or table.device != x.device:
+        raise _lib.TadError(f"spatial_sample.table: expected the device copy of spatial_sample_table() for {B} clips of {T} frames, "
+                            f"got {tuple(table.shape)} on {table.device}")
+    shape = (B, 3, T, S, S)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        _req(out, torch.float32, "spatial_sample.out")
+        if tuple(out.shape) != shape or out.device != x.device:
+            raise _lib.TadError(f"spatial_sample.out: expected {shape} on {x.device}, got {tuple(out.shape)} on {out.device}")
+    m = s = None
+    if u8:
+        m, s = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    with _timed("spatial_sample", 0.0, float(x.numel() * x.element_size() + out.numel() * 4)):
+        check(lib.tad_spatial_sample(x.data_ptr(), int(u8), out.data_ptr(), m, s, table.data_ptr(), nbytes, B, T, H, W, S, _stream()),
+              "tad_spatial_sample")
+    return out
+
+
 def soft_target_ce(logits, target=None, labels=None, smoothing: float = 0.0):
     """(loss [1], dlogits [B,classes]) of the batch-mean soft-target cross entropy over f32 logits, ONE launch (tad_soft_target_ce):
     ``target`` f32 [B,classes], or int64 ``labels`` [B] smoothed on the fly."""

@@ -17,7 +17,8 @@ stream: ``random.choice(pairs)`` over the (w, h) crop sizes, then ``random.choic
 crops', so drawing the batch's crops first and its masks second consumes both as the reference's per-sample calls do).
 
 Not built: a crop that shrinks an axis by more than 8 (Pillow's kernel grows past 17 taps; ``TadError``), the cv2 ``INTER_CUBIC``
-loader resize and ``pad_wide_clips`` of the fine-tune datasets.
+loader resize and ``pad_wide_clips`` of the fine-tune datasets.  (The fine-tune recipe's ``spatial_sampling`` -- random resized crop,
+scale jitter + crop, flip, the three test-time crops -- is ``spatial_sampling.SpatialSampling``.)
 """
 from __future__ import annotations
 
