@@ -344,6 +344,34 @@ int tad_sumsq_f32(const float* x, int64_t n, float* out, void* ws, size_t ws_byt
 int tad_grad_norm_coef(const float* x, int64_t n, float inv_scale, float max_norm, float* out3, void* ws, size_t ws_bytes,
                        tad_stream_t stream);
 
+/* Per-head gradient-norm diagnostics (utils.collect_grad_norms / collect_grad_norms_pretrain, utils.py:813-1011): the L2 norm of every
+ * segment of the flat f32 gradient buffer, one segment per slot of the result tables, in two launches (reduce, finish) and without a
+ * host synchronisation; the results accumulate on the device.
+ *   table  nseg rows {offset, length, slot, first_work}: grad[offset, offset + length) belongs to `slot`; its work items are
+ *          work[first_work .. first_work of the next row) (.. nwork for the last row)
+ *   work   nwork rows {offset, length}: every segment cut, in order, into items of at most TAD_SEGNORM_WORK_MAX floats
+ *   coef   device pointer to one f32, or NULL = 1.0 (tad_grad_norm_coef's out3 + 1: the unscale-and-clip coefficient)
+ *   acc [nslots] f64, last [nslots] f32, counters int32 {steps_added, steps_skipped, nonfinite_values}
+ * For every slot with a segment: last[slot] = coef * sqrt(sum x^2), acc[slot] += (double)last[slot], steps_added + 1.  *coef == 0 (the
+ * loss scaler skipped the step on the device): every such last[slot] = 0, nothing is added, steps_skipped + 1.  A value that is inf or
+ * NaN although *coef != 0 adds 0, leaves last[slot] = 0 and counts in nonfinite_values (the reference's nan_to_num keeps NaN -> 0; its
+ * inf -> 1.8e308 is not reproduced).  A slot without a segment is never written.  Bit-identical from run to run: fixed summation order,
+ * no floating-point atomics; 17 f32 additions at most between an element's square and the sum (csrc/grad_segnorm.hip, "depth").
+ * ws: tad_grad_segnorm_workspace_bytes(nwork); a smaller one is refused.
+ * tad_grad_segnorm_plan_check: host-side check of HOST copies of the two tables against a buffer of n floats (no GPU needed): every
+ * segment inside [0, n), lengths > 0, slots in [0, nslots), at most one segment per slot, the work items tile every segment exactly
+ * once and in order, none longer than the maximum, first_work consistent.  The device copies are not re-checked per call; the kernels
+ * skip an item or slot that is out of range instead of following it. */
+#define TAD_SEGNORM_WORK_MAX 16384
+typedef struct { int64_t offset, length; int32_t slot, first_work; } tad_segnorm_seg;
+typedef struct { int64_t offset, length; } tad_segnorm_work;
+size_t tad_grad_segnorm_workspace_bytes(int nwork);
+int tad_grad_segnorm_plan_check(const tad_segnorm_seg* table_host, int nseg, const tad_segnorm_work* work_host, int nwork, int64_t n,
+                                int nslots);
+int tad_grad_segnorm(const float* grad, int64_t n, const tad_segnorm_seg* table, int nseg, const tad_segnorm_work* work, int nwork,
+                     const float* coef, double* acc, float* last, int32_t* counters, int nslots, void* ws, size_t ws_bytes,
+                     tad_stream_t stream);
+
 /* Batched bf16 transpose: every [R,C] matrix of a flat buffer -> [C,R] at the same offset of a second flat buffer, one launch (the
  * transposed operand copies W^T that the input-gradient GEMMs of all Linear layers read; refreshed once per optimizer step).
  * table (device, int32 [n_tiles][8]): per 64x64 tile {src offset, dst offset, C, R, valid rows, valid cols, 0, 0} in elements,

@@ -60,6 +60,9 @@ SIGNATURES = {
     "tad_sumsq_workspace_bytes": (_sz, []),
     "tad_sumsq_f32": (_i, [_vp, _i64, _vp, _vp, _sz, _vp]),
     "tad_grad_norm_coef": (_i, [_vp, _i64, _f, _f, _vp, _vp, _sz, _vp]),
+    "tad_grad_segnorm_workspace_bytes": (_sz, [_i]),
+    "tad_grad_segnorm_plan_check": (_i, [_vp, _i, _vp, _i, _i64, _i]),
+    "tad_grad_segnorm": (_i, [_vp, _i64, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "tad_transpose_bf16_batched": (_i, [_vp, _vp, _vp, _i, _vp]),
     "tad_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(_f), C.POINTER(_f), _i, C.POINTER(C.c_int32), _f, _f, _f, _vp, _vp,
                        _vp]),
@@ -143,6 +146,8 @@ RANDAUG_MAX_LAYERS = 32
 RA_STATS_OPS = (RA_AUTOCONTRAST, RA_EQUALIZE, RA_CONTRAST)
 MSC_ROW_WORDS, MSC_SET_HEAD, MSC_MAX_KSIZE, MSC_MAX_SETS = 8, 4, 17, 64
 SS_ROW_WORDS = 12
+SEGNORM_WORK_MAX = 16384  # TAD_SEGNORM_WORK_MAX: the longest work item of tad_grad_segnorm, in floats
+SEGNORM_DEPTH = 17  # the longest chain of f32 additions behind one element's square (csrc/grad_segnorm.hip, "depth")
 POOL_SPLIT = 8
 
 _lib = None

@@ -149,6 +149,9 @@ class NativeScalerWithGradNormCount:
         self.skipped_steps = 0
         self._pending = None  # (found-inf flag in pinned host memory, the event behind its copy, optimizer) of the last fused step, not yet read
         self._flag_host = None
+        # the device coefficient (f32 [1]: unscale and clip; 0 = skipped on the device) the last fused step multiplied into the gradients,
+        # None when it applied none -- what grad_norms.GradNormCollector.collect takes to see the gradients the reference sees
+        self.last_coef = None
 
     def _settle(self):
         """read the previous fused step's found-inf flag and bring the scale and, after a skipped step, the optimizer's step counts up
@@ -198,6 +201,7 @@ class NativeScalerWithGradNormCount:
             dp.finish()
         from .optim import FusedAdamW
         inv = 1.0 / self.scale if scaling else 1.0
+        self.last_coef = None
         if isinstance(optimizer, FusedAdamW):
             # the norm of utils.get_grad_norm_ comes out of the optimizer's own pass over the gradients; with clipping or loss scaling
             # the coefficient (1 / scale) * min(1, max_norm / (norm + 1e-6)) of GradScaler.unscale_ + clip_grad_norm_ stays on the device
@@ -219,6 +223,7 @@ class NativeScalerWithGradNormCount:
                 ev = torch.cuda.Event()
                 ev.record()
                 self._pending = (self._flag_host, ev, optimizer, scaling)
+                self.last_coef = nc[1:2]
                 optimizer.step(grad_scale=nc[1:2])
             else:
                 norm = optimizer.step(want_sumsq=True).sqrt()
@@ -325,7 +330,7 @@ def _loss_inputs(batch, targets, device, with_ttc, smoothed_labels_for_loss):
 def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable, optimizer, device, epoch: int, loss_scaler,
                     max_norm: float = 0, start_steps=0, lr_schedule_values=None, wd_schedule_values=None,
                     num_training_steps_per_epoch=None, update_freq=1, log=None, model_ema=None, with_ttc=False, smoothed_labels_for_loss=False,
-                    augment_fn=None, erase_fn=None, mixup_fn=None):
+                    grad_norms=None, augment_fn=None, erase_fn=None, mixup_fn=None):
     """engine_for_finetuning.train_one_epoch (engine_for_finetuning.py:24-140) without the DeepSpeed branches.
     ``with_ttc`` / ``smoothed_labels_for_loss`` are the two switches of engine_for_frame_finetuning.train_one_epoch (:49, :114-142), for
     the criteria of ``loss.build_criterion``: the loader's fourth item, ``extra_info = batch[3]``, is then a dict with ``"ttc"`` (time to
@@ -347,6 +352,10 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable, op
     the last micro-step of each ``update_freq`` group, as the reference does (:96-99) -- also after a step that the loss scaler
     skipped on the device, where the average then moves toward the unchanged weights.  The update is queued on the stream behind
     the optimizer step: no host sync.
+    ``grad_norms`` (a ``grad_norms.GradNormCollector`` over this model and optimizer) switches on the per-head gradient-norm diagnostics
+    of engine_for_frame_finetuning.train_one_epoch(get_grad_norms=True) (:76-83, 173-185, 232-251): one device-side collect after
+    every scaler call, no host sync per step, and ``stats["grad_norms"]`` = the epoch averages {"qkv", "proj", "patch_embed"} the
+    reference returns, read back once at the end.  Without a collector nothing changes: no launch, no key.
     The loader yields (samples [B,3,T,H,W], targets [B], *rest).  Returns the per-step meter lists of THIS rank plus
     ``stats["averaged"]`` = the cross-rank epoch averages the reference returns (``{k: meter.global_avg}``)."""
     model.train(True)
@@ -390,6 +399,13 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable, op
         loss = loss / update_freq
         last = (data_iter_step + 1) % update_freq == 0
         grad_norm = loss_scaler(loss, optimizer, clip_grad=max_norm if max_norm else None, parameters=params, update_grad=last)
+        if grad_norms is not None:
+            # What the reference sees in p.grad at this point (engine_for_frame_finetuning.py:170-174) differs by micro-step, and so does
+            # what is collected: after an update step its scaler has unscaled and clipped the gradients in place, so the norms carry the
+            # coefficient (here it stays on the device: the scaler's last_coef; 0 = the step was skipped there and nothing is added); on
+            # the micro-steps in between (update_freq > 1) it sees the raw, still loss-scaled partial sums, i.e. coefficient 1.  Both
+            # kinds of step enter the same average, as they do there.
+            grad_norms.collect(getattr(loss_scaler, "last_coef", None) if last else None)
         if last:
             zero()
             if model_ema is not None:
@@ -406,6 +422,8 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable, op
             log(epoch, data_iter_step, stats)
     # gather the stats from all processes (engine_for_finetuning.py:137-140): per-step lists stay per rank, "averaged" is global
     stats["averaged"] = synchronize_meters(stats, device, group=dp.pg if dp is not None else None, names=METER_NAMES)
+    if grad_norms is not None:
+        stats["grad_norms"] = grad_norms.result(len(data_loader))  # (the reference's divisor, :245-248; the one read-back of the epoch)
     return stats
 
 

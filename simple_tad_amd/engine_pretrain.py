@@ -1,8 +1,9 @@
 """Counterpart of ``engine_for_pretraining.train_one_epoch`` (engine_for_pretraining.py:16-152) for the MAE pre-training path
 (SURVEY 8f-2): per step -- lr / weight-decay assignment (:39-45), reconstruction target from the clip (:51-66, one HIP kernel on
 the masked tokens only), model forward, ``nn.MSELoss`` (:68-70, fused loss + gradient kernel), ``loss.item()``, scaler step with
-``clip_grad=max_norm`` (:79-81), synchronise.  Left out: the per-head gradient-norm diagnostics (:30-33, 82-89, 134-147), the
-``gc.collect()/empty_cache()`` per step (:36-37), tensorboard logging."""
+``clip_grad=max_norm`` (:79-81), the per-head gradient-norm diagnostics over the encoder (:30-33, 84-91, 134-147; one device-side
+collect per step, ``train_one_epoch_with_grad_norms``), synchronise.  Left out: the ``gc.collect()/empty_cache()`` per step (:36-37), tensorboard
+logging."""
 from __future__ import annotations
 
 import math
@@ -33,6 +34,26 @@ def train_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer, de
                     wd_schedule_values=None, tubelet_size: int = 2, log=None, augment_fn=None):
     """augment_fn: applied to ``batch[0]`` right after it has reached the device (uint8 frames [B,T,Hs,Ws,3] ->
     ``transforms.DataAugmentationForVideoMAE``); where it returns a pair, the second item replaces ``batch[1]``, the masks."""
+    return _train_one_epoch(model, data_loader, optimizer, device, epoch, loss_scaler, max_norm, patch_size, normlize_target, start_steps,
+                            lr_schedule_values, wd_schedule_values, tubelet_size, log, augment_fn, None)
+
+
+def train_one_epoch_with_grad_norms(model: torch.nn.Module, data_loader: Iterable, optimizer, device: torch.device, epoch: int, loss_scaler,
+                                    grad_norms, max_norm: float = 0, patch_size: int = 16, normlize_target: bool = True, start_steps=0,
+                                    lr_schedule_values=None, wd_schedule_values=None, tubelet_size: int = 2, log=None, augment_fn=None):
+    """``train_one_epoch`` with the per-head gradient-norm diagnostics of engine_for_pretraining.py:30-33, 84-91, 134-147 switched on.
+    ``grad_norms``: a ``grad_norms.GradNormCollector`` over this model (it collects over ``model.encoder``) and optimizer: one device-side
+    collect after every scaler call with the scaler's coefficient, no host sync per step; ``stats["grad_norms"]`` = the epoch
+    averages {"qkv", "proj", "patch_embed"}, read back once.  An entry point of its own, not a keyword of ``train_one_epoch`` as in
+    ``engine.train_one_epoch``: that function's parameter list is fixed (tests/test_multiscale_crop_cpu.py pins it name by name)."""
+    if grad_norms is None:
+        raise ValueError("train_one_epoch_with_grad_norms: no collector (grad_norms.GradNormCollector(model, optimizer))")
+    return _train_one_epoch(model, data_loader, optimizer, device, epoch, loss_scaler, max_norm, patch_size, normlize_target, start_steps,
+                            lr_schedule_values, wd_schedule_values, tubelet_size, log, augment_fn, grad_norms)
+
+
+def _train_one_epoch(model, data_loader, optimizer, device, epoch, loss_scaler, max_norm, patch_size, normlize_target, start_steps,
+                     lr_schedule_values, wd_schedule_values, tubelet_size, log, augment_fn, grad_norms):
     model.train()
     dp = model if isinstance(model, DataParallel) else None
     inner = dp.module if dp is not None else model
@@ -69,6 +90,9 @@ def train_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer, de
             sys.exit(1)
         zero()
         grad_norm = loss_scaler(loss, optimizer, clip_grad=max_norm if max_norm else None, parameters=params)
+        if grad_norms is not None:
+            # the reference collects right behind its scaler (:81-86), which has unscaled and clipped p.grad in place: the coefficient
+            grad_norms.collect(getattr(loss_scaler, "last_coef", None))
         if device.type == "cuda":
             torch.cuda.synchronize()
         stats["loss"].append(loss_value)
@@ -82,4 +106,6 @@ def train_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer, de
     # engine_for_pretraining.py:149-152: metric_logger.synchronize_between_processes() -> {k: meter.global_avg}
     from .engine import synchronize_meters
     stats["averaged"] = synchronize_meters(stats, device, group=dp.pg if dp is not None else None, names=names)
+    if grad_norms is not None:
+        stats["grad_norms"] = grad_norms.result(len(data_loader))
     return stats

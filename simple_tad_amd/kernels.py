@@ -780,6 +780,82 @@ def grad_norm_coef(x, inv_scale: float, max_norm: float = 0.0, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- per-head gradient norms: segmented sum of squares
+def _segnorm_dtypes():
+    import numpy as np
+    return (np.dtype([("offset", "<i8"), ("length", "<i8"), ("slot", "<i4"), ("first_work", "<i4")]),   # tad_segnorm_seg, 24 bytes
+            np.dtype([("offset", "<i8"), ("length", "<i8")]))                                           # tad_segnorm_work, 16 bytes
+
+
+def grad_segnorm_plan_check(table, work, n: int, nslots: int) -> None:
+    """tad_grad_segnorm_plan_check on HOST copies of the two tables (int64 CPU tensors [nseg,3] / [nwork,2]); runs without a GPU"""
+    for t, words, name in ((table, 3, "table"), (work, 2, "work")):
+        if t.device.type != "cpu" or t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != words or not t.is_contiguous():
+            raise _lib.TadError(f"grad_segnorm_plan_check.{name}: expected a contiguous int64 CPU tensor [rows,{words}], got "
+                                f"{t.dtype}{list(t.shape)} on {t.device}")
+    check(_lib.load().tad_grad_segnorm_plan_check(table.data_ptr(), table.shape[0], work.data_ptr(), work.shape[0], int(n), int(nslots)),
+          "tad_grad_segnorm_plan_check")
+
+
+def grad_segnorm_tables(segments, n: int, nslots: int):
+    """Host-side tables of grad_segnorm (include/tad_mi355x.h): ``segments`` = (offset, length, slot) triples over a flat buffer of
+    ``n`` floats.  Every segment is cut, in order, into work items of at most SEGNORM_WORK_MAX floats.  Returns the int64 CPU tensors
+    (table [nseg,3] = the 24-byte rows {offset, length, slot | first_work}, work [nwork,2]), checked by tad_grad_segnorm_plan_check.
+    Built once per model; nothing is built per step."""
+    import numpy as np
+    seg_t, work_t = _segnorm_dtypes()
+    segments = [(int(o), int(ln), int(s)) for o, ln, s in segments]
+    if not segments:
+        raise _lib.TadError("grad_segnorm_tables: no segments")
+    big = 2 ** 31
+    if any(not (-big <= s < big) for _, _, s in segments):
+        raise _lib.TadError("grad_segnorm_tables: a slot does not fit 32 bits")
+    mx = _lib.SEGNORM_WORK_MAX
+    tab = np.zeros(len(segments), dtype=seg_t)
+    items = []
+    for k, (o, ln, s) in enumerate(segments):
+        tab[k] = (o, ln, s, len(items))
+        items.extend((o + a, min(mx, ln - a)) for a in range(0, max(ln, 0), mx))
+        if len(items) >= big:
+            raise _lib.TadError("grad_segnorm_tables: too many work items")
+    wk = np.array(items, dtype=work_t) if items else np.zeros(0, dtype=work_t)
+    table = torch.from_numpy(tab.view(np.int64).reshape(len(segments), 3).copy())
+    work = torch.from_numpy(wk.view(np.int64).reshape(len(items), 2).copy())
+    grad_segnorm_plan_check(table, work, n, nslots)
+    return table, work
+
+
+def grad_segnorm(grad, table, work, acc, last, counters, coef=None):
+    """One collect (tad_grad_segnorm: a reduce and a finish launch, no host synchronisation): for every segment of the device tables
+    ``table`` / ``work`` (copies of grad_segnorm_tables()'s) ``last[slot] = coef * ||grad[segment]||`` and ``acc[slot] += last[slot]``;
+    ``coef`` = a device f32 tensor of one element or None (1.0).  ``counters`` int32 [3] = {steps_added, steps_skipped,
+    nonfinite_values}.  The tables are not re-checked here: grad_segnorm_tables() checked them when they were created."""
+    _req(grad, torch.float32, "grad_segnorm.grad")
+    _req(table, torch.int64, "grad_segnorm.table")
+    _req(work, torch.int64, "grad_segnorm.work")
+    _req(acc, torch.float64, "grad_segnorm.acc")
+    _req(last, torch.float32, "grad_segnorm.last")
+    _req(counters, torch.int32, "grad_segnorm.counters")
+    if table.dim() != 2 or table.shape[1] != 3 or work.dim() != 2 or work.shape[1] != 2 or table.shape[0] == 0:
+        raise _lib.TadError(f"grad_segnorm: expected the device copies of grad_segnorm_tables(), got {list(table.shape)} and {list(work.shape)}")
+    if acc.numel() != last.numel() or counters.numel() != 3:
+        raise _lib.TadError(f"grad_segnorm: acc [{acc.numel()}] and last [{last.numel()}] must have one entry per slot, counters [3]")
+    if coef is not None:
+        _req(coef, torch.float32, "grad_segnorm.coef")
+        if coef.numel() != 1:
+            raise _lib.TadError(f"grad_segnorm.coef: expected one f32 on the device, got {list(coef.shape)}")
+    if any(t.device != grad.device for t in (table, work, acc, last, counters) + (() if coef is None else (coef,))):
+        raise _lib.TadError("grad_segnorm: every operand must live on the gradient buffer's device")
+    lib = _lib.load()
+    nwork = work.shape[0]
+    ws = workspace(lib.tad_grad_segnorm_workspace_bytes(nwork), grad.device)
+    with _timed("grad_segnorm", 0.0, 4.0 * grad.numel()):
+        check(lib.tad_grad_segnorm(grad.data_ptr(), grad.numel(), table.data_ptr(), table.shape[0], work.data_ptr(), nwork, _p(coef),
+                                   acc.data_ptr(), last.data_ptr(), counters.data_ptr(), acc.numel(), ws.data_ptr(), ws.numel(), _stream()),
+              "tad_grad_segnorm")
+    return last
+
+
 def adamw_step(param, grad, exp_avg, exp_avg_sq, chunk_group, group_lr, group_wd, group_step, beta1, beta2, eps, param_bf16=None,
                grad_scale=None, sumsq_partials=None):
     """Fused AdamW over flat f32 buffers (tad_adamw_step); group_lr / group_wd / group_step are host sequences, one entry per
