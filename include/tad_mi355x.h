@@ -619,7 +619,8 @@ int tad_mae_assemble(const float* x_vis, const float* mask_token, const float* p
                      float* out, int B, int n_vis, int n_mask, int D, tad_stream_t stream);
 /* reconstruction target (engine_for_pretraining.py:51-66): videos [B,3,T,H,W] f32 (normalised clip) -> labels [B*n_mask,
  * tub*p*p*3] for the masked tokens: v = x*std + mean, patch layout 'b n (p0 p1 p2) c', and with normalize_target each
- * (patch, channel) is standardised over its pixels: (v - mean) / (sqrt(unbiased var) + 1e-6).  mean3 / std3: HOST arrays. */
+ * (patch, channel) is standardised over its pixels: (v - mean) / (sqrt(unbiased var) + 1e-6).  The mean is refined by the mean of
+ * the residuals, so a constant (patch, channel) gives exactly 0 (the fp64 value), not f32 rounding noise.  mean3 / std3: HOST arrays. */
 int tad_mae_target(const float* videos, const int32_t* mask_idx, float* labels, int B, int n_mask, int T, int H, int W, int tubelet,
                    int patch, const float* mean3, const float* std3, int normalize_target, tad_stream_t stream);
 /* nn.MSELoss() (engine_for_pretraining.py:27,70): partials[tad_mse_loss_blocks(n)] = block sums of (pred-target)^2 (the loss is

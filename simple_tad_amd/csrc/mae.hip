@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void mae_assemble_kernel(const float* __restri
 // Reconstruction target (engine_for_pretraining.py:51-66): un-normalise the clip, cut tubelet patches, and (normalize_target)
 // standardise each (patch, channel) over its tub*p*p pixels with the UNBIASED variance: (v - mean) / (sqrt(var) + 1e-6).
 // labels[b, j, pix*3 + c] for the j-th masked token of clip b, pix = (kt*p + kh)*p + kw  ('b n (p c)').
-// One workgroup per masked token; wave w < 3 owns channel w (two-pass statistics in registers, tub*p*p <= 64*NPIX pixels).
+// One workgroup per masked token; wave w < 3 owns channel w (two-pass statistics in registers with a refined mean, tub*p*p <= 64*NPIX pixels).
 template <int NPIX>
 __global__ __launch_bounds__(256) void mae_target_kernel(const float* __restrict__ x, const int32_t* __restrict__ mask_idx,
                                                          float* __restrict__ labels, int Nm, int T, int H, int W, int tub, int p,
@@ -85,13 +85,27 @@ __global__ __launch_bounds__(256) void mae_target_kernel(const float* __restrict
       sum += v[i];
     }
   }
-  float mu = 0.f, inv = 1.f;
+  float inv = 1.f;
   if (normalize) {
-    mu = wave_sum(sum) / (float)npix;
+    // The mean is kept as two floats, mu + corr: mu = sum / n carries a rounding error d of about an ulp of the pixel values, and
+    // on a low-contrast patch (two adjacent grey levels, one differing pixel) d / (sigma + 1e-6) is the whole error of the label
+    // (1e-3 at sigma = 4e-3 / sqrt(n)).  The residuals v - mu are exact or nearly so there, so their mean corr recovers d.
+    const float mu = wave_sum(sum) / (float)npix;
+    float rs = 0.f;
+#pragma unroll
+    for (int i = 0; i < NPIX; ++i)
+      if (lane + 64 * i < npix) {
+        v[i] -= mu;
+        rs += v[i];
+      }
+    const float corr = wave_sum(rs) / (float)npix;
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < NPIX; ++i)
-      if (lane + 64 * i < npix) sq += (v[i] - mu) * (v[i] - mu);
+      if (lane + 64 * i < npix) {
+        v[i] -= corr;
+        sq += v[i] * v[i];
+      }
     const float var = wave_sum(sq) / (float)(npix - 1);
     inv = 1.f / (sqrtf(var) + 1e-6f);
   }
@@ -99,7 +113,7 @@ __global__ __launch_bounds__(256) void mae_target_kernel(const float* __restrict
 #pragma unroll
   for (int i = 0; i < NPIX; ++i) {
     const int pix = lane + 64 * i;
-    if (pix < npix) out[pix * 3 + c] = normalize ? (v[i] - mu) * inv : v[i];
+    if (pix < npix) out[pix * 3 + c] = normalize ? v[i] * inv : v[i];
   }
 }
 

@@ -78,7 +78,14 @@ def _train_one_epoch(model, data_loader, optimizer, device, epoch, loss_scaler, 
             raise ValueError("train_one_epoch: no masks for this step: the batch holds one item and augment_fn "
                              + ("returned the clips alone" if augment_fn is not None else "is None")
                              + " (pass (clips, masks) batches, or an augment_fn that returns (clips, masks))")
-        num_masked = int(torch.as_tensor(bool_masked_pos)[0].sum())  # host-side count (the mask comes from the loader's generator)
+        # host-side counts (the mask comes from the loader's generator): one read of all clips' counts where clip 0's was read before
+        counts = torch.as_tensor(bool_masked_pos).flatten(1).to(torch.bool).sum(1).tolist()
+        num_masked = int(counts[0])
+        if any(c != num_masked for c in counts):
+            # token_indices splits every clip at clip 0's count: masked tokens of another clip would land among the visible ones
+            # (the reference's x[~mask].reshape(B, -1, C) usually raises here)
+            raise ValueError(f"train_one_epoch: the clips of this batch mask different numbers of tokens {counts}; "
+                             "every clip of a batch must mask the same number")
         bool_masked_pos = torch.as_tensor(bool_masked_pos).to(device, non_blocking=True).flatten(1).to(torch.bool)
         with torch.no_grad():
             labels = reconstruction_target(videos, bool_masked_pos, patch_size, tubelet_size, normlize_target, num_masked)

@@ -43,7 +43,12 @@ def _init_weights(m):
 def token_indices(mask: torch.Tensor, num_masked=None):
     """bool mask [B,N] (True = masked) -> (vis_tok [B,Nv], mask_tok [B,Nm]) int32 token indices in ascending order per clip --
     the order boolean indexing ``x[~mask]`` / ``x[mask]`` produces (modeling_pretrain.py:98, 285-286).  A stable argsort of the
-    mask does it without the device sync of ``nonzero``."""
+    mask does it without the device sync of ``nonzero``.
+
+    Contract of the caller: EVERY clip masks ``num_masked`` tokens (read from ``mask[0]`` when not given).  This is not checked
+    here (a check would be a device sync): a clip with another count is split at the wrong place without an error -- some of its
+    masked tokens end up among the visible ones or the other way round -- where the reference's ``x[~mask].reshape(B, -1, C)``
+    usually raises.  ``engine_pretrain`` checks the counts while the masks are still on the host."""
     if mask.dtype != torch.bool:
         mask = mask.to(torch.bool)
     B, N = mask.shape

@@ -689,25 +689,38 @@ class BlockFn(_Fn):
 
 # --------------------------------------------------------------------------- plain Linear (f32 rows in / out)
 class LinearFn(_Fn):
-    """nn.Linear on f32 rows through the bf16 MFMA GEMM (encoder_to_decoder and the decoder head, modeling_pretrain.py:163,269)."""
+    """nn.Linear on f32 rows through the 16-bit MFMA GEMM (encoder_to_decoder and the decoder head, modeling_pretrain.py:163,269);
+    in the precise mode through the split-bf16 GEMMs."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
         _need_gpu(x, "Linear")
         shp = x.shape
         train = _differentiated(ctx)
+        ctx.params = (weight, bias)
+        ctx.shp = shp
+        ctx.precise = _PRECISION == "precise"
+        if ctx.precise:  # split-bf16 operands on f32 rows, like every other Linear of the parity gate (PreciseBlockFn)
+            x2 = _f32c(x).reshape(-1, shp[-1])
+            y = precise_linear(x2, weight, bias, fresh=train)
+            if train:
+                ctx.save_for_backward(x2)
+            return y.reshape(*shp[:-1], -1)
         xb = K.cast_bf16(_f32c(x).reshape(-1, shp[-1]))
         y, _ = K.linear_fwd(xb, w_bf16(weight, train), _f32c(bias), out_dtype=torch.float32)
         if train:
             ctx.save_for_backward(xb)
-        ctx.params = (weight, bias)
-        ctx.shp = shp
         return y.reshape(*shp[:-1], -1)
 
     @staticmethod
     def backward(ctx, dy):
         (xb,) = ctx.saved_tensors
         weight, bias = ctx.params
+        if ctx.precise:
+            dy2 = _f32c(dy).reshape(-1, dy.shape[-1])
+            dx = precise_dx(dy2, weight) if ctx.needs_input_grad[0] else None
+            dW, db = precise_dw(dy2, xb, want_bias=bias is not None)
+            return (None if dx is None else dx.reshape(ctx.shp)), dW, db
         dyb = K.cast_bf16(_f32c(dy).reshape(-1, dy.shape[-1]))
         dx = K.linear_bwd_input(dyb, wT_bf16(weight, True), out_dtype=torch.float32) if ctx.needs_input_grad[0] else None
         dW, db = linear_dw(dyb, xb, weight, bias)

@@ -626,10 +626,15 @@ def test_adamw_step_flat_buffer(K, arena, skip, fmt, poison):
 
 
 # =============================================================================================== MAE, metrics
+# (R, D, n, mse sizes): the first case is the original one; D = 260 / 384 reach the second 64-lane pass of the row movers (D4 = 65: one
+# lane of it; 96: the real decoder width); 4 * (262144 + 1) is the first size at which mse_kernel's grid-stride loop makes a second trip
+GATHER_MSE = [(37, 52, 13, (4, 1004, 70012)), (37, 260, 13, ()), (37, 384, 13, (4 * (262144 + 1),))]
+
+
 @poison
-def test_gather_scatter_mse(K, arena, poison):
+@pytest.mark.parametrize("R,D,n,mse_sizes", GATHER_MSE, ids=["D52", "D260", "D384-stride2"])
+def test_gather_scatter_mse(K, arena, R, D, n, mse_sizes, poison):
     g = torch.Generator().manual_seed(8)
-    R, D, n = 37, 52, 13
     src = torch.randn(R, D, generator=g)
     idx = torch.randperm(R, generator=g)[:n].to(torch.int32)
     got = guarded(K, arena, poison, lambda src, idx: (K.gather_rows(src, idx),), src=src, idx=Idx(idx, R))[0]
@@ -639,7 +644,7 @@ def test_gather_scatter_mse(K, arena, poison):
     want = torch.zeros(R, D)
     want[idx.long()] = rows
     assert torch.equal(back, want)
-    for cnt in (4, 1004, 70012):  # (n % 4 == 0 is the ABI's rule)
+    for cnt in mse_sizes:  # (n % 4 == 0 is the ABI's rule)
         pred, tgt = torch.randn(cnt, generator=g), torch.randn(cnt, generator=g)
         # (partials.sum() / n runs in torch on the kernel's partials: compared through the loss)
         loss, grad = guarded(K, arena, poison, lambda pred, tgt: K.mse_loss(pred, tgt), pred=pred, tgt=tgt)
@@ -651,11 +656,17 @@ def test_gather_scatter_mse(K, arena, poison):
         assert abs(loss.item() - lr.item()) < 1e-6 * lr.item() and ((grad.cpu().double() - pr.grad).norm() / pr.grad.norm()).item() < 1e-6  # (test_mae_kernels_vs_oracle)
 
 
+# (D, tubelet, patch): the first case is the original one; D = 260 / 384: second lane pass of mae_assemble; (1, 8): 64 pixels, the NPIX = 4
+# instance of mae_target; (3, 16): 768 pixels, the NPIX = 16 instance, its last slots partly filled
+ASSEMBLE_TARGET = [(52, 2, 16), (260, 1, 8), (384, 3, 16)]
+
+
 @poison
-def test_mae_assemble_and_target(K, arena, poison):
+@pytest.mark.parametrize("D,tub,p", ASSEMBLE_TARGET, ids=["D52-2x16", "D260-1x8", "D384-3x16"])
+def test_mae_assemble_and_target(K, arena, D, tub, p, poison):
     """expressions and bounds of tests/test_pretrain.py::test_mae_kernels_vs_oracle; odd counts; the index tensors sit between in-range indices"""
     g = torch.Generator().manual_seed(12)
-    B, N, D, Nm = 3, 39, 52, 27
+    B, N, Nm = 3, 39, 27
     mask = torch.zeros(B, N, dtype=torch.bool)
     for b in range(B):
         mask[b, torch.randperm(N, generator=g)[:Nm]] = True
@@ -666,14 +677,14 @@ def test_mae_assemble_and_target(K, arena, poison):
                    xv=xv.reshape(-1, D), tok=tok, pos=pos, vis=Idx(vis.reshape(-1), N), msk=Idx(msk.reshape(-1), N))[0].cpu()
     pe = pos.expand(B, -1, -1)
     assert torch.equal(full, torch.cat([xv + pe[~mask].reshape(B, -1, D), tok + pe[mask].reshape(B, -1, D)], dim=1))
-    vids = torch.randn(3, 3, 4, 32, 48, generator=g)
+    vids = torch.randn(3, 3, 2 * tub, 2 * p, 3 * p, generator=g)
     m2 = torch.zeros(3, 2 * 2 * 3, dtype=torch.bool)
     m2[:, [1, 2, 5, 7, 8, 10, 11]] = True
     mt = torch.stack([m2[b].nonzero().flatten() for b in range(3)]).to(torch.int32)
     for norm in (True, False):
-        lab = guarded(K, arena, poison, lambda v, mt: (K.mae_target(v, mt, 2, 16, (0.485, 0.456, 0.406), (0.229, 0.224, 0.225), norm),),
+        lab = guarded(K, arena, poison, lambda v, mt: (K.mae_target(v, mt, tub, p, (0.485, 0.456, 0.406), (0.229, 0.224, 0.225), norm),),
                       v=vids, mt=Idx(mt.reshape(-1), 12))[0].cpu()
-        ref = O.mae_target(vids.double(), m2, tubelet=2, patch=16, normalize_target=norm)
+        ref = O.mae_target(vids.double(), m2, tubelet=tub, patch=p, normalize_target=norm)
         assert lab.shape == ref.shape and ((lab.double() - ref).norm() / ref.norm()).item() < 2e-6, norm
 
 

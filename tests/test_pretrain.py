@@ -74,6 +74,53 @@ def test_module_surface_and_factories():
         m(torch.zeros(1, 3, 16, 224, 224), torch.zeros(1, 1568, dtype=torch.bool))
 
 
+def test_token_indices_equal_nonzero_order_on_host():
+    """equal counts in every clip (the caller's contract): the stable argsort gives the ascending order of ``nonzero``, i.e. of the
+    boolean indexing x[~mask] / x[mask], with the count given or read from mask[0], for bool and for the loader's float masks"""
+    from simple_tad_amd.modeling_pretrain import token_indices
+    g = torch.Generator().manual_seed(3)
+    for B, N, Nm in ((1, 1, 1), (2, 8, 1), (3, 36, 27), (4, 40, 39), (2, 12, 12)):
+        mask = torch.zeros(B, N, dtype=torch.bool)
+        for b in range(B):
+            mask[b, torch.randperm(N, generator=g)[:Nm]] = True
+        for m, nm in ((mask, Nm), (mask, None), (mask.double(), None)):
+            vis, msk = token_indices(m, nm)
+            assert vis.dtype == msk.dtype == torch.int32 and vis.shape == (B, N - Nm) and msk.shape == (B, Nm)
+            assert torch.equal(vis.long(), torch.stack([(~mask[b]).nonzero().flatten() for b in range(B)]))
+            assert torch.equal(msk.long(), torch.stack([mask[b].nonzero().flatten() for b in range(B)]))
+
+
+def test_engine_refuses_unequal_mask_counts_before_any_kernel(monkeypatch):
+    """a batch whose clips mask 27 and 26 of 36 tokens: token_indices would split clip 1 at clip 0's count (one visible token among
+    the masked ones) without an error; the engine reads the counts from the host masks and raises, naming them, before the target
+    kernel, the model or the library is touched"""
+    from simple_tad_amd import _lib, engine_pretrain as EP
+
+    def touched(*a, **k):
+        raise AssertionError("a kernel path was reached")
+    monkeypatch.setattr(_lib, "load", touched)
+    monkeypatch.setattr(EP, "reconstruction_target", touched)
+
+    class Model(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.w = torch.nn.Parameter(torch.zeros(1))
+
+        def forward(self, *a, **k):
+            touched()
+    mask = torch.zeros(2, 36, dtype=torch.bool)
+    mask[0, :27] = True
+    mask[1, 9:35] = True
+    clips = torch.zeros(2, 3, 8, 48, 48)
+    for masks in (mask, mask.view(2, 4, 9), mask.double().numpy()):
+        with pytest.raises(ValueError, match=r"different numbers of tokens \[27, 26\]"):
+            EP.train_one_epoch(Model(), [(clips, masks)], None, torch.device("cpu"), 0, None)
+    # what would have happened: clip 1's "masked" tokens taken at clip 0's count include a visible one
+    from simple_tad_amd.modeling_pretrain import token_indices
+    _, msk = token_indices(mask)
+    assert not bool(mask[1, msk[1].long()].all())
+
+
 # ------------------------------------------------------------------------------------------------------------------ GPU
 @pytest.mark.gpu
 def test_mae_kernels_vs_oracle():
