@@ -95,6 +95,17 @@ int tad_patch_embed_fwd_implicit(const float* x, const uint16_t* w_bf16, const f
  * the stride tad_patch_embed_ldk(3, tubelet, patch) (= K for multiples of 8; /14: 1216, padding columns zeroed). */
 int tad_im2col_tubelets_u8(const uint8_t* frames, uint16_t* cols, int B, int T, int H, int W, int tubelet, int patch,
                            const float* mean3, const float* std3, int bgr, int t_offset, tad_stream_t stream);
+/* Patch matrix of B windows read from ONE frame store [F,H,W,3] uint8: frame t of window b is slot idx[b*T+t].
+ * Same arithmetic, row order, row stride (tad_patch_embed_ldk) and padding columns as tad_im2col_tubelets_u8
+ * on the clip store[idx] -- bit-identical to it.
+ * cols_dtype: TAD_BF16 or TAD_F16.  idx: DEVICE int32.  mean3/std3: HOST, RGB order.
+ * One entry point for both operand formats (the format is an argument: there is no _f16 twin).  store and idx must be 4-byte aligned,
+ * cols 16-byte aligned.  The index table is on the device, so this call cannot check it: the CALLER guarantees 0 <= idx < F.  As a
+ * defence the kernels clamp every slot into [0, F-1]: an index outside the store reads the first / last frame instead of memory outside
+ * the store -- a wrong result, never a wild address.  Do not rely on the clamp as padding. */
+int tad_im2col_frame_windows(const uint8_t* store, int64_t F, const int32_t* idx, void* cols, int cols_dtype,
+                             int B, int T, int H, int W, int tubelet, int patch,
+                             const float* mean3, const float* std3, int bgr, tad_stream_t stream);
 /* GEMM part of tad_patch_embed_fwd on an existing patch matrix: out = cols * w^T + bias (+ pos broadcast over the batch) */
 int tad_patch_embed_gemm(const uint16_t* cols, const uint16_t* w_bf16, const float* bias, const float* pos, float* out,
                          int64_t M, int ntok, int D, int K, tad_stream_t stream);

@@ -7,6 +7,9 @@ optimizer step, ``zero_grad``, device synchronise, meters.  Differences, by desi
 for IEEE-half operands (``set_precision("half")``, the reference's own autocast dtype); the bfloat16 kernels need
 none and the scaler then reports ``scale == 1.0``; the gradient all-reduce is the bucketed RCCL exchange of
 ``parallel.DataParallel``.
+
+Evaluation: ``validation_one_epoch`` and ``final_test`` (engine_for_frame_finetuning.py:282-383, 385-545; the latter writes the
+reference's ``predictions.csv`` and stats file).  Both take clip tensors or ``frame_store.FrameWindows`` as ``batch[0]``.
 """
 from __future__ import annotations
 
@@ -478,3 +481,105 @@ def validation_one_epoch(data_loader, model, device, criterion=None, with_ttc=Fa
           "logitsN_std": all_preds[:, 0].std().item(), "logitsN_median": all_preds[:, 0].median().item(),
           "probs_mean": values.mean().item(), "probs_std": values.std().item(), "probs_median": values.median().item()}
     return {"loss": float(np.mean(losses)), "acc": 100.0 * correct / max(seen, 1)}, my, {"confmat": confmat, "pr_curve": pr_curve, "roc_curve": roc_curve}
+
+
+# ----------------------------------------------------------------------------------------------------------------- final test
+PREDICTION_COLUMNS = ("clip", "filename", "logits_safe", "logits_risk", "label", "ttc")
+
+
+def merge_prediction_shards(name_shards, logits, labels, ttc):
+    """The table ``final_test`` writes, from what the ranks gathered: ``name_shards[r] = (clips, filenames)`` of rank r (what
+    ``all_gather_object`` returns, rank after rank) and ``logits`` [S,2] / ``labels`` [S] / ``ttc`` [S], the rank-ordered concatenations
+    ``gather_predictions`` returns.  Rows keep that order: rank 0's windows first.  Pure host code (tests/test_frame_store_cpu.py).
+    Returns {column: list or numpy array} with the columns of PREDICTION_COLUMNS."""
+    clips = [c for shard in name_shards for c in shard[0]]
+    files = [f for shard in name_shards for f in shard[1]]
+    for r, shard in enumerate(name_shards):
+        if len(shard[0]) != len(shard[1]):
+            raise ValueError(f"merge_prediction_shards: rank {r} sent {len(shard[0])} clip names but {len(shard[1])} file names")
+    logits = logits.detach().to(torch.float32).cpu().numpy()
+    labels = labels.detach().cpu().numpy().astype(int)
+    ttc = ttc.detach().cpu().numpy()
+    if logits.ndim != 2 or logits.shape[1] != 2 or not (len(clips) == logits.shape[0] == labels.shape[0] == ttc.shape[0]):
+        raise ValueError(f"merge_prediction_shards: {len(clips)} names, logits {logits.shape}, labels {labels.shape}, ttc {ttc.shape}")
+    return {"clip": clips, "filename": files, "logits_safe": logits[:, 0], "logits_risk": logits[:, 1], "label": labels, "ttc": ttc}
+
+
+def write_predictions_csv(path, table) -> None:
+    """``DataFrame(table).to_csv(path, index=True, header=True)`` with the csv module: an unnamed index column, then
+    PREDICTION_COLUMNS.  Floats are written with ``repr`` of their exact value, so that parsing a float32 logit returns that float32."""
+    import csv
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, lineterminator="\n")
+        w.writerow(("",) + PREDICTION_COLUMNS)
+        for i in range(len(table["clip"])):
+            w.writerow((i, table["clip"][i], table["filename"][i], repr(float(table["logits_safe"][i])), repr(float(table["logits_risk"][i])),
+                        int(table["label"][i]), repr(float(table["ttc"][i]))))
+
+
+@torch.no_grad()
+def final_test(data_loader, model, device, preds_file, stats_file, plot_dir=None, with_ttc=False, smoothed_labels_for_loss=False,
+               criterion=None):
+    """engine_for_frame_finetuning.final_test (:385-545): run the model over the test windows, write ``preds_file`` (a CSV with an index
+    column and clip, filename, logits_safe, logits_risk, label, ttc: the input of anaysis/metrics*.py) and ``stats_file`` (the five
+    lines mAP / auroc / acc, P / R / F1 at 0.5, confusion matrix, from ``metrics.calculate_metrics``), return the global averages
+    ``{"loss", "acc1"}`` (acc1 in percent, weighted by batch size; loss per batch, as the reference's meters count them).
+    A batch is ``(videos, target, ids, extra_info)``: ``videos`` a clip tensor or a ``frame_store.FrameWindows`` (``StoreViews.batches``),
+    ``extra_info`` a dict with ``ttc`` [B], ``clip`` and ``frame`` (B names each) and, for ``smoothed_labels_for_loss``, ``smoothed_labels``.
+    ``criterion`` (default CrossEntropyLoss, the reference's), ``with_ttc`` and ``smoothed_labels_for_loss`` as in validation_one_epoch.
+    Differences, by design: the plots are not built (``plot_dir`` is accepted and ignored with one warning); the reference reads
+    ``output`` before it is assigned when no process group exists (:414) -- the labels collected are the targets in every case.
+    With several ranks the tensors travel through ``gather_predictions``, the names through ``all_gather_object``; rank 0 writes."""
+    import torch.distributed as dist
+    from . import metrics as M
+    if plot_dir is not None:
+        import warnings
+        warnings.warn("final_test: the PR / ROC plots of the reference are not built; plot_dir is ignored")
+    if criterion is None:
+        criterion = torch.nn.CrossEntropyLoss()
+    model.eval()
+    clips, frame_names, preds, labels, ttcs = [], [], [], [], []
+    loss_sum, n_batches, correct, seen = 0.0, 0, 0, 0
+    for batch in data_loader:
+        videos = batch[0].to(device, non_blocking=True)
+        target = batch[1].to(device, non_blocking=True)
+        extra_info = batch[3]
+        clips.extend(extra_info["clip"])
+        frame_names.extend(extra_info["frame"])
+        labels.append(target.detach())
+        ttcs.append(torch.as_tensor(extra_info["ttc"]).clone().detach().to(device, non_blocking=True))
+        targets_loss, ttc = _loss_inputs(batch, target, device, with_ttc, smoothed_labels_for_loss)
+        output = model(videos)
+        loss = criterion(output, targets_loss, ttc) if with_ttc else criterion(output, targets_loss)
+        preds.append(output.detach())
+        loss_sum += loss.item()
+        n_batches += 1
+        correct += int((output.max(-1)[1] == target).sum())
+        seen += int(videos.shape[0])
+    distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    all_preds, all_labels, all_ttcs = gather_predictions(preds), gather_predictions(labels), gather_predictions(ttcs)
+    name_shards = [(clips, frame_names)]
+    meters = torch.tensor([loss_sum, n_batches, correct, seen], dtype=torch.float64)
+    if distributed:
+        name_shards = [None] * dist.get_world_size()
+        dist.all_gather_object(name_shards, (clips, frame_names))
+        if dist.get_backend() == "nccl":
+            meters = meters.to(device)
+        dist.all_reduce(meters)
+        meters = meters.cpu()
+    if not distributed or dist.get_rank() == 0:
+        table = merge_prediction_shards(name_shards, all_preds, all_labels, all_ttcs)
+        acc, recall, precision, f1, confmat, auroc, ap, _, _, _ = M.calculate_metrics(all_preds.float(), all_labels)
+        lines = ["\n===================================",
+                 f"mAP: {ap}, auroc: {auroc}, acc: {acc}",
+                 f"P@0.5: {precision}, R@0.5: {recall}, F1@0.5: {f1}",
+                 f"Confmat: \n\t{confmat[0][0]} | {confmat[0][1]} \n\t{confmat[1][0]} | {confmat[1][1]}",
+                 "----------------------------"]
+        with open(stats_file, "w") as f:
+            for line in lines:
+                f.write(line + "\n")
+                print(line)
+        write_predictions_csv(preds_file, table)
+    result = {"loss": float(meters[0] / max(float(meters[1]), 1.0)), "acc1": float(100.0 * meters[2] / max(float(meters[3]), 1.0))}
+    print("* Acc@1 {:.3f} loss {:.3f}".format(result["acc1"], result["loss"]))
+    return result

@@ -6,6 +6,10 @@ again (a 9.6 MB copy) before running the model.  Here the window is a uint8 ring
 150 KB upload into the oldest slot, nothing is shifted, and the patch-embed kernel reads the ring in temporal order while applying
 the normalisation (``PatchEmbed.t_offset`` -> tad_im2col_tubelets_u8).  Results are identical to running the model on the
 reference's window: same arithmetic, same frame order.
+
+``score_video`` is the batched counterpart for a whole video that is already there: the frames are uploaded once into a
+``frame_store.FrameStore`` and the windows of a sequencer run ``batch_size`` at a time straight from the store (one window per forward
+is launch-bound; ``SlidingWindow`` stays the tool for frames that arrive one by one).
 """
 from __future__ import annotations
 
@@ -18,6 +22,51 @@ from ._lib import TadError
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
+
+
+@torch.no_grad()
+def score_video(model: torch.nn.Module, frames, *, orig_fps: int, target_fps: int, view_step: int = 1, sequencer=None, batch_size: int = 32,
+                mean=IMAGENET_MEAN, std=IMAGENET_STD, bgr: bool = False) -> dict:
+    """The anomaly score of every window of a video, batched: ``frames`` (uint8 [F,H,W,3], numpy or tensor, at the model's input size) is
+    uploaded ONCE into a ``frame_store.FrameStore``; its windows come from ``sequencer`` (default: the reference datasets'
+    ``RegularSequencer(target_fps, model.num_frames, view_step)``, dota.py:209) as a table of slots, and the model runs ``batch_size``
+    windows per forward straight from the store, in eval mode under no_grad.  Results stay on the device until the last batch is done.
+    Returns ``{"frame": int64 [S], "logits": f32 [S, num_classes], "prob": f32 [S]}`` on the host: the last frame index of each window
+    (the frame the reference labels, dota.py:217), the raw logits and softmax(logits)[:, 1]; empty tensors when the video is shorter
+    than one window (the sequencer returns None).  ``"bytes_uploaded"`` (an int, counted not timed) is what went host-to-device for
+    the frames: F * H * W * 3, against S * T * H * W * 3 when every window is uploaded as a clip.  Each window's logits are those of running the model on that window's frames as a
+    uint8 clip at the same batch size, bit for bit."""
+    from .frame_store import FrameStore
+    from .sequencing import BasicLabeledSequencer_Abs, RegularSequencer
+    pe = model.patch_embed
+    device = next(model.parameters()).device
+    if device.type != "cuda":
+        raise TadError("score_video keeps its frames in HBM: the model must be on a GPU (no CPU path)")
+    if int(batch_size) < 1:
+        raise ValueError(f"batch_size must be at least 1, got {batch_size}")
+    if isinstance(sequencer, BasicLabeledSequencer_Abs):
+        raise TypeError("score_video has no labels to give: pass a sequencer that takes the frame count (RegularSequencer[WithStart])")
+    n_frames = len(frames)
+    seq = sequencer if sequencer is not None else RegularSequencer(int(target_fps), int(model.num_frames), int(view_step))
+    store = FrameStore(max(n_frames, 1), int(pe.img_size[0]), int(pe.img_size[1]), device, bgr=bgr)
+    if n_frames:
+        store.append(frames)  # (also the dtype / shape check)
+    windows = seq.get_sequences(n_frames, int(orig_fps))
+    nc = int(model.num_classes)
+    if windows is None:
+        return {"frame": torch.zeros(0, dtype=torch.int64), "logits": torch.zeros((0, nc), dtype=torch.float32),
+                "prob": torch.zeros(0, dtype=torch.float32), "bytes_uploaded": store.bytes_uploaded}
+    table = np.asarray(windows, dtype=np.int64)
+    pe.set_input_normalization(mean, std, bgr=bgr)
+    was_training = model.training
+    model.eval()
+    try:
+        outs = [model(store.windows(table[lo:lo + int(batch_size)])) for lo in range(0, len(table), int(batch_size))]
+    finally:
+        model.train(was_training)
+    logits = torch.cat(outs, dim=0).float()
+    prob = torch.softmax(logits, dim=1)[:, 1]
+    return {"frame": torch.from_numpy(table[:, -1].copy()), "logits": logits.cpu(), "prob": prob.cpu(), "bytes_uploaded": store.bytes_uploaded}
 
 
 class SlidingWindow:

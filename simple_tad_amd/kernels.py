@@ -298,6 +298,30 @@ def im2col_tubelets_u8(frames: torch.Tensor, tubelet: int, patch: int, mean, std
     return cols
 
 
+def im2col_frame_windows(store: torch.Tensor, idx: torch.Tensor, tubelet: int, patch: int, mean, std, bgr: bool = False, dtype=None) -> torch.Tensor:
+    """store [F,H,W,3] uint8, idx [B,T] int32 (device; the CALLER has checked 0 <= idx < F on the host: frame_store.FrameStore.windows)
+    -> the normalised 16-bit patch matrix of the B windows store[idx], bit-identical to im2col_tubelets_u8(store[idx])
+    (tad_im2col_frame_windows; one entry point, the operand format travels as an argument)"""
+    import ctypes as C
+    _req(store, torch.uint8, "im2col_frame_windows.store")
+    _req(idx, torch.int32, "im2col_frame_windows.idx")
+    if store.dim() != 4 or store.shape[-1] != 3:
+        raise _lib.TadError(f"im2col_frame_windows: store must be [F,H,W,3] uint8, got {tuple(store.shape)}")
+    if idx.dim() != 2 or idx.device != store.device:
+        raise _lib.TadError(f"im2col_frame_windows: idx must be [B,T] int32 on {store.device}, got {tuple(idx.shape)} on {idx.device}")
+    F, H, W, _ = store.shape
+    B, T = idx.shape
+    ntok = (T // tubelet) * (H // patch) * (W // patch)
+    cols = torch.empty((B * ntok, patch_embed_ldk(3, tubelet, patch)), dtype=dtype or _op16, device=store.device)
+    _req16(cols, "im2col_frame_windows.cols")
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s = (C.c_float * 3)(*[float(v) for v in std])
+    with _timed("im2col_u8", 0.0, float(B * T * H * W * 3) + 2.0 * cols.numel()):
+        check(_lib.load().tad_im2col_frame_windows(store.data_ptr(), F, idx.data_ptr(), cols.data_ptr(), _dt(cols), B, T, H, W, tubelet, patch, m, s,
+                                                   int(bool(bgr)), _stream()), "tad_im2col_frame_windows")
+    return cols
+
+
 def patch_embed_gemm(cols, w_bf16, bias, pos, ntok: int):
     """cols [B*ntok, K] bf16 -> out [B, ntok, D] f32 = cols w^T + bias (+ pos [ntok, D] broadcast over the batch)"""
     op = _req16(cols, "patch_embed_gemm.cols")

@@ -21,6 +21,7 @@ import torch.utils.checkpoint as checkpoint
 
 from . import ops
 from ._lib import TadError
+from .frame_store import FrameWindows
 from .registry import register_model
 
 
@@ -246,7 +247,20 @@ class PatchEmbed(nn.Module):
         return ops.PatchEmbedU8Fn.apply(frames, self.proj.weight, self.proj.bias, pos_embed, self.tubelet_size, self.patch_size[0],
                                         self.input_mean, self.input_std, self.input_bgr, int(self.t_offset))
 
+    def _forward_windows(self, fw, pos_embed):
+        """fw: frame_store.FrameWindows -- B windows [B,T] of one uint8 frame store [F,H,W,3]: the patch matrix is built straight from
+        the store (no [B,T,H,W,3] clips in memory); the channel order is the store's, mean / std are this module's"""
+        B, T, H, W, C = fw.shape
+        assert C == 3 and H == self.img_size[0] and W == self.img_size[1], \
+            f"Input image size ({H}*{W}) doesn't match model ({self.img_size[0]}*{self.img_size[1]})."
+        if ops.get_precision() == "precise":
+            raise TadError('precision "precise" takes the normalised f32 clip (the uint8 input stage feeds the bf16 path)')
+        return ops.PatchEmbedWindowsFn.apply(fw.store, fw.idx, self.proj.weight, self.proj.bias, pos_embed, self.tubelet_size, self.patch_size[0],
+                                             self.input_mean, self.input_std, fw.bgr)
+
     def forward(self, x, pos_embed=None, **kwargs):
+        if isinstance(x, FrameWindows):
+            return self._forward_windows(x, pos_embed)
         if x.dtype == torch.uint8:
             return self._forward_u8(x, pos_embed)
         B, C, T, H, W = x.shape

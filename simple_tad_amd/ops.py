@@ -384,6 +384,28 @@ class PatchEmbedU8Fn(_Fn):
         return None, (None if dW is None else dW.reshape(weight.shape)), db, None, None, None, None, None, None, None
 
 
+class PatchEmbedWindowsFn(_Fn):
+    """PatchEmbed on B windows of ONE device-resident frame store (frame_store.FrameWindows): PatchEmbedU8Fn with the patch matrix read
+    through an index table [B,T] instead of from materialised clips (K.im2col_frame_windows: bit-identical to
+    K.im2col_tubelets_u8(store[idx])); the same saved ``cols`` and the same backward, so training from a store costs nothing extra."""
+
+    @staticmethod
+    def forward(ctx, store, idx, weight, bias, pos, tubelet, patch, mean, std, bgr):
+        _need_gpu(store, "PatchEmbed")
+        B, T = idx.shape
+        _, H, W, _ = store.shape
+        cols = K.im2col_frame_windows(store, idx, tubelet, patch, mean, std, bgr)   # row stride tad_patch_embed_ldk (zero-padded for /14)
+        ntok = (T // tubelet) * (H // patch) * (W // patch)
+        out = K.patch_embed_gemm(cols, K.pad_k(w_bf16(weight, _differentiated(ctx)), cols.shape[1]), _f32c(bias), _f32c(pos), ntok)
+        ctx.save_for_backward(cols)
+        ctx.params = (weight, bias)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        return (None,) + PatchEmbedU8Fn.backward(ctx, dy)[:-1]  # (store, idx | weight, bias, pos, tubelet, patch, mean, std, bgr)
+
+
 # --------------------------------------------------------------------------- attention / mlp cores (2-D tensors)
 def head_dim_of(qkv_w, H):
     return qkv_w.shape[0] // (3 * H)
