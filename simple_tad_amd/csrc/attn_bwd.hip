@@ -178,8 +178,9 @@ __global__ __launch_bounds__(256, HD == 64 ? 3 : 2) void attn_bwd_dq_kernel(cons
   }
 
   // K/V tiles go global -> LDS by LDS-DMA (see attn_fwd.hip): 1-KiB piece = 8 keys x 128 B, wave w moves pieces w and w+4 of K and
-  // of V; the swizzle is applied to the per-lane SOURCE chunk.  Reads past the tensor return zero; keys >= N are masked below.
-  const uint32_t qkv_bytes = (uint32_t)B * (uint32_t)N * (uint32_t)tok * 2u;
+  // of V; the swizzle is applied to the per-lane SOURCE chunk.  The descriptor ends with clip b, so keys >= N read as zero (never the
+  // first rows of clip b + 1: a non-finite V row there would make dP, and with it 0 * dP, NaN); they are masked below as well.
+  const uint32_t qkv_bytes = (uint32_t)(b + 1) * (uint32_t)N * (uint32_t)tok * 2u;
   const auto rs_qkv = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(qkv), 0, (int)qkv_bytes, 0x00020000);
   uint32_t dma_k[2];
 #pragma unroll
@@ -382,9 +383,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __
   }
 
   // Q / dO tiles go global -> LDS by LDS-DMA (1-KiB piece = 8 rows x 128 B, wave w moves pieces w and w+4 of each; swizzle on the
-  // per-lane SOURCE chunk); rows past the tensor read as zero, rows >= N are neutralised through the row constants below.
-  const uint32_t qkv_bytes = (uint32_t)B * (uint32_t)N * (uint32_t)tok * 2u;
-  const uint32_t do_bytes = (uint32_t)B * (uint32_t)N * (uint32_t)(H * BHD) * 2u;
+  // per-lane SOURCE chunk).  Both descriptors end with clip b, so rows >= N read as zero (never the first Q / dO rows of clip b + 1,
+  // which would otherwise enter the scores and the second products: inf + -3e30, 0 * inf); they are also neutralised through the row
+  // constants below.
+  const uint32_t qkv_bytes = (uint32_t)(b + 1) * (uint32_t)N * (uint32_t)tok * 2u;
+  const uint32_t do_bytes = (uint32_t)(b + 1) * (uint32_t)N * (uint32_t)(H * BHD) * 2u;
   const auto rs_qkv = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(qkv), 0, (int)qkv_bytes, 0x00020000);
   const auto rs_do = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(dout), 0, (int)do_bytes, 0x00020000);
   uint32_t dma_q[2], dma_do[2];

@@ -102,8 +102,10 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_kernel(const uint16_t* __rest
 
   // staging: K/V tiles go global -> LDS by LDS-DMA (no staging registers, no ds_write): a 1-KiB piece = 8 keys x 128 B; wave w
   // moves pieces w and w+4 of K and of V.  The LDS destination is lane-linear, so the swizzle is applied to the per-lane
-  // SOURCE chunk.  Keys past the end of the tensor read as zero (buffer bounds check); keys >= N of this sequence are masked.
-  const uint32_t qkv_bytes = (uint32_t)B * (uint32_t)N * (uint32_t)tok_stride * 2u;
+  // SOURCE chunk.  The descriptor ends with clip b (a wave-uniform constant), so keys >= N of this sequence read as zero (buffer bounds
+  // check) -- never the first rows of clip b + 1, whose V rows would otherwise meet P = 0 in the second product (0 * inf = NaN) -- and
+  // their scores are masked.
+  const uint32_t qkv_bytes = (uint32_t)(b + 1) * (uint32_t)N * (uint32_t)tok_stride * 2u;
   const auto rs_qkv = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(qkv), 0, (int)qkv_bytes, 0x00020000);
   const int dkey = lane >> 3, dch = lane & 7;
   uint32_t dma_k[2], dma_v[2];
@@ -402,7 +404,7 @@ __global__ __launch_bounds__(128, 2) void attn_fwd_q64_kernel(const uint16_t* __
     for (int ks = 0; ks < NKS; ++ks) qf[hh][ks] = *reinterpret_cast<const op16x8*>(qp + 16 * ks);
   }
   // staging as in attn_fwd_kernel; a tile's 8 + 8 one-KiB pieces are shared by TWO waves: wave w moves pieces w, w + 2, w + 4, w + 6 of K and of V
-  const uint32_t qkv_bytes = (uint32_t)B * (uint32_t)N * (uint32_t)tok_stride * 2u;
+  const uint32_t qkv_bytes = (uint32_t)(b + 1) * (uint32_t)N * (uint32_t)tok_stride * 2u;  // (ends with clip b: see attn_fwd_kernel)
   const auto rs_qkv = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(qkv), 0, (int)qkv_bytes, 0x00020000);
   const int dkey = lane >> 3, dch = lane & 7;
   uint32_t dma_k[4], dma_v[4];

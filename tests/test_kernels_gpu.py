@@ -335,12 +335,13 @@ def test_attention_fwd_q64_variant_is_bit_identical(K, B, N, H):
 @pytest.mark.parametrize("prescaled", [True, False], ids=["q_prescaled", "plain_q"])
 def test_attention_softmax_spike(K, prescaled):
     """Force every branch of the online softmax's offset handling (cdna_hip_programming.md rule 26: a rare data-dependent branch needs an
-    input that takes it).  The kernel keeps the offset at 0 while a row's tile maxima stay inside (-RESCALE_LOW, RESCALE_THR] log2
-    units, re-bases on the first tile when its maximum is below that window and whenever a later tile's maximum exceeds it; the
-    score accumulators then start from the per-wave LDS table instead of the constant 0:
-      query 17: late-arriving maxima in tiles 0 and 2 (two upward moves);  query 64: one upward move in tile 2;
-      query 40: every score far below 0 (q anti-parallel to all keys' common component): downward move on the first tile;
-      query 41: far below 0 in tile 0, a key in tile 1 with a positive score far above the (negative) offset."""
+    input that takes it).  attn_fwd.hip keeps one running maximum per row, started at -1e30, so the first tile always sets it; in a later
+    tile it moves -- for all 32 rows of the wave, each to its own maximum so far, with the accumulators and the row sum rescaled -- only
+    when some row of the wave has a tile maximum more than RESCALE_THR = 8 log2 units above its running one, and P may reach 2^8
+    meanwhile.  One v_sub per score takes the running maximum off; there is no other offset:
+      query 17: late-arriving maxima in tiles 0 and 2 (the move in tile 2 rescales the whole wave);  query 64: one move in tile 2;
+      query 40: every score far below 0 (q anti-parallel to all keys' common component): the first tile sets a maximum near -96;
+      query 41: far below 0 in tile 0, a key in tile 1 with a positive score far above that (negative) maximum."""
     B, N, H = 1, 200, 1
     scale = 64 ** -0.5
     qkv = bf(R.tensor_for("att.spike", (B * N, 3 * H * 64), scale=1.0))
