@@ -24,6 +24,39 @@ namespace tad {
 // shared by both passes (defined once, capi.hip)
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+
+// grid of a streaming kernel: one thread per work item up to 2048 blocks (~8 per CU), a grid-stride loop beyond
+static inline int capped_grid(int64_t work_items, int block) {
+  int64_t g = (work_items + block - 1) / block;
+  if (g > 2048) g = 2048;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
+// f32 -> 16-bit operand of format FMT (TAD_BF16 / TAD_F16), round-to-nearest-even: the plain casts lower to v_cvt_pk_bf16_f32 /
+// v_cvt_pk_f16_f32 on gfx950 and keep a NaN a NaN.  The format is a template argument for files compiled once for both formats
+// (im2col.hip); the per-pass f32_to_op16 / pack_op16x2 below are the current pass's instances.
+template <int FMT>
+__device__ __forceinline__ uint16_t f32_to_16(float f) {
+  if constexpr (FMT == TAD_F16) return __builtin_bit_cast(uint16_t, (_Float16)f);
+  else return __builtin_bit_cast(uint16_t, (__bf16)f);
+}
+template <int FMT>
+__device__ __forceinline__ uint32_t pack16x2(float lo, float hi) {
+  if constexpr (FMT == TAD_F16) {
+    typedef __attribute__((ext_vector_type(2))) _Float16 h2;
+    const h2 v = {(_Float16)lo, (_Float16)hi};
+    return __builtin_bit_cast(uint32_t, v);
+  } else {
+    typedef __attribute__((ext_vector_type(2))) __bf16 b2;
+    const b2 v = {(__bf16)lo, (__bf16)hi};
+    return __builtin_bit_cast(uint32_t, v);
+  }
+}
+
+// A uint8 pixel value as the network sees it: ToTensor (u / 255), then tensor_normalize ((v - mean) / std).  Two IEEE divisions and one
+// subtraction, each rounded on its own whatever -ffp-contract says: every kernel that reads uint8 frames writes these bits.
+__device__ __forceinline__ float normalize_u8(float u, float mean, float sd) { return __fdiv_rn(__fsub_rn(__fdiv_rn(u, 255.0f), mean), sd); }
 }  // namespace tad
 
 TAD_NAMESPACE_BEGIN
@@ -61,8 +94,7 @@ constexpr int WAVE = 64;
     }                                         \
   } while (0)
 
-// 16-bit operand <-> f32.  bf16: the upper half of the f32 pattern; f16: v_cvt_f32_f16.  Round-to-nearest-even on the way down;
-// the plain casts lower to v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32 on gfx950 and keep a NaN a NaN.
+// 16-bit operand <-> f32.  bf16: the upper half of the f32 pattern; f16: v_cvt_f32_f16.  Round-to-nearest-even on the way down.
 __device__ __forceinline__ float op16_to_f32(uint16_t v) {
 #ifdef TAD_OPND_F16
   return (float)__builtin_bit_cast(_Float16, v);
@@ -85,16 +117,8 @@ __device__ __forceinline__ float op16_hi_f32(uint32_t w) {
   return __uint_as_float(w & 0xffff0000u);
 #endif
 }
-__device__ __forceinline__ uint16_t f32_to_op16(float f) {
-  op16_t b = (op16_t)f;
-  return __builtin_bit_cast(uint16_t, b);
-}
-__device__ __forceinline__ uint32_t pack_op16x2(float lo, float hi) {
-  op16x2 v;
-  v[0] = (op16_t)lo;
-  v[1] = (op16_t)hi;
-  return __builtin_bit_cast(uint32_t, v);
-}
+__device__ __forceinline__ uint16_t f32_to_op16(float f) { return f32_to_16<TAD_OP16>(f); }
+__device__ __forceinline__ uint32_t pack_op16x2(float lo, float hi) { return pack16x2<TAD_OP16>(lo, hi); }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -1,15 +1,8 @@
-// HBM-bound helper kernels: casts, tubelet im2col, mean-pool, column sums, sum of squares.
+// HBM-bound helper kernels: casts, mean-pool, column sums, sum of squares.
 // All are streaming kernels: 16-byte vector accesses, grid capped at ~8 blocks/CU with grid-stride loops.
 #include "common.h"
 
 TAD_NAMESPACE_BEGIN
-
-static inline int capped_grid(int64_t work_items, int block) {
-  int64_t g = (work_items + block - 1) / block;
-  if (g > 2048) g = 2048;
-  if (g < 1) g = 1;
-  return (int)g;
-}
 
 // ---------------------------------------------------------------- cast f32 -> bf16
 __global__ void cast_f32_bf16_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, int64_t n) {
@@ -84,168 +77,6 @@ __global__ __launch_bounds__(256) void transpose_bf16_batched_kernel(const uint1
     }
   }
 }
-
-// ---------------------------------------------------------------- input stage: uint8 frames -> normalised bf16 patch matrix
-// frames [B,T,H,W,3] uint8 (decoder / cv2 layout) -> cols [B*N, 3*tub*p*p] bf16 with the reference's arithmetic
-//   v = (float(u8) / 255 - mean[c]) / std[c]      (run_inference.py:22-32 prepare_image; dota.py:443-460 tensor_normalize)
-// in f32 with IEEE divisions, then the same RNE cast to bf16 as the f32 path -- so the patch matrix is bit-identical to
-// im2col_tubelets(normalise(frames)) while reading 4x fewer bytes and skipping the f32 clip entirely.  ``bgr``: the channel in
-// memory is 2 - c (cv2 frames; the reference converts with cv2.cvtColor(BGR2RGB)).  ``t_offset``: frame t of the clip lives in
-// slot (t + t_offset) % T of the buffer (sliding-window ring buffer of run_inference.py:86-93 without shifting the frames).
-// One thread: 8 consecutive pixels of one row = 24 contiguous bytes in, three 16-byte chunks out (one per channel).
-__global__ void im2col_tubelets_u8_kernel(const uint8_t* __restrict__ frames, uint16_t* __restrict__ cols, int B, int T, int H, int W,
-                                          int tub, int p, float m0, float m1, float m2, float s0, float s1, float s2, int bgr,
-                                          int t_offset) {
-  const int W8 = W >> 3;
-  const int64_t total = (int64_t)B * T * H * W8;
-  const int Hp = H / p, Wp = W / p, Tp = T / tub;
-  const int K = 3 * tub * p * p;
-  const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    int64_t r = i;
-    const int w8 = (int)(r % W8); r /= W8;
-    const int h = (int)(r % H); r /= H;
-    const int t = (int)(r % T); r /= T;  // frame index inside the clip
-    const int b = (int)r;
-    int slot = t + t_offset;
-    slot = slot >= T ? slot - T : slot;
-    const uint8_t* src = frames + ((((int64_t)b * T + slot) * H + h) * W + (int64_t)w8 * 8) * 3;
-    uint32_t raw[6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) raw[q] = reinterpret_cast<const uint32_t*>(src)[q];  // (W*3*8) % 4 == 0: 4-byte aligned
-    const int w = w8 * 8;
-    const int tp = t / tub, kt = t - tp * tub, hp = h / p, kh = h - hp * p, wp = w / p, kw = w - wp * p;
-    const int64_t n = ((int64_t)b * Tp + tp) * Hp * Wp + (int64_t)hp * Wp + wp;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int cm = bgr ? 2 - c : c;  // channel position in memory
-      float v[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int byte = e * 3 + cm;
-        const float u = (float)((raw[byte >> 2] >> ((byte & 3) * 8)) & 0xffu);
-        v[e] = (u / 255.0f - mean[c]) / sd[c];
-      }
-      const int k = ((c * tub + kt) * p + kh) * p + kw;
-      *reinterpret_cast<uint4*>(cols + n * K + k) =
-          make_uint4(pack_op16x2(v[0], v[1]), pack_op16x2(v[2], v[3]), pack_op16x2(v[4], v[5]), pack_op16x2(v[6], v[7]));
-    }
-  }
-}
-
-// The same for even patch sizes that are not multiples of 8 (/14): one thread = 2 pixels = 6 contiguous bytes in, three 4-byte pairs out
-// (a pair never straddles a patch: p and w are even); rows have stride ldk = K rounded up to 64 and the thread that owns k = 0 of a
-// token zeroes the padding columns, as im2col_tubelets_pairs_kernel does for the f32 clip.
-__global__ void im2col_tubelets_u8_pairs_kernel(const uint8_t* __restrict__ frames, uint16_t* __restrict__ cols, int B, int T, int H, int W,
-                                                int tub, int p, int ldk, float m0, float m1, float m2, float s0, float s1, float s2, int bgr,
-                                                int t_offset) {
-  const int W2 = W >> 1;
-  const int64_t total = (int64_t)B * T * H * W2;
-  const int Hp = H / p, Wp = W / p, Tp = T / tub;
-  const int K = 3 * tub * p * p;
-  const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    int64_t r = i;
-    const int w2 = (int)(r % W2); r /= W2;
-    const int h = (int)(r % H); r /= H;
-    const int t = (int)(r % T); r /= T;
-    const int b = (int)r;
-    int slot = t + t_offset;
-    slot = slot >= T ? slot - T : slot;
-    const uint8_t* src = frames + ((((int64_t)b * T + slot) * H + h) * W + (int64_t)w2 * 2) * 3;  // 6 bytes, 2-byte aligned
-    const uint16_t* s2p = reinterpret_cast<const uint16_t*>(src);
-    const uint32_t lo = (uint32_t)s2p[0] | ((uint32_t)s2p[1] << 16);  // bytes 0..3
-    const uint32_t hi = (uint32_t)s2p[2];                             // bytes 4..5
-    const int w = w2 * 2;
-    const int tp = t / tub, kt = t - tp * tub, hp = h / p, kh = h - hp * p, wp = w / p, kw = w - wp * p;
-    const int64_t n = ((int64_t)b * Tp + tp) * Hp * Wp + (int64_t)hp * Wp + wp;
-    uint16_t* row = cols + n * ldk;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int cm = bgr ? 2 - c : c;
-      const int b0 = cm, b1 = 3 + cm;  // byte positions of the two pixels' channel
-      const float u0 = (float)((lo >> (b0 * 8)) & 0xffu);
-      const float u1 = (float)(((b1 < 4 ? lo >> (b1 * 8) : hi >> ((b1 - 4) * 8))) & 0xffu);
-      const int k = ((c * tub + kt) * p + kh) * p + kw;
-      *reinterpret_cast<uint32_t*>(row + k) = pack_op16x2((u0 / 255.0f - mean[c]) / sd[c], (u1 / 255.0f - mean[c]) / sd[c]);
-    }
-    if (kt == 0 && kh == 0 && kw == 0)  // (k = 0 of channel 0)
-      for (int z = K; z < ldk; z += 2) *reinterpret_cast<uint32_t*>(row + z) = 0u;
-  }
-}
-
-// ---------------------------------------------------------------- tubelet im2col
-// x [B,C,T,H,W] f32 -> cols [B*N, K] bf16, token n = (t'*H' + h')*W' + w', k = ((c*tub+kt)*p+kh)*p+kw.
-// One thread moves 8 consecutive w (32 B in, 16 B out); threads walk x in memory order -> coalesced reads.
-__global__ void im2col_tubelets_kernel(const float* __restrict__ x, uint16_t* __restrict__ cols, int B, int C,
-                                       int T, int H, int W, int tub, int p) {
-  const int W8 = W >> 3;
-  const int64_t total = (int64_t)B * C * T * H * W8;
-  const int Hp = H / p, Wp = W / p, Tp = T / tub;
-  const int K = C * tub * p * p;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    int64_t r = i;
-    const int w8 = (int)(r % W8); r /= W8;
-    const int h = (int)(r % H); r /= H;
-    const int t = (int)(r % T); r /= T;
-    const int c = (int)(r % C); r /= C;
-    const int b = (int)r;
-    const int w = w8 << 3;
-    const float4 a0 = reinterpret_cast<const float4*>(x)[2 * i];
-    const float4 a1 = reinterpret_cast<const float4*>(x)[2 * i + 1];
-    const int tp = t / tub, kt = t - tp * tub;
-    const int hp = h / p, kh = h - hp * p;
-    const int wp = w / p, kw = w - wp * p;
-    const int64_t n = ((int64_t)(b * Tp + tp) * Hp + hp) * Wp + wp;
-    const int k = ((c * tub + kt) * p + kh) * p + kw;
-    uint4 o;
-    o.x = pack_op16x2(a0.x, a0.y);
-    o.y = pack_op16x2(a0.z, a0.w);
-    o.z = pack_op16x2(a1.x, a1.y);
-    o.w = pack_op16x2(a1.z, a1.w);
-    *reinterpret_cast<uint4*>(cols + n * K + k) = o;
-  }
-}
-
-// Patch sizes that are even but not a multiple of 8 (ViT-L/14: p = 14, K = 3*2*14*14 = 1176): one thread moves 2 consecutive w.  The
-// patch matrix gets a row stride of ldk = K rounded up to the GEMM's K-tile (64); the thread that owns k = 0 of a token zeroes the
-// ldk - K padding columns of its row, so the padded matrix times a zero-padded weight is the un-padded product exactly.
-template <typename OutT>
-__global__ void im2col_tubelets_pairs_kernel(const float* __restrict__ x, OutT* __restrict__ cols, int B, int C, int T, int H, int W,
-                                             int tub, int p, int ldk) {
-  const int W2 = W >> 1;
-  const int64_t total = (int64_t)B * C * T * H * W2;
-  const int Hp = H / p, Wp = W / p, Tp = T / tub;
-  const int K = C * tub * p * p;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    int64_t r = i;
-    const int w2 = (int)(r % W2); r /= W2;
-    const int h = (int)(r % H); r /= H;
-    const int t = (int)(r % T); r /= T;
-    const int c = (int)(r % C); r /= C;
-    const int b = (int)r;
-    const int w = w2 << 1;
-    const float2 a = reinterpret_cast<const float2*>(x)[i];
-    const int tp = t / tub, kt = t - tp * tub, hp = h / p, kh = h - hp * p, wp = w / p, kw = w - wp * p;
-    const int64_t n = ((int64_t)(b * Tp + tp) * Hp + hp) * Wp + wp;
-    const int k = ((c * tub + kt) * p + kh) * p + kw;
-    OutT* row = cols + n * ldk;
-    if constexpr (sizeof(OutT) == 2) *reinterpret_cast<uint32_t*>(row + k) = pack_op16x2(a.x, a.y);
-    else *reinterpret_cast<float2*>(row + k) = a;
-    if (k == 0) {
-      for (int z = K; z < ldk; z += 2) {
-        if constexpr (sizeof(OutT) == 2) *reinterpret_cast<uint32_t*>(row + z) = 0u;
-        else *reinterpret_cast<float2*>(row + z) = make_float2(0.f, 0.f);
-      }
-    }
-  }
-}
-template __global__ void im2col_tubelets_pairs_kernel<uint16_t>(const float*, uint16_t*, int, int, int, int, int, int, int, int);
-template __global__ void im2col_tubelets_pairs_kernel<float>(const float*, float*, int, int, int, int, int, int, int, int);
 
 // ---------------------------------------------------------------- mean-pool
 // partial[b][s][D]: block (x = column chunk of 256, y = split s, z = b); 4 waves stride over the rows of the split.
@@ -634,13 +465,6 @@ int launch_reduce_partials(const float* partial, float* out, int splits, int64_t
 TAD_NAMESPACE_END
 
 TAD_NAMESPACE_BEGIN
-// precise-mode (f32) patch matrix for even patch sizes that are not a multiple of 4; called from precise.hip
-int launch_im2col_pairs_f32(const float* x, float* cols, int B, int C, int T, int H, int W, int tubelet, int patch, int ldk, hipStream_t st) {
-  const int64_t pairs = (int64_t)B * C * T * H * (W / 2);
-  hipLaunchKernelGGL(im2col_tubelets_pairs_kernel<float>, dim3(capped_grid(pairs, 256)), dim3(256), 0, st, x, cols, B, C, T, H, W, tubelet,
-                     patch, ldk);
-  return check_launch("im2col_f32");
-}
 // ---------------------------------------------------------------- operand split for the precise / split-operand Linears
 // x = hi + lo with hi = op16(x), lo = op16(x - hi) (bf16: 16 significant bits, f16: 22).  A product of two f32 operands is recovered
 // to ~2^-17 (bf16) relative from three MFMA products  A_hi*B_hi + A_hi*B_lo + A_lo*B_hi  -- and those three products are ONE GEMM
@@ -714,46 +538,6 @@ int tad_patch_embed_ldk(int C, int tubelet, int patch) {
   return (K + 63) / 64 * 64;
 }
 #endif
-
-int tad_im2col_tubelets(const float* x, uint16_t* cols, int B, int C, int T, int H, int W, int tubelet, int patch,
-                        tad_stream_t stream) {
-  TAD_REQUIRE(x && cols, "im2col: null pointer");
-  TAD_REQUIRE(B > 0 && C > 0 && tubelet > 0 && patch > 0 && T % tubelet == 0 && H % patch == 0 && W % patch == 0,
-              "im2col: T/H/W must be multiples of tubelet/patch (got T=%d H=%d W=%d tub=%d p=%d)", T, H, W, tubelet, patch);
-  TAD_REQUIRE(patch % 2 == 0, "im2col: patch size must be even (got %d)", patch);
-  if (patch % 8) {  // row stride tad_patch_embed_ldk(): see im2col_tubelets_pairs_kernel
-    const int64_t pairs = (int64_t)B * C * T * H * (W / 2);
-    hipLaunchKernelGGL(im2col_tubelets_pairs_kernel<uint16_t>, dim3(capped_grid(pairs, 256)), dim3(256), 0, (hipStream_t)stream, x, cols, B,
-                       C, T, H, W, tubelet, patch, tad_patch_embed_ldk(C, tubelet, patch));
-    return check_launch("im2col_tubelets");
-  }
-  const int64_t total = (int64_t)B * C * T * H * (W / 8);
-  hipLaunchKernelGGL(im2col_tubelets_kernel, dim3(capped_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, x, cols, B, C, T,
-                     H, W, tubelet, patch);
-  return check_launch("im2col_tubelets");
-}
-
-int tad_im2col_tubelets_u8(const uint8_t* frames, uint16_t* cols, int B, int T, int H, int W, int tubelet, int patch, const float* mean3,
-                           const float* std3, int bgr, int t_offset, tad_stream_t stream) {
-  TAD_REQUIRE(frames && cols && mean3 && std3, "im2col_u8: null pointer");
-  TAD_REQUIRE(B > 0 && tubelet > 0 && patch > 0 && T % tubelet == 0 && H % patch == 0 && W % patch == 0,
-              "im2col_u8: T/H/W must be multiples of tubelet/patch (got T=%d H=%d W=%d tub=%d p=%d)", T, H, W, tubelet, patch);
-  TAD_REQUIRE(patch % 2 == 0, "im2col_u8: patch size must be even (got %d)", patch);
-  TAD_REQUIRE(t_offset >= 0 && t_offset < T, "im2col_u8: t_offset=%d outside [0, %d)", t_offset, T);
-  TAD_REQUIRE(std3[0] != 0.f && std3[1] != 0.f && std3[2] != 0.f, "im2col_u8: zero std");
-  TAD_REQUIRE((((uintptr_t)frames) & 3) == 0 && (((uintptr_t)cols) & 15) == 0, "im2col_u8: misaligned buffers");
-  if (patch % 8) {  // rows of stride tad_patch_embed_ldk, zero-padded (ViT-L/14: K = 1176 -> 1216)
-    const int ldk = tad_patch_embed_ldk(3, tubelet, patch);
-    const int64_t pairs = (int64_t)B * T * H * (W / 2);
-    hipLaunchKernelGGL(im2col_tubelets_u8_pairs_kernel, dim3(capped_grid(pairs, 256)), dim3(256), 0, (hipStream_t)stream, frames, cols, B, T,
-                       H, W, tubelet, patch, ldk, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], bgr ? 1 : 0, t_offset);
-    return check_launch("im2col_tubelets_u8");
-  }
-  const int64_t total = (int64_t)B * T * H * (W / 8);
-  hipLaunchKernelGGL(im2col_tubelets_u8_kernel, dim3(capped_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, frames, cols, B, T, H,
-                     W, tubelet, patch, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], bgr ? 1 : 0, t_offset);
-  return check_launch("im2col_tubelets_u8");
-}
 
 #ifndef TAD_OPND_F16  // format-independent: one copy for the library (bf16 pass)
 int tad_meanpool_fwd(const float* x, float* y, float* ws, int B, int N, int D, tad_stream_t stream) {

@@ -10,7 +10,7 @@
 // Arithmetic: Pillow's 8-bit resample (ImagingResampleHorizontal_8bpc, then ImagingResampleVertical_8bpc over its bytes), in int32:
 //   ss = 1 << 21;  ss += pixel * k over the `count` taps from xmin;  byte = clip(ss >> 22, 0, 255)
 // All double arithmetic (the triangle weights, their normalisation and the rounding to 22 bits) stays on the host.  The fused f32
-// value is frames_to_clip's: ((float)byte / 255 - mean) / std with IEEE division and subtraction; the file is compiled without
+// value is frames_to_clip's: normalize_u8 (common.h) of the byte, IEEE division and subtraction; the file is compiled without
 // floating-point contraction (build.py) as randaug.hip is.
 //
 // Shape: a workgroup owns MC_TR x MC_TC outputs of one frame.  It resamples, horizontally, the input rows its vertical taps span into
@@ -147,8 +147,7 @@ __global__ __launch_bounds__(MC_THREADS) void multiscale_crop_kernel(const uint8
     for (int ch = 0; ch < 3; ++ch) {
       float v[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q)
-        v[q] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)mc_clip8(acc[ch][q]), 255.0f), nm.mean[ch]), nm.sd[ch]);
+      for (int q = 0; q < 4; ++q) v[q] = normalize_u8((float)mc_clip8(acc[ch][q]), nm.mean[ch], nm.sd[ch]);
       float* oc = o + ch * plane;
       if (valid == 4 && (reinterpret_cast<uintptr_t>(oc) & 15) == 0) {
         *reinterpret_cast<float4*>(oc) = make_float4(v[0], v[1], v[2], v[3]);

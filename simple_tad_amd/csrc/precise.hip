@@ -7,29 +7,6 @@
 
 TAD_NAMESPACE_BEGIN
 
-// x [B,C,T,H,W] f32 -> cols [B*N, K] f32 (same token / k order as im2col_tubelets_kernel)
-__global__ void im2col_tubelets_f32_kernel(const float* __restrict__ x, float* __restrict__ cols, int B, int C, int T, int H, int W,
-                                           int tub, int p) {
-  const int W4 = W >> 2;
-  const int64_t total = (int64_t)B * C * T * H * W4;
-  const int Hp = H / p, Wp = W / p, Tp = T / tub;
-  const int K = C * tub * p * p;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    int64_t r = i;
-    const int w4 = (int)(r % W4); r /= W4;
-    const int h = (int)(r % H); r /= H;
-    const int t = (int)(r % T); r /= T;
-    const int c = (int)(r % C); r /= C;
-    const int b = (int)r;
-    const int w = w4 << 2;
-    const int tp = t / tub, kt = t - tp * tub, hp = h / p, kh = h - hp * p, wp = w / p, kw = w - wp * p;
-    const int64_t n = ((int64_t)(b * Tp + tp) * Hp + hp) * Wp + wp;
-    const int k = ((c * tub + kt) * p + kh) * p + kw;
-    *reinterpret_cast<float4*>(cols + n * K + k) = reinterpret_cast<const float4*>(x)[i];
-  }
-}
-
 // elementwise erf-GELU forward / backward on f32 and f32 column sums (bias gradients) for the precise path
 __global__ void gelu_f32_kernel(const float* __restrict__ h, float* __restrict__ a, int64_t n) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -96,43 +73,22 @@ __global__ __launch_bounds__(1024) void colsum_f32_wide_kernel(const float* __re
   if (threadIdx.x < 16 && blockIdx.x * 16 + (int)threadIdx.x < N) out[blockIdx.x * 16 + threadIdx.x] = (float)red[0][threadIdx.x];
 }
 
-static inline int grid_for(int64_t items) {
-  int64_t g = (items + 255) / 256;
-  return (int)(g > 2048 ? 2048 : (g < 1 ? 1 : g));
-}
-
 TAD_NAMESPACE_END
 
-TAD_NAMESPACE_BEGIN
-int launch_im2col_pairs_f32(const float* x, float* cols, int B, int C, int T, int H, int W, int tubelet, int patch, int ldk, hipStream_t st);
-TAD_NAMESPACE_END
 using namespace tad;
 
 extern "C" {
 
 
-int tad_im2col_tubelets_f32(const float* x, float* cols, int B, int C, int T, int H, int W, int tubelet, int patch, tad_stream_t stream) {
-  TAD_REQUIRE(x && cols, "im2col_f32: null pointer");
-  TAD_REQUIRE(B > 0 && C > 0 && tubelet > 0 && patch > 0 && T % tubelet == 0 && H % patch == 0 && W % patch == 0 && patch % 2 == 0,
-              "im2col_f32: T/H/W must be multiples of tubelet/patch and patch even");
-  if (patch % 8)  // same rule as the bf16 patch matrix: row stride tad_patch_embed_ldk(), zero padding (ViT-L/14)
-    return launch_im2col_pairs_f32(x, cols, B, C, T, H, W, tubelet, patch, tad_patch_embed_ldk(C, tubelet, patch), (hipStream_t)stream);
-  hipLaunchKernelGGL(im2col_tubelets_f32_kernel, dim3(grid_for((int64_t)B * C * T * H * (W / 4))), dim3(256), 0, (hipStream_t)stream, x,
-                     cols, B, C, T, H, W, tubelet, patch);
-  return check_launch("im2col_f32");
-}
-
-
-
 int tad_gelu_f32(const float* h, float* a, int64_t n, tad_stream_t stream) {
   TAD_REQUIRE(h && a && n > 0, "gelu_f32: bad args");
-  hipLaunchKernelGGL(gelu_f32_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, h, a, n);
+  hipLaunchKernelGGL(gelu_f32_kernel, dim3(capped_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, h, a, n);
   return check_launch("gelu_f32");
 }
 
 int tad_gelu_bwd_f32(const float* dy, const float* h, float* dh, int64_t n, tad_stream_t stream) {
   TAD_REQUIRE(dy && h && dh && n > 0, "gelu_bwd_f32: bad args");
-  hipLaunchKernelGGL(gelu_bwd_f32_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, dy, h, dh, n);
+  hipLaunchKernelGGL(gelu_bwd_f32_kernel, dim3(capped_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, dy, h, dh, n);
   return check_launch("gelu_bwd_f32");
 }
 

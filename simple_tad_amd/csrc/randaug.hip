@@ -373,7 +373,7 @@ __global__ __launch_bounds__(RA_THREADS) void randaug_apply_kernel(const uint8_t
 }
 
 // ---------------------------------------------------------------- uint8 frames [B,T,H,W,3] -> normalised f32 clips [B,3,T,H,W]
-// ToTensor (x / 255), tensor_normalize ((v - mean) / std), permute: two IEEE divisions and one subtraction in f32 per element.  An item
+// ToTensor, tensor_normalize (normalize_u8, common.h: two IEEE divisions and one subtraction in f32 per element), permute.  An item
 // is four pixels of a frame: twelve bytes in, one 16-byte store per channel plane where the planes are 16-byte aligned
 __global__ __launch_bounds__(RA_THREADS) void frames_to_clip_kernel(const uint8_t* __restrict__ x, float* __restrict__ out, float m0, float m1,
                                                                    float m2, float s0, float s1, float s2, int T, int HW) {
@@ -394,14 +394,14 @@ __global__ __launch_bounds__(RA_THREADS) void frames_to_clip_kernel(const uint8_
 #pragma unroll
       for (int k = 0; k < 12; ++k) {
         const float f = (float)((w[k >> 2] >> ((k & 3) * 8)) & 255u);
-        v[k % 3][k / 3] = __fdiv_rn(__fsub_rn(__fdiv_rn(f, 255.0f), mean[k % 3]), sd[k % 3]);
+        v[k % 3][k / 3] = normalize_u8(f, mean[k % 3], sd[k % 3]);
       }
 #pragma unroll
       for (int c = 0; c < 3; ++c) *reinterpret_cast<float4*>(o + c * plane + p0) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
     } else {
       for (int k = 0; k < 3 * np; ++k) {
         const float f = (float)s[3 * p0 + k];
-        o[(k % 3) * plane + p0 + k / 3] = __fdiv_rn(__fsub_rn(__fdiv_rn(f, 255.0f), mean[k % 3]), sd[k % 3]);
+        o[(k % 3) * plane + p0 + k / 3] = normalize_u8(f, mean[k % 3], sd[k % 3]);
       }
     }
   }

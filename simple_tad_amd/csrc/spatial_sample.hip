@@ -15,7 +15,7 @@
 // without floating-point contraction, build.py)
 //   src = max(scale * (d + 0.5f) - 0.5f, 0);  i0 = min((int)src, n_in - 1);  i1 = min(i0 + 1, n_in - 1);  l1 = src - (float)i0;  l0 = 1 - l1
 //   value = l0y * (l0x * a + l1x * b) + l1y * (l0x * c + l1x * d)
-// A uint8 tap first becomes frames_to_clip's ((float)byte / 255 - mean) / std; a workgroup states those 3 x 256 values once, in LDS.
+// A uint8 tap first becomes frames_to_clip's normalize_u8 (common.h) of the byte; a workgroup states those 3 x 256 values once, in LDS.
 //
 // Shape: a gather without reuse beyond the two rows and two columns of a tap, bound by memory traffic.  A workgroup owns SS_TR x
 // SS_TC outputs of one frame for all three channels; a thread owns four neighbouring output columns of one row: it states its row's
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(SS_THREADS) void spatial_sample_kernel(const void* 
     // frames_to_clip's value of every byte, per channel: 768 entries, three per thread
     for (int e = tid; e < 3 * 256; e += SS_THREADS) {
       const int ch = e >> 8;
-      lut[e] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)(e & 255), 255.0f), nm.mean[ch]), nm.sd[ch]);
+      lut[e] = normalize_u8((float)(e & 255), nm.mean[ch], nm.sd[ch]);
     }
     __syncthreads();
   }

@@ -271,11 +271,21 @@ def pad_k(w: torch.Tensor, ldk: int) -> torch.Tensor:
     return w if w.shape[1] == ldk else torch.nn.functional.pad(w, (0, ldk - w.shape[1]))
 
 
+def _f3(values):
+    """three host floats (a per-channel mean or std) as the C entry points take them"""
+    return (C.c_float * 3)(*[float(v) for v in values])
+
+
+def _patch_matrix(B, Cc, T, H, W, tubelet, patch, dtype, device):
+    """(tokens per clip, the empty patch matrix [B*ntok, tad_patch_embed_ldk]) of B clips [Cc,T,H,W]"""
+    ntok = (T // tubelet) * (H // patch) * (W // patch)
+    return ntok, torch.empty((B * ntok, patch_embed_ldk(Cc, tubelet, patch)), dtype=dtype, device=device)
+
+
 def im2col_tubelets(x: torch.Tensor, tubelet: int, patch: int, dtype=None) -> torch.Tensor:
     _req(x, torch.float32, "im2col.x")
     B, Cc, T, H, W = x.shape
-    ntok = (T // tubelet) * (H // patch) * (W // patch)
-    cols = torch.empty((B * ntok, patch_embed_ldk(Cc, tubelet, patch)), dtype=dtype or _op16, device=x.device)
+    _, cols = _patch_matrix(B, Cc, T, H, W, tubelet, patch, dtype or _op16, x.device)
     check(_fn("tad_im2col_tubelets", cols.dtype)(x.data_ptr(), cols.data_ptr(), B, Cc, T, H, W, tubelet, patch, _stream()),
           "tad_im2col_tubelets")
     return cols
@@ -283,18 +293,14 @@ def im2col_tubelets(x: torch.Tensor, tubelet: int, patch: int, dtype=None) -> to
 
 def im2col_tubelets_u8(frames: torch.Tensor, tubelet: int, patch: int, mean, std, bgr: bool = False, t_offset: int = 0, dtype=None) -> torch.Tensor:
     """frames [B,T,H,W,3] uint8 -> normalised bf16 patch matrix [B*N, 3*tub*p*p] (tad_im2col_tubelets_u8)"""
-    import ctypes as C
     _req(frames, torch.uint8, "im2col_u8.frames")
     if frames.dim() != 5 or frames.shape[-1] != 3:
         raise _lib.TadError(f"im2col_u8: frames must be [B,T,H,W,3] uint8, got {tuple(frames.shape)}")
     B, T, H, W, _ = frames.shape
-    ntok = (T // tubelet) * (H // patch) * (W // patch)
-    cols = torch.empty((B * ntok, patch_embed_ldk(3, tubelet, patch)), dtype=dtype or _op16, device=frames.device)
-    m = (C.c_float * 3)(*[float(v) for v in mean])
-    s = (C.c_float * 3)(*[float(v) for v in std])
+    _, cols = _patch_matrix(B, 3, T, H, W, tubelet, patch, dtype or _op16, frames.device)
     with _timed("im2col_u8", 0.0, float(frames.numel()) + 2.0 * cols.numel()):
-        check(_fn("tad_im2col_tubelets_u8", cols.dtype)(frames.data_ptr(), cols.data_ptr(), B, T, H, W, tubelet, patch, m, s, int(bool(bgr)),
-                                                 int(t_offset), _stream()), "tad_im2col_tubelets_u8")
+        check(_fn("tad_im2col_tubelets_u8", cols.dtype)(frames.data_ptr(), cols.data_ptr(), B, T, H, W, tubelet, patch, _f3(mean), _f3(std),
+                                                 int(bool(bgr)), int(t_offset), _stream()), "tad_im2col_tubelets_u8")
     return cols
 
 
@@ -302,7 +308,6 @@ def im2col_frame_windows(store: torch.Tensor, idx: torch.Tensor, tubelet: int, p
     """store [F,H,W,3] uint8, idx [B,T] int32 (device; the CALLER has checked 0 <= idx < F on the host: frame_store.FrameStore.windows)
     -> the normalised 16-bit patch matrix of the B windows store[idx], bit-identical to im2col_tubelets_u8(store[idx])
     (tad_im2col_frame_windows; one entry point, the operand format travels as an argument)"""
-    import ctypes as C
     _req(store, torch.uint8, "im2col_frame_windows.store")
     _req(idx, torch.int32, "im2col_frame_windows.idx")
     if store.dim() != 4 or store.shape[-1] != 3:
@@ -311,14 +316,11 @@ def im2col_frame_windows(store: torch.Tensor, idx: torch.Tensor, tubelet: int, p
         raise _lib.TadError(f"im2col_frame_windows: idx must be [B,T] int32 on {store.device}, got {tuple(idx.shape)} on {idx.device}")
     F, H, W, _ = store.shape
     B, T = idx.shape
-    ntok = (T // tubelet) * (H // patch) * (W // patch)
-    cols = torch.empty((B * ntok, patch_embed_ldk(3, tubelet, patch)), dtype=dtype or _op16, device=store.device)
+    _, cols = _patch_matrix(B, 3, T, H, W, tubelet, patch, dtype or _op16, store.device)
     _req16(cols, "im2col_frame_windows.cols")
-    m = (C.c_float * 3)(*[float(v) for v in mean])
-    s = (C.c_float * 3)(*[float(v) for v in std])
     with _timed("im2col_u8", 0.0, float(B * T * H * W * 3) + 2.0 * cols.numel()):
-        check(_lib.load().tad_im2col_frame_windows(store.data_ptr(), F, idx.data_ptr(), cols.data_ptr(), _dt(cols), B, T, H, W, tubelet, patch, m, s,
-                                                   int(bool(bgr)), _stream()), "tad_im2col_frame_windows")
+        check(_lib.load().tad_im2col_frame_windows(store.data_ptr(), F, idx.data_ptr(), cols.data_ptr(), _dt(cols), B, T, H, W, tubelet, patch,
+                                                   _f3(mean), _f3(std), int(bool(bgr)), _stream()), "tad_im2col_frame_windows")
     return cols
 
 
@@ -884,7 +886,6 @@ def adamw_step(param, grad, exp_avg, exp_avg_sq, chunk_group, group_lr, group_wd
                grad_scale=None, sumsq_partials=None):
     """Fused AdamW over flat f32 buffers (tad_adamw_step); group_lr / group_wd / group_step are host sequences, one entry per
     parameter group (group_step: 1-based update count of the group's tensors after this call)."""
-    import ctypes as C
     for t, nm in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
         _req(t, torch.float32, "adamw." + nm)
     n = param.numel()
@@ -1096,9 +1097,8 @@ def frames_to_clip(x, mean, std, out=None):
         _req(out, torch.float32, "frames_to_clip.out")
         if tuple(out.shape) != (B, 3, T, H, W) or out.device != x.device:
             raise _lib.TadError(f"frames_to_clip.out: expected {(B, 3, T, H, W)} on {x.device}, got {tuple(out.shape)} on {out.device}")
-    m, s = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
     with _timed("frames_to_clip", 0.0, 13.0 * B * T * H * W):
-        check(_lib.load().tad_frames_to_clip(x.data_ptr(), out.data_ptr(), m, s, B, T, H, W, _stream()), "tad_frames_to_clip")
+        check(_lib.load().tad_frames_to_clip(x.data_ptr(), out.data_ptr(), _f3(mean), _f3(std), B, T, H, W, _stream()), "tad_frames_to_clip")
     return out
 
 
@@ -1154,9 +1154,7 @@ def multiscale_crop(x, table, n_hsets: int, n_vsets: int, S_h: int, S_w: int, me
         _req(out, torch.float32 if f32 else torch.uint8, "multiscale_crop.out")
         if tuple(out.shape) != shape or out.device != x.device:
             raise _lib.TadError(f"multiscale_crop.out: expected {shape} on {x.device}, got {tuple(out.shape)} on {out.device}")
-    m = s = None
-    if f32:
-        m, s = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    m, s = (_f3(mean), _f3(std)) if f32 else (None, None)
     with _timed("multiscale_crop", 0.0, float(x.numel() + out.numel() * out.element_size())):
         check(lib.tad_multiscale_crop(x.data_ptr(), out.data_ptr(), int(f32), m, s, table.data_ptr(), nbytes, B, T, Hs, Ws, S_h, S_w,
                                       n_hsets, n_vsets, _stream()), "tad_multiscale_crop")
@@ -1218,9 +1216,7 @@ def spatial_sample(x, table, S: int, mean=None, std=None, out=None):
         _req(out, torch.float32, "spatial_sample.out")
         if tuple(out.shape) != shape or out.device != x.device:
             raise _lib.TadError(f"spatial_sample.out: expected {shape} on {x.device}, got {tuple(out.shape)} on {out.device}")
-    m = s = None
-    if u8:
-        m, s = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    m, s = (_f3(mean), _f3(std)) if u8 else (None, None)
     with _timed("spatial_sample", 0.0, float(x.numel() * x.element_size() + out.numel() * 4)):
         check(lib.tad_spatial_sample(x.data_ptr(), int(u8), out.data_ptr(), m, s, table.data_ptr(), nbytes, B, T, H, W, S, _stream()),
               "tad_spatial_sample")
@@ -1324,7 +1320,6 @@ def mae_assemble(x_vis, mask_token, pos, vis_idx, mask_idx, B):
 
 def mae_target(videos, mask_idx, tubelet, patch, mean, std, normalize_target=True):
     """videos [B,3,T,H,W] f32 (normalised) -> labels [B, Nm, tub*p*p*3] f32 for the masked tokens (engine_for_pretraining.py:51-66)"""
-    import ctypes as C
     _req(videos, torch.float32, "mae_target.videos")
     _idx(mask_idx, "mae_target.mask_idx")
     B, Cc, T, H, W = videos.shape
@@ -1332,11 +1327,9 @@ def mae_target(videos, mask_idx, tubelet, patch, mean, std, normalize_target=Tru
         raise _lib.TadError("mae_target: clips must have 3 channels")
     Nm = mask_idx.numel() // B
     labels = torch.empty((B, Nm, tubelet * patch * patch * 3), dtype=torch.float32, device=videos.device)
-    m = (C.c_float * 3)(*[float(v) for v in mean])
-    s = (C.c_float * 3)(*[float(v) for v in std])
     with _timed("mae_target", 0.0, 8.0 * labels.numel()):
-        check(_lib.load().tad_mae_target(videos.data_ptr(), mask_idx.data_ptr(), labels.data_ptr(), B, Nm, T, H, W, tubelet, patch, m, s,
-                                         int(bool(normalize_target)), _stream()), "tad_mae_target")
+        check(_lib.load().tad_mae_target(videos.data_ptr(), mask_idx.data_ptr(), labels.data_ptr(), B, Nm, T, H, W, tubelet, patch, _f3(mean),
+                                         _f3(std), int(bool(normalize_target)), _stream()), "tad_mae_target")
     return labels
 
 
@@ -1356,7 +1349,6 @@ def mse_loss(pred, target, want_grad=True):
 
 
 def device_info():
-    import ctypes as C
     cu, clk, ldsb = C.c_int(), C.c_int(), C.c_int()
     name = C.create_string_buffer(64)
     check(_lib.load().tad_device_info(C.byref(cu), C.byref(clk), C.byref(ldsb), name, 64), "tad_device_info")
@@ -1376,8 +1368,7 @@ def split_bf16x3(x, role_b: bool, stack: bool = False, dtype=torch.bfloat16):
 def im2col_tubelets_f32(x, tubelet: int, patch: int):
     _req(x, torch.float32, "im2col_f32.x")
     B, Cc, T, H, W = x.shape
-    ntok = (T // tubelet) * (H // patch) * (W // patch)
-    cols = torch.empty((B * ntok, patch_embed_ldk(Cc, tubelet, patch)), dtype=torch.float32, device=x.device)
+    _, cols = _patch_matrix(B, Cc, T, H, W, tubelet, patch, torch.float32, x.device)
     check(_lib.load().tad_im2col_tubelets_f32(x.data_ptr(), cols.data_ptr(), B, Cc, T, H, W, tubelet, patch, _stream()),
           "tad_im2col_tubelets_f32")
     return cols

@@ -319,6 +319,20 @@ class LayerNormFn(_Fn):
 IMPLICIT_PATCH_EMBED_MIN_TILES = 512
 
 
+def _patch_embed_backward(ctx, dy, trailing: int):
+    """(dweight, dbias) of a 16-bit patch embedding from its saved patch matrix, then ``trailing`` Nones for the inputs after bias"""
+    (cols,) = ctx.saved_tensors
+    weight, bias = ctx.params
+    dyb = K.cast_bf16(_f32c(dy).reshape(-1, dy.shape[-1]))
+    kw = weight.numel() // weight.shape[0]
+    if cols.shape[1] != kw:  # padded K: the gradient of the padding columns is dropped (no in-place sink for a [D, ldk] result)
+        dWp, db = K.linear_bwd_weight(dyb, cols, want_bias=bias is not None)
+        dW = dWp[:, :kw]
+    else:
+        dW, db = linear_dw(dyb, cols, weight, bias)
+    return (None if dW is None else dW.reshape(weight.shape), db) + (None,) * trailing
+
+
 class PatchEmbedFn(_Fn):
     """Conv3d(k=s=(tub,p,p)) + flatten/transpose (+ sinusoid pos_embed) (modeling_finetune.py:181-190, 312-313)."""
 
@@ -344,16 +358,7 @@ class PatchEmbedFn(_Fn):
 
     @staticmethod
     def backward(ctx, dy):
-        (cols,) = ctx.saved_tensors
-        weight, bias = ctx.params
-        D = dy.shape[-1]
-        dyb = K.cast_bf16(_f32c(dy).reshape(-1, D))
-        kw = weight.numel() // weight.shape[0]
-        if cols.shape[1] != kw:  # padded K: the gradient of the padding columns is dropped (no in-place sink for a [D, ldk] result)
-            dWp, db = K.linear_bwd_weight(dyb, cols, want_bias=bias is not None)
-            return None, dWp[:, :kw].reshape(weight.shape), db, None, None, None
-        dW, db = linear_dw(dyb, cols, weight, bias)
-        return None, (None if dW is None else dW.reshape(weight.shape)), db, None, None, None
+        return (None,) + _patch_embed_backward(ctx, dy, 3)  # x | weight, bias | pos, tubelet, patch
 
 
 class PatchEmbedU8Fn(_Fn):
@@ -373,15 +378,7 @@ class PatchEmbedU8Fn(_Fn):
 
     @staticmethod
     def backward(ctx, dy):
-        (cols,) = ctx.saved_tensors
-        weight, bias = ctx.params
-        dyb = K.cast_bf16(_f32c(dy).reshape(-1, dy.shape[-1]))
-        kw = weight.numel() // weight.shape[0]
-        if cols.shape[1] != kw:  # padded K (see PatchEmbedFn.backward)
-            dWp, db = K.linear_bwd_weight(dyb, cols, want_bias=bias is not None)
-            return None, dWp[:, :kw].reshape(weight.shape), db, None, None, None, None, None, None, None
-        dW, db = linear_dw(dyb, cols, weight, bias)
-        return None, (None if dW is None else dW.reshape(weight.shape)), db, None, None, None, None, None, None, None
+        return (None,) + _patch_embed_backward(ctx, dy, 7)  # frames | weight, bias | pos, tubelet, patch, mean, std, bgr, t_offset
 
 
 class PatchEmbedWindowsFn(_Fn):
@@ -403,7 +400,7 @@ class PatchEmbedWindowsFn(_Fn):
 
     @staticmethod
     def backward(ctx, dy):
-        return (None,) + PatchEmbedU8Fn.backward(ctx, dy)[:-1]  # (store, idx | weight, bias, pos, tubelet, patch, mean, std, bgr)
+        return (None, None) + _patch_embed_backward(ctx, dy, 6)  # store, idx | weight, bias | pos, tubelet, patch, mean, std, bgr
 
 
 # --------------------------------------------------------------------------- attention / mlp cores (2-D tensors)

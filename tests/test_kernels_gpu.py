@@ -87,6 +87,49 @@ def test_im2col_index_bookkeeping_bit_exact(K, golden):
     assert torch.equal(cols.reshape(3, 8, 384), O.im2col_tubelets(x, 2, 8))
 
 
+# The im2col kernels launch at most 2048 blocks of 256 threads and walk further items in a grid-stride loop: the smallest shape at which each
+# instance makes a second trip, whole tensor against the CPU oracle, bit for bit.  (The 8-pixel uint8 kernels: tests/test_frame_store_gpu.py.)
+IM2COL_ONE_TRIP = 2048 * 256
+_BITS = {torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float32: torch.int32}
+
+
+def _assert_patch_matrix(cols, want, what):
+    """cols [B*N, ldk] (device) == want [B, N, K] (oracle, already in cols' dtype) bit for bit, padding columns exactly zero"""
+    Kd = want.shape[-1]
+    bits = cols.cpu().view(_BITS[cols.dtype])
+    assert cols.dtype == want.dtype and bits.shape[0] == want.shape[0] * want.shape[1] and bits.shape[1] >= Kd, what
+    assert torch.equal(bits[:, :Kd], want.reshape(-1, Kd).contiguous().view(_BITS[cols.dtype])), what
+    assert not bits[:, Kd:].any(), what + ": padding"
+
+
+@pytest.mark.parametrize("shape,patch,per,dtype", [
+    ((3, 3, 8, 256, 256), 16, 8, torch.bfloat16), ((3, 3, 8, 256, 256), 16, 8, torch.float16), ((3, 3, 4, 256, 256), 16, 4, torch.float32),
+    ((1, 3, 10, 196, 196), 14, 2, torch.bfloat16), ((1, 3, 10, 196, 196), 14, 2, torch.float16), ((1, 3, 10, 196, 196), 14, 2, torch.float32)],
+    ids=["wide-bf16", "wide-f16", "wide-f32", "pairs-bf16", "pairs-f16", "pairs-f32"])
+def test_im2col_f32_source_second_grid_stride_trip(K, shape, patch, per, dtype):
+    assert math.prod(shape) // per > IM2COL_ONE_TRIP
+    x = torch.randn(shape, generator=torch.Generator().manual_seed(11))
+    cols = K.im2col_tubelets_f32(dev(x), 2, patch) if dtype == torch.float32 else K.im2col_tubelets(dev(x), 2, patch, dtype=dtype)
+    assert (cols.shape[1] > 3 * 2 * patch * patch) == (patch == 14)
+    _assert_patch_matrix(cols, O.im2col_tubelets(x.to(dtype), 2, patch), f"{shape} /{patch} {dtype}")
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
+@pytest.mark.parametrize("policy", ["ring", "table"])
+def test_im2col_u8_pairs_second_grid_stride_trip(K, policy, dtype):
+    B, T, HW, mean, std = 7, 4, 196, (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+    assert B * T * HW * HW // 2 > IM2COL_ONE_TRIP
+    frames = torch.randint(0, 256, (B, T, HW, HW, 3), generator=torch.Generator().manual_seed(12), dtype=torch.uint8)
+    want = O.im2col_tubelets(O.tensor_normalize(frames, mean, std).permute(0, 4, 1, 2, 3), 2, 14).to(dtype)
+    if policy == "ring":  # slot (t + 1) % T of a clip holds its frame t
+        cols = K.im2col_tubelets_u8(dev(torch.roll(frames, shifts=1, dims=1)), 2, 14, mean, std, t_offset=1, dtype=dtype)
+    else:                 # identity slots over the same frames
+        idx = torch.arange(B * T, dtype=torch.int32).reshape(B, T)
+        cols = K.im2col_frame_windows(dev(frames.reshape(B * T, HW, HW, 3)), dev(idx), 2, 14, mean, std, dtype=dtype)
+    assert cols.shape[1] == 1216
+    _assert_patch_matrix(cols, want, f"u8 {policy} {dtype}")
+
+
 def test_patch_embed_fwd(K):
     x = R.tensor_for("pe.x", (1, 3, 4, 32, 32))
     w = R.tensor_for("pe.w", (64, 3, 2, 16, 16), scale=0.02)

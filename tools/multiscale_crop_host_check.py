@@ -97,9 +97,11 @@ def build(workdir):
     with open(KERNEL) as f:
         src = f.read()
     body = src[src.index("constexpr int MC_THREADS"):src.index("TAD_NAMESPACE_END")]
+    with open(os.path.join(os.path.dirname(KERNEL), "common.h")) as f:  # the one helper of common.h the kernel calls, in its own text too
+        normalize = next(line for line in f if "float normalize_u8(" in line)
     cpp, exe = os.path.join(workdir, "msc_host.cpp"), os.path.join(workdir, "msc_host")
     with open(cpp, "w") as f:
-        f.write(SHIM + body + MAIN)
+        f.write(SHIM + normalize + body + MAIN)
     subprocess.run([compiler(), "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, cpp],
                    check=True)
     return exe
