@@ -577,6 +577,66 @@ int tad_multiscale_crop_plan_check(const int32_t* table_host, int64_t n_words, i
 int tad_multiscale_crop(const uint8_t* x, void* out, int out_f32, const float* mean, const float* std_, const void* workspace,
                         size_t workspace_bytes, int B, int T, int Hs, int Ws, int S_h, int S_w, int n_hsets, int n_vsets, tad_stream_t stream);
 
+/* The loader resize of the fine-tune and inference paths on the device: cv2.resize(frame, (S_w, S_h), INTER_CUBIC) of every decoded
+ * frame (run_inference.py:76,91; dota.py:347-348; dada.py:309-310), optionally behind video_transforms.pad_wide_clips (:1301-1337),
+ * on uint8 frames [B,T,H,W,3]; all clips of a call share one source size.
+ * THE CONTRACT is OpenCV's generic integer formulation of the 8-bit cubic resize as stated here, not the bytes of a particular OpenCV
+ * build: a build's vector path finishes the vertical pass in float, its scalar path in integers, the two can differ by one grey
+ * level, and which bytes take which path depends on the build and the row width.  The tests hold the kernel to a CPU restatement of
+ * this text bit for bit, and that restatement to an independent float64 bicubic within one grey level.
+ * Per axis, on the HOST (numpy float32 / float64; the device sees integers only), source extent n_src, output extent n_dst:
+ *   scale = n_src / n_dst                           a double
+ *   f = float32((d + 0.5) * scale - 0.5)            the double expression, rounded once
+ *   s = floor(f);  x = float32(f - s)
+ *   Keys' cubic weights, A = -0.75f, every operation in float32:
+ *     c0 = ((A*(x+1) - 5A)*(x+1) + 8A)*(x+1) - 4A;   c1 = ((A+2)*x - (A+3))*x*x + 1
+ *     c2 = ((A+2)*(1-x) - (A+3))*(1-x)*(1-x) + 1;    c3 = 1 - c0 - c1 - c2
+ *   k[j] = saturate_int16(rint(c_j * 2048f)), ties to even.  The four k are NOT renormalised: their sum is 2047, 2048 or 2049, and
+ *   sum |k| <= TAD_FR_MAX_ABS_SUM.  first = s - 1; the taps are source indices first .. first + 3, each clamped to [0, n_src - 1]
+ *   (replicate border) ON THE DEVICE: first lies in [-2, n_src - 2].  Equal extents give k = (0, 2048, 0, 0): output == input.
+ * On the device, two passes in int32 with no rounding in between:
+ *   h[row][d] = sum_j src[row][tap_j] * kx[d][j]
+ *   byte      = clip((sum_j h[tap_j][d] * ky[r][j] + (1 << 21)) >> 22, 0, 255)        arithmetic shift
+ *   (255 * 2818 * 2818 + 2^21 < 2^31)
+ * Wide-clip padding is a VIRTUAL source of pad_top + H + pad_bottom rows that the vertical pass indexes; no padded frame exists.
+ * Virtual row v inside the frame (pad_top <= v < pad_top + H) is the frame's row in every mode; a band row is, per mode:
+ *   TAD_FR_CONST      every byte of stored channel c is (colour >> 8c) & 255 (black: colour = 0)
+ *   TAD_FR_REPLICATE  frame row 0 (top band) or H - 1 (bottom band)
+ *   TAD_FR_REFLECT    top band row v = frame row pad_top - 1 - v, the j-th row of the bottom band = frame row H - 1 - j (cv2's
+ *                     BORDER_REFLECT: the edge row doubled), each byte faded to rint((float)p * alpha), ties to even, the product
+ *                     on its own: cv2.addWeighted(reflect, a, black, 1 - a, 0), which inside the frame returns the byte itself
+ *   A pad above H would need a second reflection and is refused.
+ * table: int32, three parts in this order:
+ *   rows    [B][TAD_FR_ROW_WORDS], one per clip (every sample exactly once):
+ *           {sample, mode, pad_top, pad_bottom, alpha (f32 bits), colour (c0 | c1 << 8 | c2 << 16), vset, 0}
+ *   hset    ONE horizontal set of TAD_FR_SET_HEAD + S_w * 5 words (W -> S_w)
+ *   vsets   [n_vsets] vertical sets of TAD_FR_SET_HEAD + S_h * 5 words, one per distinct virtual height (pad_top + H + pad_bottom -> S_h)
+ *   a set = {in, out, 0, 0}, first[out], k[out][4]
+ * tad_frame_resize_workspace_bytes: the size of the table = of the workspace, which holds nothing else and is only read.
+ * tad_frame_resize_plan_check: host-side check of a HOST copy of the table (n_words = its length, which must be the sum of the three
+ *   parts; 0 <= sample < B exactly once; a known mode; 0 <= pad <= H, both 0 under TAD_FR_NONE; alpha in [0, 1] under REFLECT; vset in
+ *   range and stated for the row's virtual height; the horizontal set stated for W; first in [-2, in - 2]; sum |k| <=
+ *   TAD_FR_MAX_ABS_SUM); no launch.
+ * tad_frame_resize: ONE launch, no host synchronisation; x is only read.  out_f32 == 0: out = uint8 [B,T,S_h,S_w,3], any alignment
+ *   (a slot of a ring buffer, a slice of a frame store); mean / std_ are ignored.  out_f32 != 0: out = f32 [B,3,T,S_h,S_w] =
+ *   ((float)byte / 255 - mean[c]) / std_[c], the bits tad_frames_to_clip gives on the uint8 result; mean / std_: 3 host floats.
+ *   workspace = the table on the device.  On the device the mode is cut to the known modes, a pad to [0, H], a set index to the sets,
+ *   every tap to its source, a faded byte to [0, 255], and a row whose sample is outside the batch is ignored (a malformed table is
+ *   never an address); a clip that no row names is left unwritten.  Source pixels are loaded as the aligned 4-byte words that hold
+ *   them: up to three bytes to either side of x share a word with its first / last pixel and are loaded and dropped. */
+#define TAD_FR_ROW_WORDS 8
+#define TAD_FR_SET_HEAD 4
+#define TAD_FR_MAX_SETS 64
+#define TAD_FR_MAX_ABS_SUM 2818
+#define TAD_FR_NONE 0
+#define TAD_FR_CONST 1
+#define TAD_FR_REFLECT 2
+#define TAD_FR_REPLICATE 3
+size_t tad_frame_resize_workspace_bytes(int B, int n_vsets, int S_h, int S_w);
+int tad_frame_resize_plan_check(const int32_t* table_host, int64_t n_words, int B, int n_vsets, int H, int W, int S_h, int S_w);
+int tad_frame_resize(const uint8_t* x, void* out, int out_f32, const float* mean, const float* std_, const void* workspace,
+                     size_t workspace_bytes, int B, int T, int H, int W, int S_h, int S_w, int n_vsets, tad_stream_t stream);
+
 /* The spatial sampling of the class fine-tuning recipe on the device (kinetics.py / ssv2.py of the reference: spatial_sampling, i.e.
  * video_transforms.random_resized_crop, random_resized_crop_with_shift, or random_short_side_scale_jitter + random_crop, then
  * horizontal_flip; with spatial_idx 0 / 1 / 2 the jitter + uniform_crop).  Every route is: a window of the source frame, a bilinear

@@ -82,6 +82,9 @@ SIGNATURES = {
     "tad_multiscale_crop_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "tad_multiscale_crop_plan_check": (_i, [_vp, _i64, _i, _i, _i, _i, _i, _i, _i]),
     "tad_multiscale_crop": (_i, [_vp, _vp, _i, C.POINTER(_f), C.POINTER(_f), _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "tad_frame_resize_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "tad_frame_resize_plan_check": (_i, [_vp, _i64, _i, _i, _i, _i, _i, _i]),
+    "tad_frame_resize": (_i, [_vp, _vp, _i, C.POINTER(_f), C.POINTER(_f), _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "tad_spatial_sample_workspace_bytes": (_sz, [_i, _i]),
     "tad_spatial_sample_plan_check": (_i, [_vp, _i64, _i, _i, _i, _i, _i]),
     "tad_spatial_sample": (_i, [_vp, _i, _vp, C.POINTER(_f), C.POINTER(_f), _vp, _sz, _i, _i, _i, _i, _i, _vp]),
@@ -147,6 +150,8 @@ RANDAUG_MAX_LAYERS = 32
 RA_STATS_OPS = (RA_AUTOCONTRAST, RA_EQUALIZE, RA_CONTRAST)
 MSC_ROW_WORDS, MSC_SET_HEAD, MSC_MAX_KSIZE, MSC_MAX_SETS = 8, 4, 17, 64
 SS_ROW_WORDS = 12
+FR_ROW_WORDS, FR_SET_HEAD, FR_MAX_SETS, FR_MAX_ABS_SUM = 8, 4, 64, 2818
+FR_NONE, FR_CONST, FR_REFLECT, FR_REPLICATE = range(4)
 SEGNORM_WORK_MAX = 16384  # TAD_SEGNORM_WORK_MAX: the longest work item of tad_grad_segnorm, in floats
 SEGNORM_DEPTH = 17  # the longest chain of f32 additions behind one element's square (csrc/grad_segnorm.hip, "depth")
 POOL_SPLIT = 8

@@ -18,7 +18,7 @@ _LIB_NAME = os.environ.get("TAD_BUILD_LIB", "libtad_ablation.so" if _ABLATION el
 EXP_DIR = os.path.join(os.path.dirname(HERE), "build_exp")
 _PRODUCTION = _LIB_NAME == "libtad_mi355x.so"
 LIB = os.path.join(HERE if _PRODUCTION else EXP_DIR, os.path.basename(_LIB_NAME))
-SOURCES = ["capi.hip", "elementwise.hip", "patch_embed.hip", "layernorm.hip", "gemm.hip", "gemm_plan.hip", "gemm_w4.hip", "attn_fwd.hip", "attn_bwd.hip", "attn_plan.hip", "attn_f32.hip", "precise.hip", "optim.hip", "ema.hip", "mixup.hip", "frame_loss.hip", "erasing.hip", "randaug.hip", "multiscale_crop.hip", "spatial_sample.hip", "mae.hip", "metrics.hip", "grad_segnorm.hip", "collective.hip", "im2col.hip"]
+SOURCES = ["capi.hip", "elementwise.hip", "patch_embed.hip", "layernorm.hip", "gemm.hip", "gemm_plan.hip", "gemm_w4.hip", "attn_fwd.hip", "attn_bwd.hip", "attn_plan.hip", "attn_f32.hip", "precise.hip", "optim.hip", "ema.hip", "mixup.hip", "frame_loss.hip", "erasing.hip", "randaug.hip", "multiscale_crop.hip", "frame_resize.hip", "spatial_sample.hip", "mae.hip", "metrics.hip", "grad_segnorm.hip", "collective.hip", "im2col.hip"]
 # Sources that touch 16-bit GEMM / attention operands are compiled a second time with -DTAD_OPND_F16: the same kernels for IEEE half
 # operands, exported as tad_*_f16 (csrc/common.h, csrc/opnd_f16_names.h; include/tad_mi355x.h "IEEE half operand twins").
 F16_SOURCES = ["elementwise.hip", "patch_embed.hip", "layernorm.hip", "gemm.hip", "gemm_w4.hip", "attn_fwd.hip", "attn_bwd.hip", "optim.hip"]
@@ -33,8 +33,9 @@ EXTRA_DEPS = {"gemm.hip": ["gemm_kernels.h", "gemm_plan.h"], "gemm_w4.hip": ["ge
 # randaug.hip must round like PIL's C code (a float blend, a double affine map and cubic: each product and sum on its own).
 # multiscale_crop.hip writes the same normalised f32 values as randaug.hip's frames_to_clip and takes the same flags.
 # spatial_sample.hip must round its bilinear blend like the arithmetic include/tad_mi355x.h states (every product and sum on its own).
+# frame_resize.hip fades a reflected pad band with one f32 product rounded on its own (cv2.addWeighted) and writes frames_to_clip's f32 values.
 # A `#pragma clang fp contract(off)` is not enough: -ffp-contract=fast also lets the code generator fuse fmul + fadd by itself.
-NO_FP_CONTRACT = {"ema.hip", "mixup.hip", "randaug.hip", "multiscale_crop.hip", "spatial_sample.hip"}
+NO_FP_CONTRACT = {"ema.hip", "mixup.hip", "randaug.hip", "multiscale_crop.hip", "spatial_sample.hip", "frame_resize.hip"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wno-unused-result",
          # keep MFMA accumulators in the (unified) VGPR file: without it the compiler parks them in AGPRs and pays a
          # v_accvgpr_read/write per element around every softmax / epilogue

@@ -1,0 +1,333 @@
+// The loader resize of the fine-tune and inference paths on the device: cv2.resize(frame, (S_w, S_h), INTER_CUBIC) of every decoded
+// frame (run_inference.py:76,91; dota.py:347-348; dada.py:309-310), and video_transforms.pad_wide_clips (:1301-1337), which pads a wide
+// frame at top and bottom before that resize.  The host states the per-axis taps and coefficients (simple_tad_amd/frame_resize.py);
+// this file carries them out on uint8 frames [B, T, H, W, 3] in ONE launch, into uint8 frames [B, T, S_h, S_w, 3] (any alignment: a
+// slot of a ring, a slice of a frame store) or straight into the normalised f32 clip [B, 3, T, S_h, S_w].
+//
+// Table (int32, include/tad_mi355x.h documents the words): B rows {sample, mode, pad_top, pad_bottom, alpha bits, packed colour, vset,
+// 0}, one horizontal set and n_vsets vertical sets, each {in, out, 0, 0}, first[out], k[out][4].  The table is only read.
+//
+// Arithmetic -- the contract: OpenCV's GENERIC INTEGER formulation of the 8-bit cubic resize, not the bytes of one OpenCV build (the
+// vector path of a build finishes the vertical pass in float and can differ from this by one grey level).  Per output four taps
+// first .. first + 3, each clamped to the source (replicate border), 11-bit coefficients that are NOT renormalised; two passes in
+// int32 with no rounding in between:
+//   h[row][d] = sum_j src[row][tap_j] * kx[d][j];      byte = clip((sum_j h[tap_j][d] * ky[r][j] + (1 << 21)) >> 22, 0, 255)
+// 255 * 2818 * 2818 + 2^21 < 2^31 (sum |k| <= 2818 per output, which tad_frame_resize_plan_check holds the table to).  All float work
+// (the sample positions, Keys' weights with A = -0.75, their rounding) stays on the host.
+//
+// Padding is a VIRTUAL source of pad_top + H + pad_bottom rows that the vertical taps index; no padded frame exists.  The horizontal
+// pass maps each virtual row it needs to a frame row (reflect, replicate), or to the band's colour.  A reflected band byte is faded
+// towards black: rint((float)p * alpha), the product on its own -- cv2.addWeighted(reflect, a, black, 1 - a, 0) in float; the file is
+// compiled without floating-point contraction (build.py).  The fused f32 value is frames_to_clip's: normalize_u8 (common.h).
+//
+// Shape: a workgroup of 256 threads owns FR_TR x FR_TC outputs of one frame.  It stages the tile's taps and coefficients in LDS, runs
+// the horizontal pass over the virtual rows the tile's vertical taps name into int32 LDS planes (one per row and channel), then the
+// vertical pass out of LDS.  The rows are held densely (slot = row - lowest row) when the taps of the tile span at most 4 rows per
+// output row -- upscales and shrinks up to 4 -- and as four slots per output row otherwise, so only rows under taps are ever read.
+// The four pixels under an output's horizontal taps are 12 contiguous bytes at no particular alignment (W * 3 breaks every one): they come
+// in as aligned words and a funnel shift (fr_load12); where a tap clamps at a border, byte by byte.  A thread's outputs in the vertical
+// pass are four neighbouring columns.
+#include "common.h"
+#include <math.h>
+#include <string.h>
+#include <type_traits>
+
+TAD_NAMESPACE_BEGIN
+
+constexpr int FR_THREADS = 256;
+constexpr int FR_TR = 32, FR_TC = 32;                    // output rows x columns of a tile: FR_TR * FR_TC / 4 = FR_THREADS
+constexpr int FR_CG = FR_TC / 4;                         // column groups of four per tile row
+constexpr int FR_SLOTS = 4 * FR_TR;                      // virtual rows a tile can need: four taps per output row
+static_assert(FR_TR * FR_CG == FR_THREADS, "tile shape");
+static_assert(FR_SLOTS * 3 * FR_TC * 4 + (FR_TC + FR_TR) * 5 * 4 <= 64 * 1024, "static LDS stays at or below 64 KB");
+
+struct FrNorm {
+  float mean[3], sd[3];
+};
+
+__host__ __device__ __forceinline__ int64_t fr_set_words(int out) { return TAD_FR_SET_HEAD + (int64_t)out * 5; }
+__host__ __device__ __forceinline__ int64_t fr_table_words(int B, int nv, int Sh, int Sw) {
+  return (int64_t)B * TAD_FR_ROW_WORDS + fr_set_words(Sw) + nv * fr_set_words(Sh);
+}
+__device__ __forceinline__ int fr_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ __forceinline__ uint32_t fr_clip8(int ss) { return (uint32_t)fr_clamp(ss >> 22, 0, 255); }
+
+// a reflected band byte faded towards black: rint((float)p * alpha), the product on its own, cut to a byte
+__device__ __forceinline__ int fr_fade(int b, float alpha) { return fr_clamp(__float2int_rn(__fmul_rn((float)b, alpha)), 0, 255); }
+
+// the 12 bytes from p (any alignment) as three words: aligned 4-byte loads and a funnel shift.  Only the aligned words that hold one of
+// the 12 bytes are loaded -- three when p is aligned, else four -- so no load leaves the pages of the bytes asked for; the up to three
+// bytes to either side that share a word with them are shifted out
+__device__ __forceinline__ void fr_load12(const uint8_t* p, uint32_t w[3]) {
+  const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3);
+  const uint32_t* q = static_cast<const uint32_t*>(__builtin_assume_aligned(p - sh, 4));  // (derived from p: stays a global pointer)
+  const uint32_t d0 = q[0], d1 = q[1], d2 = q[2], d3 = sh ? q[3] : 0u;
+  w[0] = __builtin_amdgcn_alignbyte(d1, d0, sh);
+  w[1] = __builtin_amdgcn_alignbyte(d2, d1, sh);
+  w[2] = __builtin_amdgcn_alignbyte(d3, d2, sh);
+}
+
+// first tap and coefficients of `n` outputs from output `o0` of a set, staged in LDS (slots past n: tap 0, coefficients 0)
+__device__ __forceinline__ void fr_stage(const int32_t* __restrict__ set, int out_size, int o0, int n, int* first, int (*kk)[4], int slots) {
+  const int32_t* f = set + TAD_FR_SET_HEAD;
+  const int32_t* k = f + out_size;
+  for (int i = threadIdx.x; i < slots * 5; i += FR_THREADS) {
+    const int o = i / 5, j = i - o * 5;
+    if (j == 4)
+      first[o] = o < n ? f[o0 + o] : 0;
+    else
+      kk[o][j] = o < n ? k[(int64_t)(o0 + o) * 4 + j] : 0;
+  }
+}
+
+template <bool F32>
+__global__ __launch_bounds__(FR_THREADS) void frame_resize_kernel(const uint8_t* __restrict__ x, void* __restrict__ out,
+                                                                 const int32_t* __restrict__ tab, FrNorm nm, int B, int T, int H, int W, int Sh,
+                                                                 int Sw, int nv, int tiles_x) {
+  __shared__ __attribute__((aligned(16))) int hp[FR_SLOTS][3][FR_TC];  // (read back four columns at a time)
+  __shared__ int hf[FR_TC], hk[FR_TC][4], vf[FR_TR], vk[FR_TR][4];
+  const int32_t* r = tab + (int64_t)blockIdx.z * TAD_FR_ROW_WORDS;
+  const int sample = r[0];
+  if (sample < 0 || sample >= B) return;  // (the same for every thread of the workgroup)
+  const int t = blockIdx.y, tid = threadIdx.x;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  // mode and pads cut to what the frame allows, the set index to the sets: a malformed table is never an address
+  const int mode = fr_clamp(r[1], TAD_FR_NONE, TAD_FR_REPLICATE);
+  const int pt = mode == TAD_FR_NONE ? 0 : fr_clamp(r[2], 0, H), pb = mode == TAD_FR_NONE ? 0 : fr_clamp(r[3], 0, H);
+  const float alpha = __int_as_float(r[4]);
+  const uint32_t colour = (uint32_t)r[5];
+  const int Hv = pt + H + pb;
+  const int32_t* hset = tab + (int64_t)B * TAD_FR_ROW_WORDS;
+  const int32_t* vset = hset + fr_set_words(Sw) + fr_clamp(r[6], 0, nv - 1) * fr_set_words(Sh);
+  const int c0 = tx * FR_TC, o0 = ty * FR_TR;
+  const int nc = Sw - c0 < FR_TC ? Sw - c0 : FR_TC, nr = Sh - o0 < FR_TR ? Sh - o0 : FR_TR;
+  fr_stage(hset, Sw, c0, nc, hf, hk, FR_TC);
+  fr_stage(vset, Sh, o0, nr, vf, vk, FR_TR);
+  __syncthreads();
+
+  // the virtual rows under the tile's vertical taps: [lo, hi], held densely when that is no more rows than four per output row
+  int lo = Hv - 1, hi = 0;
+  for (int i = 0; i < nr; ++i) {
+    const int a = fr_clamp(vf[i], 0, Hv - 1), b = fr_clamp(vf[i] + 3, 0, Hv - 1);
+    lo = a < lo ? a : lo, hi = b > hi ? b : hi;
+  }
+  const bool dense = hi - lo + 1 <= 4 * nr;
+  const int nslots = dense ? hi - lo + 1 : 4 * nr;
+
+  // horizontal pass: an item is one column of one virtual row, all three channels; a thread keeps its column and walks the rows.  The
+  // fade of a reflected band is compiled into the pass of the clips that reflect alone (the mode is the workgroup's)
+  const uint8_t* frame = x + ((int64_t)sample * T + t) * H * W * 3;
+  auto hpass = [&](auto reflect) {
+    constexpr bool REFLECT = decltype(reflect)::value;
+    const int c = tid & (FR_TC - 1);
+    if (c >= nc) return;
+    for (int slot = tid / FR_TC; slot < nslots; slot += FR_THREADS / FR_TC) {
+      const int v = dense ? lo + slot : fr_clamp(vf[slot >> 2] + (slot & 3), 0, Hv - 1);
+      // the row map: inside the frame the row itself; in a band its mirror image (faded), the edge row, or the colour
+      int fr = v - pt;
+      bool band = false;
+      if (v < pt) {
+        band = true;
+        fr = REFLECT ? pt - 1 - v : 0;
+      } else if (v >= pt + H) {
+        band = true;
+        fr = REFLECT ? H - 1 - (v - pt - H) : H - 1;
+      }
+      fr = fr_clamp(fr, 0, H - 1);
+      const bool constant = band && mode == TAD_FR_CONST, fade = REFLECT && band;
+      const uint8_t* row = frame + (int64_t)fr * W * 3;
+      int acc[3] = {0, 0, 0};
+      const int f0 = hf[c];
+      if (!constant && f0 >= 0 && f0 + 3 <= W - 1) {  // no tap clamps: the four pixels are 12 contiguous bytes
+        uint32_t w[3];
+        fr_load12(row + (int64_t)f0 * 3, w);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int k = hk[c][j];
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) {
+            int b = (int)((w[(3 * j + ch) >> 2] >> (((3 * j + ch) & 3) * 8)) & 255u);
+            if (fade) b = fr_fade(b, alpha);
+            acc[ch] += b * k;
+          }
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int k = hk[c][j];
+          const uint8_t* p = row + (int64_t)fr_clamp(f0 + j, 0, W - 1) * 3;
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) {
+            int b = constant ? (int)((colour >> (8 * ch)) & 255u) : (int)p[ch];
+            if (fade) b = fr_fade(b, alpha);
+            acc[ch] += b * k;
+          }
+        }
+      }
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) hp[slot][ch][c] = acc[ch];
+    }
+  };
+  if (mode == TAD_FR_REFLECT)
+    hpass(std::true_type{});
+  else
+    hpass(std::false_type{});
+  __syncthreads();
+
+  // vertical pass: a thread owns four columns of one output row, all three channels
+  const int orow = tid / FR_CG, cg = tid - orow * FR_CG;
+  const int col = c0 + cg * 4, valid = Sw - col < 4 ? Sw - col : 4;
+  if (orow >= nr || valid <= 0) return;
+  int acc[3][4];
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[ch][q] = 1 << 21;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int v = fr_clamp(vf[orow] + j, 0, Hv - 1);
+    const int slot = fr_clamp(dense ? v - lo : orow * 4 + j, 0, FR_SLOTS - 1);
+    const int k = vk[orow][j];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const int4 h = *reinterpret_cast<const int4*>(&hp[slot][ch][cg * 4]);
+      acc[ch][0] += h.x * k, acc[ch][1] += h.y * k, acc[ch][2] += h.z * k, acc[ch][3] += h.w * k;
+    }
+  }
+  const int oy = o0 + orow;
+  if (F32) {
+    float* o = static_cast<float*>(out) + (((int64_t)sample * 3 * T + t) * Sh + oy) * Sw + col;  // channel ch: + ch * T * Sh * Sw
+    const int64_t plane = (int64_t)T * Sh * Sw;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      float v[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = normalize_u8((float)fr_clip8(acc[ch][q]), nm.mean[ch], nm.sd[ch]);
+      float* oc = o + ch * plane;
+      if (valid == 4 && (reinterpret_cast<uintptr_t>(oc) & 15) == 0) {
+        *reinterpret_cast<float4*>(oc) = make_float4(v[0], v[1], v[2], v[3]);
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (q < valid) oc[q] = v[q];
+      }
+    }
+  } else {
+    uint8_t* o = static_cast<uint8_t*>(out) + ((((int64_t)sample * T + t) * Sh + oy) * Sw + col) * 3;
+    uint32_t pk[3] = {0, 0, 0};
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) pk[(3 * q + ch) >> 2] |= fr_clip8(acc[ch][q]) << (((3 * q + ch) & 3) * 8);
+    if (valid == 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) reinterpret_cast<uint32_t*>(o)[i] = pk[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 12; ++i)
+        if (i < 3 * valid) o[i] = (uint8_t)(pk[i >> 2] >> ((i & 3) * 8));
+    }
+  }
+}
+
+TAD_NAMESPACE_END
+
+using namespace tad;
+
+static int fr_shape_ok(int B, int nv, int H, int W, int Sh, int Sw, const char* who) {
+  TAD_REQUIRE(B > 0 && B <= 65535, "%s: B=%d must be in [1, 65535]", who, B);
+  TAD_REQUIRE(nv > 0 && nv <= TAD_FR_MAX_SETS, "%s: n_vsets=%d must be in [1, %d]", who, nv, TAD_FR_MAX_SETS);
+  TAD_REQUIRE(H > 0 && W > 0 && (int64_t)H * W <= ((int64_t)1 << 28), "%s: H=%d W=%d: a frame must have 1 .. 2^28 pixels", who, H, W);
+  TAD_REQUIRE(Sh > 0 && Sw > 0 && Sh <= 16384 && Sw <= 16384, "%s: S_h=%d S_w=%d must be in [1, 16384]", who, Sh, Sw);
+  return TAD_OK;
+}
+
+extern "C" size_t tad_frame_resize_workspace_bytes(int B, int n_vsets, int S_h, int S_w) {
+  if (B <= 0 || n_vsets <= 0 || S_h <= 0 || S_w <= 0) return 0;
+  return (size_t)fr_table_words(B, n_vsets, S_h, S_w) * 4;
+}
+
+static int fr_check_set(const int32_t* set, int out_size, const char* axis, int index) {
+  const int in = set[0];
+  TAD_REQUIRE(set[1] == out_size, "frame_resize_plan_check: %s set %d: output extent %d, expected %d", axis, index, set[1], out_size);
+  const int32_t* f = set + TAD_FR_SET_HEAD;
+  const int32_t* k = f + out_size;
+  for (int o = 0; o < out_size; ++o) {
+    // s = first + 1 = floor of a sample position that lies within half a source step of the source: s in [-1, in - 1]
+    TAD_REQUIRE(f[o] >= -2 && f[o] <= in - 2, "frame_resize_plan_check: %s set %d: output %d has its taps at [%d, %d], outside the %d samples of the source",
+                axis, index, o, f[o], f[o] + 3, in);
+    int64_t mag = 0;
+    for (int j = 0; j < 4; ++j) mag += k[4 * o + j] < 0 ? -(int64_t)k[4 * o + j] : (int64_t)k[4 * o + j];
+    TAD_REQUIRE(mag <= TAD_FR_MAX_ABS_SUM, "frame_resize_plan_check: %s set %d: output %d: sum |k| = %lld is above %d (the int32 passes would overflow)",
+                axis, index, o, (long long)mag, TAD_FR_MAX_ABS_SUM);
+  }
+  return TAD_OK;
+}
+
+extern "C" int tad_frame_resize_plan_check(const int32_t* table_host, int64_t n_words, int B, int n_vsets, int H, int W, int S_h, int S_w) {
+  TAD_REQUIRE(table_host, "frame_resize_plan_check: null pointer");
+  if (int rc = fr_shape_ok(B, n_vsets, H, W, S_h, S_w, "frame_resize_plan_check")) return rc;
+  const int64_t want = fr_table_words(B, n_vsets, S_h, S_w);
+  TAD_REQUIRE(n_words == want, "frame_resize_plan_check: %lld words, expected B * %d + the sets = %lld", (long long)n_words, TAD_FR_ROW_WORDS,
+              (long long)want);
+  const int32_t* hset = table_host + (int64_t)B * TAD_FR_ROW_WORDS;
+  TAD_REQUIRE(hset[0] == W, "frame_resize_plan_check: horizontal set: input extent %d, the source has %d columns", hset[0], W);
+  if (int rc = fr_check_set(hset, S_w, "horizontal", 0)) return rc;
+  const int32_t* vsets = hset + fr_set_words(S_w);
+  for (int i = 0; i < n_vsets; ++i) {
+    const int32_t* set = vsets + i * fr_set_words(S_h);
+    TAD_REQUIRE(set[0] >= H && (int64_t)set[0] <= (int64_t)3 * H,
+                "frame_resize_plan_check: vertical set %d: virtual height %d is not the %d rows of the source plus two pads of at most %d", i, set[0], H, H);
+    if (int rc = fr_check_set(set, S_h, "vertical", i)) return rc;
+  }
+  uint64_t seen[1024] = {0};  // (B <= 65535)
+  for (int k = 0; k < B; ++k) {
+    const int32_t* r = table_host + (int64_t)k * TAD_FR_ROW_WORDS;
+    const int sample = r[0], mode = r[1], pt = r[2], pb = r[3], vs = r[6];
+    TAD_REQUIRE(0 <= sample && sample < B, "frame_resize_plan_check: row %d: sample=%d outside the batch B=%d", k, sample, B);
+    TAD_REQUIRE(!(seen[sample >> 6] >> (sample & 63) & 1), "frame_resize_plan_check: row %d: sample=%d has two rows", k, sample);
+    seen[sample >> 6] |= (uint64_t)1 << (sample & 63);
+    TAD_REQUIRE(mode >= TAD_FR_NONE && mode <= TAD_FR_REPLICATE, "frame_resize_plan_check: row %d: unknown mode %d", k, mode);
+    TAD_REQUIRE(pt >= 0 && pb >= 0, "frame_resize_plan_check: row %d: negative pad (%d, %d)", k, pt, pb);
+    TAD_REQUIRE(pt <= H && pb <= H, "frame_resize_plan_check: row %d: pad (%d, %d) is greater than H=%d (a second reflection is not built)", k, pt, pb, H);
+    TAD_REQUIRE(mode != TAD_FR_NONE || (pt == 0 && pb == 0), "frame_resize_plan_check: row %d: mode none with pads (%d, %d)", k, pt, pb);
+    if (mode == TAD_FR_REFLECT) {
+      float a;
+      memcpy(&a, &r[4], 4);
+      TAD_REQUIRE(std::isfinite(a) && a >= 0.0f && a <= 1.0f, "frame_resize_plan_check: row %d: alpha=%g must be in [0, 1]", k, (double)a);
+    }
+    TAD_REQUIRE((r[5] & ~0xffffff) == 0, "frame_resize_plan_check: row %d: colour word 0x%x holds more than three bytes", k, (unsigned)r[5]);
+    TAD_REQUIRE(0 <= vs && vs < n_vsets, "frame_resize_plan_check: row %d: vertical set %d outside [0, %d)", k, vs, n_vsets);
+    TAD_REQUIRE(vsets[vs * fr_set_words(S_h)] == pt + H + pb, "frame_resize_plan_check: row %d: its vertical set is stated for %d rows, the padded frame has %d",
+                k, vsets[vs * fr_set_words(S_h)], pt + H + pb);
+  }
+  return TAD_OK;
+}
+
+extern "C" int tad_frame_resize(const uint8_t* x, void* out, int out_f32, const float* mean, const float* std_, const void* workspace,
+                                size_t workspace_bytes, int B, int T, int H, int W, int S_h, int S_w, int n_vsets, tad_stream_t stream) {
+  TAD_REQUIRE(x && out && workspace, "frame_resize: null pointer");
+  if (int rc = fr_shape_ok(B, n_vsets, H, W, S_h, S_w, "frame_resize")) return rc;
+  TAD_REQUIRE(T > 0 && T <= 65535, "frame_resize: T=%d must be in [1, 65535]", T);
+  TAD_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "frame_resize: workspace must be 4-byte aligned");
+  TAD_REQUIRE(workspace_bytes >= tad_frame_resize_workspace_bytes(B, n_vsets, S_h, S_w), "frame_resize: workspace of %zu bytes, need %zu",
+              workspace_bytes, tad_frame_resize_workspace_bytes(B, n_vsets, S_h, S_w));
+  FrNorm nm = {{0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}};
+  if (out_f32) {
+    TAD_REQUIRE(mean && std_, "frame_resize: the f32 output needs mean and std");
+    TAD_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "frame_resize: an f32 out must be 4-byte aligned");
+    for (int c = 0; c < 3; ++c) {
+      TAD_REQUIRE(std::isfinite(mean[c]) && std::isfinite(std_[c]) && std_[c] != 0.0f, "frame_resize: mean / std of channel %d", c);
+      nm.mean[c] = mean[c], nm.sd[c] = std_[c];
+    }
+  }
+  const int tiles_x = (S_w + FR_TC - 1) / FR_TC, tiles_y = (S_h + FR_TR - 1) / FR_TR;
+  const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)T, (unsigned)B);
+  const int32_t* tab = static_cast<const int32_t*>(workspace);
+  hipStream_t s = (hipStream_t)stream;
+  if (out_f32)
+    hipLaunchKernelGGL(frame_resize_kernel<true>, grid, dim3(FR_THREADS), 0, s, x, out, tab, nm, B, T, H, W, S_h, S_w, n_vsets, tiles_x);
+  else
+    hipLaunchKernelGGL(frame_resize_kernel<false>, grid, dim3(FR_THREADS), 0, s, x, out, tab, nm, B, T, H, W, S_h, S_w, n_vsets, tiles_x);
+  return check_launch("frame_resize");
+}

@@ -6,6 +6,9 @@ At test time the reference decodes, resizes and uploads all T frames of every wi
 builds its patch matrix straight from the store (``ops.PatchEmbedWindowsFn`` -> tad_im2col_frame_windows): no ``[B,T,H,W,3]`` clips in
 memory, and results bit-identical to running the model on ``store[idx]``.
 
+``store.append_resized`` takes the frames as decoded, of any size, and resizes them on the device (the loader's cv2 INTER_CUBIC resize:
+``frame_resize``), so the host never shrinks a frame.
+
 ``StoreViews`` stands in for the reference datasets' test mode (``_prepare_views`` + ``__getitem__`` + the default collate): videos with
 their per-frame labels go in, reference-shaped batches ``(FrameWindows, labels, ids, extra_info)`` come out -- what
 ``engine.final_test`` and ``engine.validation_one_epoch`` iterate over.
@@ -85,7 +88,8 @@ class FrameStore:
         self.bgr = bool(bgr)
         self.frames = torch.zeros((self.capacity, self.H, self.W, 3), dtype=torch.uint8, device=self.device)
         self.count = 0            # frames held: slots [0, count) are valid window entries
-        self.bytes_uploaded = 0   # bytes that went in through append() since construction / clear()
+        self.bytes_uploaded = 0   # bytes that went in through append() / append_resized() since construction / clear()
+        self._staging = None      # append_resized's device buffer for raw frames [RESIZE_CHUNK,h,w,3], kept between calls
 
     def __len__(self):
         return self.count
@@ -108,6 +112,39 @@ class FrameStore:
         self.frames[lo:lo + n].copy_(f, non_blocking=True)
         self.count += n
         self.bytes_uploaded += n * self.H * self.W * 3
+        return range(lo, lo + n)
+
+    RESIZE_CHUNK = 64  # raw frames per staging copy and resize launch of append_resized (64 frames of 1280 x 720 are 177 MB)
+
+    def append_resized(self, frames) -> range:
+        """frames: uint8 [n,h,w,3] (numpy or tensor, host or device) of ANY size h x w, as decoded.  They travel to the device once, in
+        chunks of at most ``RESIZE_CHUNK`` frames through a staging buffer that is kept between calls, and each chunk is resized
+        (``frame_resize.resize_frames``: the loader's cv2 INTER_CUBIC resize, one launch) straight into the next slots.
+        ``bytes_uploaded`` counts the raw bytes.  Never waits for the device.  Returns the slot range."""
+        from .frame_resize import resize_frames
+        f = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
+        if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or f.dim() != 4 or f.shape[-1] != 3 or f.shape[1] < 1 or f.shape[2] < 1:
+            got = f"{f.dtype} {tuple(f.shape)}" if isinstance(f, torch.Tensor) else type(frames).__name__
+            raise TypeError(f"Input must be uint8 frames of shape {('n', 'h', 'w', 3)}, but got {got}")
+        if self.device.type != "cuda":
+            raise TadError("append_resized resizes on the GPU: the store must live on one (no CPU path)")
+        n, h, w = int(f.shape[0]), int(f.shape[1]), int(f.shape[2])
+        if self.count + n > self.capacity:
+            raise TadError(f"FrameStore is full: {self.count} of {self.capacity} slots used, cannot append {n} frames")
+        lo = self.count
+        on_device = f.is_cuda and _same_device(self.device, f.device) and f.is_contiguous()
+        if not on_device and n and (self._staging is None or tuple(self._staging.shape[1:3]) != (h, w)):
+            self._staging = torch.empty((self.RESIZE_CHUNK, h, w, 3), dtype=torch.uint8, device=self.device)
+        for at in range(0, n, self.RESIZE_CHUNK):
+            m = min(self.RESIZE_CHUNK, n - at)
+            if on_device:
+                raw = f[at:at + m]
+            else:
+                raw = self._staging[:m]
+                raw.copy_(f[at:at + m], non_blocking=True)
+            resize_frames(raw, (self.H, self.W), out=self.frames[lo + at:lo + at + m])
+        self.count += n
+        self.bytes_uploaded += n * h * w * 3
         return range(lo, lo + n)
 
     def windows(self, idx) -> FrameWindows:
@@ -136,7 +173,8 @@ class StoreViews:
         self.store = store
         self.videos = []
 
-    def add_video(self, name: str, frames, frame_names, labels, ttc, smoothed_labels=None) -> range:
+    def add_video(self, name: str, frames, frame_names, labels, ttc, smoothed_labels=None, resize: bool = False) -> range:
+        """``resize=True``: the frames are as decoded, of any size, and are resized on the device (``FrameStore.append_resized``)"""
         n = len(frame_names)
         labels = np.asarray(labels)
         ttc = np.asarray(ttc)
@@ -148,7 +186,7 @@ class StoreViews:
             smoothed = np.asarray(smoothed_labels)
             if smoothed.shape[0] != n:
                 raise ValueError(f"add_video: {n} frames but smoothed_labels {smoothed.shape}")
-        slots = self.store.append(frames)
+        slots = self.store.append_resized(frames) if resize else self.store.append(frames)
         self.videos.append(dict(name=str(name), offset=slots.start, frame_names=[str(f) for f in frame_names],
                                 labels=labels.astype(np.int64), ttc=ttc, smoothed=smoothed))
         return slots

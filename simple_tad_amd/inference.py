@@ -10,6 +10,9 @@ reference's window: same arithmetic, same frame order.
 ``score_video`` is the batched counterpart for a whole video that is already there: the frames are uploaded once into a
 ``frame_store.FrameStore`` and the windows of a sequencer run ``batch_size`` at a time straight from the store (one window per forward
 is launch-bound; ``SlidingWindow`` stays the tool for frames that arrive one by one).
+
+Frames as decoded, of any size, go in through ``SlidingWindow.push_raw`` and ``score_video(resize=True)``: the reference's
+``cv2.resize(img, (224, 224), INTER_CUBIC)`` (run_inference.py:76,91) runs on the device (``frame_resize``).
 """
 from __future__ import annotations
 
@@ -26,7 +29,7 @@ IMAGENET_STD = (0.229, 0.224, 0.225)
 
 @torch.no_grad()
 def score_video(model: torch.nn.Module, frames, *, orig_fps: int, target_fps: int, view_step: int = 1, sequencer=None, batch_size: int = 32,
-                mean=IMAGENET_MEAN, std=IMAGENET_STD, bgr: bool = False) -> dict:
+                mean=IMAGENET_MEAN, std=IMAGENET_STD, bgr: bool = False, resize: bool = False) -> dict:
     """The anomaly score of every window of a video, batched: ``frames`` (uint8 [F,H,W,3], numpy or tensor, at the model's input size) is
     uploaded ONCE into a ``frame_store.FrameStore``; its windows come from ``sequencer`` (default: the reference datasets'
     ``RegularSequencer(target_fps, model.num_frames, view_step)``, dota.py:209) as a table of slots, and the model runs ``batch_size``
@@ -35,7 +38,9 @@ def score_video(model: torch.nn.Module, frames, *, orig_fps: int, target_fps: in
     (the frame the reference labels, dota.py:217), the raw logits and softmax(logits)[:, 1]; empty tensors when the video is shorter
     than one window (the sequencer returns None).  ``"bytes_uploaded"`` (an int, counted not timed) is what went host-to-device for
     the frames: F * H * W * 3, against S * T * H * W * 3 when every window is uploaded as a clip.  Each window's logits are those of running the model on that window's frames as a
-    uint8 clip at the same batch size, bit for bit."""
+    uint8 clip at the same batch size, bit for bit.  ``resize=True``: ``frames`` are as decoded, [F,h,w,3] of any size; they are uploaded
+    raw and resized to the model's input size on the device (``FrameStore.append_resized``: run_inference.py:76's cv2 INTER_CUBIC
+    resize), and ``"bytes_uploaded"`` counts the raw bytes."""
     from .frame_store import FrameStore
     from .sequencing import BasicLabeledSequencer_Abs, RegularSequencer
     pe = model.patch_embed
@@ -50,7 +55,7 @@ def score_video(model: torch.nn.Module, frames, *, orig_fps: int, target_fps: in
     seq = sequencer if sequencer is not None else RegularSequencer(int(target_fps), int(model.num_frames), int(view_step))
     store = FrameStore(max(n_frames, 1), int(pe.img_size[0]), int(pe.img_size[1]), device, bgr=bgr)
     if n_frames:
-        store.append(frames)  # (also the dtype / shape check)
+        store.append_resized(frames) if resize else store.append(frames)  # (also the dtype / shape check)
     windows = seq.get_sequences(n_frames, int(orig_fps))
     nc = int(model.num_classes)
     if windows is None:
@@ -92,6 +97,7 @@ class SlidingWindow:
         self._params = list(model.parameters())
         self._sig = None
         self._cap_stream = None
+        self._raw = None  # push_raw's device buffer for one decoded frame [1,h,w,3], kept between frames
 
     def _drop_graphs(self) -> None:
         """forget every captured graph together with what only they needed: their memory pool (the allocator retires a pool with its
@@ -123,6 +129,26 @@ class SlidingWindow:
             slot = self.start
             self.start = (self.start + 1) % self.T
         self.ring[0, slot].copy_(f, non_blocking=True)
+        self.count += 1
+
+    def push_raw(self, frame) -> None:
+        """frame: uint8 [h,w,3] of ANY size, as decoded (numpy from cv2.imread, or a tensor, host or device): uploaded raw and resized on
+        the device (run_inference.py:76's cv2 INTER_CUBIC resize; ``frame_resize.resize_frames``, one launch) into the ring slot
+        ``push`` would have written.  The ring stays the static input of the captured graphs: the resize runs outside them."""
+        from .frame_resize import resize_frames
+        f = torch.from_numpy(np.ascontiguousarray(frame)) if isinstance(frame, np.ndarray) else frame
+        if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != 3 or f.shape[0] < 1 or f.shape[1] < 1:
+            got = f"{f.dtype} {tuple(f.shape)}" if isinstance(f, torch.Tensor) else type(frame).__name__
+            raise TypeError(f"Input must be a uint8 image of shape {('h', 'w', 3)}, but got {got}")
+        if self._raw is None or tuple(self._raw.shape[1:3]) != tuple(f.shape[:2]):
+            self._raw = torch.empty((1, int(f.shape[0]), int(f.shape[1]), 3), dtype=torch.uint8, device=self.device)
+        if self.count < self.T:
+            slot = self.count
+        else:  # overwrite the oldest frame; the window now starts one slot later
+            slot = self.start
+            self.start = (self.start + 1) % self.T
+        self._raw[0].copy_(f, non_blocking=True)
+        resize_frames(self._raw, (self.H, self.W), out=self.ring[0, slot:slot + 1])
         self.count += 1
 
     @torch.no_grad()

@@ -1161,6 +1161,72 @@ def multiscale_crop(x, table, n_hsets: int, n_vsets: int, S_h: int, S_w: int, me
     return out
 
 
+# ----------------------------------------------------------------------------- the loader's cubic resize of uint8 frames, behind pad_wide_clips
+def frame_resize_table(rows, hset, vsets, B: int, H: int, W: int, S_h: int, S_w: int):
+    """Host-side table of frame_resize (include/tad_mi355x.h): ``rows`` = one (sample, mode, pad_top, pad_bottom, alpha, colour, vset)
+    per clip, alpha a float and colour three bytes (one per stored channel); ``hset`` = (in, first [S_w], k [S_w][4]) and ``vsets`` =
+    such sets towards S_h outputs, one per distinct virtual height.  Returns the int32 CPU tensor of tad_frame_resize_workspace_bytes
+    / 4 words, checked by tad_frame_resize_plan_check (word count, every sample once, pads within H, sets stated for the extents
+    they serve, taps next to their source, sum |k| <= 2818); runs without a GPU."""
+    import numpy as np
+    lib = _lib.load()
+    nv = len(vsets)
+    if len(rows) != B or not 1 <= nv <= _lib.FR_MAX_SETS:
+        raise _lib.TadError(f"frame_resize_table: {len(rows)} rows for {B} clips, {nv} vertical sets (1 .. {_lib.FR_MAX_SETS})")
+    tab = np.zeros(lib.tad_frame_resize_workspace_bytes(B, nv, S_h, S_w) // 4, dtype=np.int32)
+    head = tab[:B * _lib.FR_ROW_WORDS].reshape(B, _lib.FR_ROW_WORDS)
+    for i, (sample, mode, pad_top, pad_bottom, alpha, colour, vset) in enumerate(rows):
+        c = [int(v) for v in colour]
+        if len(c) != 3 or not all(0 <= v <= 255 for v in c):
+            raise _lib.TadError(f"frame_resize_table: row {i}: colour {colour!r} must hold three bytes")
+        words = [int(sample), int(mode), int(pad_top), int(pad_bottom), int(np.float32(alpha).view(np.int32)), c[0] | c[1] << 8 | c[2] << 16, int(vset)]
+        if any(abs(w) >= 2 ** 31 for w in words):
+            raise _lib.TadError(f"frame_resize_table: row {i} does not fit 32 bits")
+        head[i, :7] = words
+    at = B * _lib.FR_ROW_WORDS
+    for sets, out in (([hset], S_w), (vsets, S_h)):
+        for n_in, first, kk in sets:
+            first, kk = np.asarray(first, dtype=np.int32), np.asarray(kk, dtype=np.int32)
+            if first.shape != (out,) or kk.shape != (out, 4):
+                raise _lib.TadError(f"frame_resize_table: a set with first {first.shape} and k {kk.shape} for {out} outputs")
+            tab[at:at + 2] = n_in, out
+            tab[at + _lib.FR_SET_HEAD:at + _lib.FR_SET_HEAD + out] = first
+            tab[at + _lib.FR_SET_HEAD + out:at + _lib.FR_SET_HEAD + 5 * out] = kk.reshape(-1)
+            at += _lib.FR_SET_HEAD + 5 * out
+    check(lib.tad_frame_resize_plan_check(tab.ctypes.data, tab.size, B, nv, H, W, S_h, S_w), "tad_frame_resize_plan_check")
+    return torch.from_numpy(tab)
+
+
+def frame_resize(x, table, n_vsets: int, S_h: int, S_w: int, mean=None, std=None, out=None):
+    """Resize (cubic, behind the virtual pad bands the table states) the contiguous uint8 frames x [B,T,H,W,3] as the device table
+    ``table`` (a copy of frame_resize_table()'s: the call's workspace, only read) says (tad_frame_resize, ONE launch).  Without
+    ``mean`` / ``std``: uint8 [B,T,S_h,S_w,3]; with them: the normalised f32 clips [B,3,T,S_h,S_w], the bits frames_to_clip gives on
+    the uint8 result.  ``out`` may be any contiguous view of that shape (a ring slot, a slice of a frame store).  x is only read."""
+    _req_frames(x, "frame_resize.x")
+    B, T, H, W, _ = x.shape
+    _req(table, torch.int32, "frame_resize.table")
+    lib = _lib.load()
+    nbytes = lib.tad_frame_resize_workspace_bytes(B, n_vsets, S_h, S_w)
+    if table.dim() != 1 or nbytes == 0 or table.numel() * 4 != nbytes or table.device != x.device:
+        raise _lib.TadError(f"frame_resize.table: expected the device copy of frame_resize_table() for {B} clips ({nbytes} bytes), "
+                            f"got {tuple(table.shape)} on {table.device}")
+    if (mean is None) != (std is None):
+        raise _lib.TadError("frame_resize: mean and std come together")
+    f32 = mean is not None
+    shape = (B, 3, T, S_h, S_w) if f32 else (B, T, S_h, S_w, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32 if f32 else torch.uint8, device=x.device)
+    else:
+        _req(out, torch.float32 if f32 else torch.uint8, "frame_resize.out")
+        if tuple(out.shape) != shape or out.device != x.device:
+            raise _lib.TadError(f"frame_resize.out: expected {shape} on {x.device}, got {tuple(out.shape)} on {out.device}")
+    m, s = (_f3(mean), _f3(std)) if f32 else (None, None)
+    with _timed("frame_resize", 0.0, float(x.numel() + out.numel() * out.element_size())):
+        check(lib.tad_frame_resize(x.data_ptr(), out.data_ptr(), int(f32), m, s, table.data_ptr(), nbytes, B, T, H, W, S_h, S_w, n_vsets,
+                                   _stream()), "tad_frame_resize")
+    return out
+
+
 # ----------------------------------------------------------------------------- fine-tune spatial sampling: window, bilinear resize, crop, flip
 def spatial_sample_table(rows, B: int, T: int, H: int, W: int, S: int):
     """Host-side table of spatial_sample (include/tad_mi355x.h): ``rows`` = one (sample, i, j, h, w, rh, rw, oy, ox, flip) per (clip,

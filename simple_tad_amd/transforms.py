@@ -16,9 +16,10 @@ stream: ``random.choice(pairs)`` over the (w, h) crop sizes, then ``random.choic
 ``DataAugmentationForVideoMAE`` come from numpy's GLOBAL stream, one ``TubeMaskingGenerator`` call per clip (another stream than the
 crops', so drawing the batch's crops first and its masks second consumes both as the reference's per-sample calls do).
 
-Not built: a crop that shrinks an axis by more than 8 (Pillow's kernel grows past 17 taps; ``TadError``), the cv2 ``INTER_CUBIC``
-loader resize and ``pad_wide_clips`` of the fine-tune datasets.  (The fine-tune recipe's ``spatial_sampling`` -- random resized crop,
-scale jitter + crop, flip, the three test-time crops -- is ``spatial_sampling.SpatialSampling``.)
+Not built: a crop that shrinks an axis by more than 8 (Pillow's kernel grows past 17 taps; ``TadError``).  (The fine-tune recipe's
+``spatial_sampling`` -- random resized crop, scale jitter + crop, flip, the three test-time crops -- is
+``spatial_sampling.SpatialSampling``; the cv2 ``INTER_CUBIC`` loader resize and ``pad_wide_clips`` of the fine-tune datasets are
+``frame_resize.resize_frames`` and ``frame_resize.PadWideClips``.)
 """
 from __future__ import annotations
 
