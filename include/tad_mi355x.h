@@ -708,6 +708,27 @@ int tad_mse_loss(const float* pred, const float* target, int64_t n, float* parti
 int tad_threshold_histogram(const float* probs, const int32_t* labels, const float* thresholds, int n_thresholds, int64_t n,
                             int64_t* hist, tad_stream_t stream);
 
+/* ---- grouped evaluation report (anaysis/metrics_dota.py, metrics_dada.py, metrics_by_categories.py) ---------------------------
+ * The same counts for up to 64 sample groups at once (TOTAL, accident categories, ego / non-ego, night / day ...): bit g of
+ * member[i] says that sample i belongs to group g; a sample may belong to any number of groups, also to none.
+ * tad_group_threshold_histogram: hist int64 [n_groups][2][n_thresholds+1] (device, overwritten): hist[g] is tad_threshold_histogram's
+ * table over the members of group g (same comparison in f32, NaN gives k = 0, ascending thresholds, exact counts; n_groups = 1 with
+ * every mask = 1 gives that table bit for bit).  1 <= n_groups <= 64, 1 <= n_thresholds <= 255. */
+int tad_group_threshold_histogram(const float* probs, const int32_t* labels, const uint64_t* member, int n_groups,
+                                  const float* thresholds, int n_thresholds, int64_t n, int64_t* hist, tad_stream_t stream);
+/* tad_group_rank_stats: scikit-learn's roc_auc_score / average_precision_score of every group from ONE ordering of all samples.
+ * labels_sorted / member_sorted: the samples in DESCENDING score order; run_end[i] = 1 where score[i] != score[i+1] (compared in f32:
+ * -0.0 and 0.0 tie) or i == n - 1, else 0.  A run of tied scores counts for a group only through the group's members in it, so the
+ * runs of the whole array are the right runs for every group.  With T, F the group's positives / negatives up to a run end e and
+ * (T_s, F_s) those at the run end before it (0, 0 at the start):
+ *   out_int[g] = {P, N, U2},  U2 = sum_e (F_e - F_s)(T_e + T_s) = 2 P N AUROC, an exact integer (AUROC = U2 / (2 P N) on the host)
+ *   out_ap[g]  = sum_e (T_e - T_s) T_e / (T_e + F_e) / P in fp64; 0 when P == 0 (scikit-learn's value for a group without positives)
+ * One workgroup per group walks the array in tiles of TAD_GROUP_RANK_TILE samples; the fp64 sum runs in a fixed order (no
+ * floating-point atomics): two calls give the same bits.  No workspace.  1 <= n_groups <= 64, 1 <= n < 2^31. */
+#define TAD_GROUP_RANK_TILE 4096
+int tad_group_rank_stats(const int32_t* labels_sorted, const uint64_t* member_sorted, const uint8_t* run_end, int n_groups, int64_t n,
+                         int64_t* out_int, double* out_ap, tad_stream_t stream);
+
 /* ---- "precise" mode (parity gate, not throughput): f32-accurate Linear via split-bf16 operands, f32 attention ----------
  * x = hi + lo (bf16 each).  concat mode: out [M,3K] = [hi|hi|lo] (role_b=0) or [hi|lo|hi] (role_b=1); stack mode: out [3M,K]
  * with the three parts stacked along rows.  Feeding tad_linear_* with both operands split this way (K or M tripled) gives the

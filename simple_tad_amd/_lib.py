@@ -95,6 +95,8 @@ SIGNATURES = {
     "tad_mse_loss_blocks": (_i, [_i64]),
     "tad_mse_loss": (_i, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "tad_threshold_histogram": (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp]),
+    "tad_group_threshold_histogram": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i64, _vp, _vp]),
+    "tad_group_rank_stats": (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
     "tad_split_bf16x3": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp]),
     "tad_im2col_tubelets_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "tad_attn_fwd_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, C.c_uint32, _vp]),
@@ -155,6 +157,7 @@ FR_NONE, FR_CONST, FR_REFLECT, FR_REPLICATE = range(4)
 SEGNORM_WORK_MAX = 16384  # TAD_SEGNORM_WORK_MAX: the longest work item of tad_grad_segnorm, in floats
 SEGNORM_DEPTH = 17  # the longest chain of f32 additions behind one element's square (csrc/grad_segnorm.hip, "depth")
 POOL_SPLIT = 8
+GROUP_MAX, GROUP_RANK_TILE = 64, 4096  # tad_group_*: the most groups of one call; TAD_GROUP_RANK_TILE, the samples per scan tile
 
 _lib = None
 

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import json
 import math
+import os
 import sys
 from typing import Iterable, Optional
 
@@ -519,7 +520,7 @@ def write_predictions_csv(path, table) -> None:
 
 @torch.no_grad()
 def final_test(data_loader, model, device, preds_file, stats_file, plot_dir=None, with_ttc=False, smoothed_labels_for_loss=False,
-               criterion=None):
+               criterion=None, group_annotations=None, group_report_file=None):
     """engine_for_frame_finetuning.final_test (:385-545): run the model over the test windows, write ``preds_file`` (a CSV with an index
     column and clip, filename, logits_safe, logits_risk, label, ttc: the input of anaysis/metrics*.py) and ``stats_file`` (the five
     lines mAP / auroc / acc, P / R / F1 at 0.5, confusion matrix, from ``metrics.calculate_metrics``), return the global averages
@@ -529,9 +530,14 @@ def final_test(data_loader, model, device, preds_file, stats_file, plot_dir=None
     ``criterion`` (default CrossEntropyLoss, the reference's), ``with_ttc`` and ``smoothed_labels_for_loss`` as in validation_one_epoch.
     Differences, by design: the plots are not built (``plot_dir`` is accepted and ignored with one warning); the reference reads
     ``output`` before it is assigned when no process group exists (:414) -- the labels collected are the targets in every case.
-    With several ranks the tensors travel through ``gather_predictions``, the names through ``all_gather_object``; rank 0 writes."""
+    With several ranks the tensors travel through ``gather_predictions``, the names through ``all_gather_object``; rank 0 writes.
+    ``group_annotations`` (default None: nothing more is written): ``{"clip_lvl_cat": {clip name: category code}, "clip_lvl_ego":
+    {clip name: bool}}`` and optionally ``"cat_codes"`` -- rank 0 then also writes ``metrics.group_report`` of the logits it gathered
+    (the group_metrics.txt of anaysis/metrics_dota.py) to ``group_report_file`` (default: group_metrics.txt next to ``preds_file``)."""
     import torch.distributed as dist
     from . import metrics as M
+    if group_report_file is not None and group_annotations is None:
+        raise ValueError("final_test: group_report_file needs group_annotations")
     if plot_dir is not None:
         import warnings
         warnings.warn("final_test: the PR / ROC plots of the reference are not built; plot_dir is ignored")
@@ -580,6 +586,13 @@ def final_test(data_loader, model, device, preds_file, stats_file, plot_dir=None
                 f.write(line + "\n")
                 print(line)
         write_predictions_csv(preds_file, table)
+        if group_annotations is not None:
+            cat, ego = group_annotations["clip_lvl_cat"], group_annotations["clip_lvl_ego"]
+            report = M.group_report(torch.softmax(all_preds.float(), dim=1)[:, 1], all_labels, table["clip"],
+                                    clip_lvl_cat=[cat[c] for c in table["clip"]], clip_lvl_ego=[bool(ego[c]) for c in table["clip"]],
+                                    cat_codes=group_annotations.get("cat_codes", M.DOTA_CAT_CODES))
+            with open(group_report_file or os.path.join(os.path.dirname(preds_file), "group_metrics.txt"), "w") as f:
+                f.write("\n".join(report))
     result = {"loss": float(meters[0] / max(float(meters[1]), 1.0)), "acc1": float(100.0 * meters[2] / max(float(meters[3]), 1.0))}
     print("* Acc@1 {:.3f} loss {:.3f}".format(result["acc1"], result["loss"]))
     return result
