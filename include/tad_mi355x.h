@@ -329,6 +329,28 @@ int tad_meanpool_fwd(const float* x, float* y, float* ws, int B, int N, int D, t
 int tad_meanpool_bwd(const float* dy, float* dx, uint16_t* dx_bf16, int B, int N, int D,
                      tad_stream_t stream);
 
+/* ---- pooled tail: the last block when only the token mean of its output is read (csrc/pooled_tail.hip) ----
+ * x2 = x1 + dp2 (a W2^T + b2) is linear in a, so mean_n(x2) needs only the per-clip column sums of a, and every token of a clip
+ * receives the same gradient dy[b]/N: one accumulator row t[b] = gb[b] W2 per clip serves all N rows of the fc2 input gradient.
+ * One entry point each for both operand formats: op_dtype is TAD_BF16 or TAD_F16 (there is no _f16 twin).
+ *
+ * S[b,:] = sum_{n<N} a[b*N+n,:]: a [B*N,K] 16-bit, S [B,K] f32.  f32 accumulation in a fixed order (two stages, no atomics).
+ * ws: B*TAD_POOL_SPLIT*K floats (ws_bytes is checked: TAD_ENOSPACE).  K % 8 == 0 and a, S, ws 16-byte aligned, else TAD_EINVAL:
+ * callers fall back to the general path. */
+int tad_colsum_segments(const uint16_t* a, int op_dtype, float* S, void* ws, size_t ws_bytes, int B, int N, int K,
+                        tad_stream_t stream);
+/* The pooled fc2: out[b,:] = xbar[b,:] + rowscale[b] ((S[b,:] W^T) / N + bias).  S [B,K] f32 (tad_colsum_segments), w [D,K] 16-bit,
+ * bias [D] (nullable), rowscale [B] (nullable), xbar and out [B,D] f32 (out must not alias xbar).  The B*D dot products run on the
+ * f32 sums (the pooled operand is not rounded to 16 bits) with f64 accumulation and one rounding to f32 at the end.
+ * K % 8 == 0 and S, w 16-byte aligned, else TAD_EINVAL. */
+int tad_pooled_linear(const float* S, const uint16_t* w, int op_dtype, const float* bias, const float* rowscale, const float* xbar,
+                      float* out, int B, int N, int D, int K, tad_stream_t stream);
+/* dh[b*N+n,:] = op16(t[b,:] * gelu'(h[b*N+n,:])): t [B,K] f32, h and dh [B*N,K] 16-bit.  The arithmetic and the rounding are those
+ * of tad_linear_bwd_input's gelu_preact epilogue on an accumulator row t[b]: bit-identical to it.
+ * K % 8 == 0 and t, h, dh 16-byte aligned, else TAD_EINVAL. */
+int tad_gelu_grad_bcast(const float* t, const uint16_t* h, uint16_t* dh, int op_dtype, int B, int N, int K,
+                        tad_stream_t stream);
+
 /* ---- small helpers used by the training step ------------------------------------------
  * column sums of a bf16 [M,N] matrix into f32 [N] (bias gradients: q_bias/v_bias/fc1.bias). */
 size_t tad_colsum_workspace_bytes(int64_t M, int N);

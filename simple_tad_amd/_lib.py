@@ -54,6 +54,9 @@ SIGNATURES = {
     "tad_attn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _f, C.c_uint32, _vp]),
     "tad_meanpool_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "tad_meanpool_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "tad_colsum_segments": (_i, [_vp, _i, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "tad_pooled_linear": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "tad_gelu_grad_bcast":(_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "tad_colsum_workspace_bytes": (_sz, [_i64, _i]),
     "tad_colsum_bf16": (_i, [_vp, _vp, _i, _vp, _sz, _i64, _i, _vp]),
     "tad_colsum_window_f32": (_i, [_vp, _vp, _i, _vp, _sz, _i, _i, _i, _i, _i, _vp]),

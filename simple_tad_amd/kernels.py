@@ -784,6 +784,56 @@ def meanpool_bwd(dy, N: int, want_bf16=False):
     return dx, dxb
 
 
+# ----------------------------------------------------------------------------- pooled tail (ops.BlockPoolFn)
+def colsum_segments_ok(K: int) -> bool:
+    """shapes tad_colsum_segments / tad_gelu_grad_bcast take (else: the general path)"""
+    return K % 8 == 0
+
+
+def colsum_segments(a, B: int, N: int):
+    """a [B*N, K] 16-bit -> S [B, K] f32, S[b] = sum of the N rows of clip b (f32 accumulation, fixed order)"""
+    op = _req16(a, "colsum_segments.a")
+    M, Kc = a.shape
+    assert M == B * N, (M, B, N)
+    S = torch.empty((B, Kc), dtype=torch.float32, device=a.device)
+    ws = workspace(B * _lib.POOL_SPLIT * Kc * 4, a.device)
+    with _timed("colsum", 0.0, 2.0 * M * Kc):
+        check(_lib.load().tad_colsum_segments(a.data_ptr(), _dt(a), S.data_ptr(), ws.data_ptr(), ws.numel(), B, N, Kc, _stream()),
+              "tad_colsum_segments")
+    return S
+
+
+def pooled_linear(S, w, bias, rowscale, xbar, N: int):
+    """xbar [B, D] + rowscale[b] * ((S [B, K] @ w [D, K]^T) / N + bias): f32 sums times 16-bit weights, f64 accumulation, f32 [B, D]"""
+    _req(S, torch.float32, "pooled_linear.S")
+    _req(xbar, torch.float32, "pooled_linear.xbar")
+    _req16(w, "pooled_linear.w")
+    B, Kc = S.shape
+    D = w.shape[0]
+    assert w.shape[1] == Kc and tuple(xbar.shape) == (B, D), (tuple(S.shape), tuple(w.shape), tuple(xbar.shape))
+    for name, t, n in (("bias", bias, D), ("rowscale", rowscale, B)):
+        if t is not None:
+            _req(t, torch.float32, "pooled_linear." + name)
+            assert t.numel() == n, (name, t.numel(), n)
+    out = torch.empty((B, D), dtype=torch.float32, device=S.device)
+    check(_lib.load().tad_pooled_linear(S.data_ptr(), w.data_ptr(), _dt(w), _p(bias), _p(rowscale), xbar.data_ptr(), out.data_ptr(), B, N, D, Kc,
+                                        _stream()), "tad_pooled_linear")
+    return out
+
+
+def gelu_grad_bcast(t, h, N: int):
+    """t [B, K] f32 (one accumulator row of the fc2 input gradient per clip), h [B*N, K] 16-bit pre-activations ->
+    dh [B*N, K] = op16(t[clip] * gelu'(h)): what linear_bwd_input(..., gelu_preact=h) writes when the N rows of a clip are equal"""
+    _req(t, torch.float32, "gelu_grad_bcast.t")
+    op = _req16(h, "gelu_grad_bcast.h")
+    B, Kc = t.shape
+    assert tuple(h.shape) == (B * N, Kc), (tuple(h.shape), B, N, Kc)
+    dh = torch.empty((B * N, Kc), dtype=op, device=h.device)
+    with _timed("cast", 0.0, 4.0 * B * N * Kc):
+        check(_lib.load().tad_gelu_grad_bcast(t.data_ptr(), h.data_ptr(), dh.data_ptr(), _dt(h), B, N, Kc, _stream()), "tad_gelu_grad_bcast")
+    return dh
+
+
 def sumsq(x, out):
     _req(x, torch.float32, "sumsq.x")
     lib = _lib.load()

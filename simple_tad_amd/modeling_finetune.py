@@ -180,6 +180,26 @@ class Block(nn.Module):
                 and self.norm1.elementwise_affine and self.norm2.elementwise_affine and self.norm1.eps == self.norm2.eps
                 and not (self.training and (self.mlp.drop.p > 0 or self.attn.proj_drop.p > 0 or self.attn.attn_drop.p > 0)))
 
+    def _fused(self, x, apply):
+        self.attn._check()
+        dp = self.drop_path if isinstance(self.drop_path, DropPath) else None
+        s1 = dp.sample(x.shape[0], x.device) if dp is not None else None
+        s2 = dp.sample(x.shape[0], x.device) if dp is not None else None
+        a, m = self.attn, self.mlp
+        return apply(x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.q_bias, a.v_bias, a.proj.weight,
+                     a.proj.bias, self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight,
+                     m.fc2.bias, s1, s2, a.num_heads, a.scale, self.norm1.eps)
+
+    def pools_fused(self):
+        """may ``forward_pooled`` stand for ``forward(x).mean(1)``?  The fused 16-bit block, the switch on (ops.set_pooled_tail), and
+        no hook on this module that would have to see the [B, N, D] output that is never formed."""
+        return (self._fusable() and ops.pooled_tail_ok(self.mlp.fc2.weight)
+                and not (self._forward_hooks or self._forward_pre_hooks or self._backward_hooks or self._backward_pre_hooks))
+
+    def forward_pooled(self, x):
+        """mean over tokens of ``forward(x)``: [B, N, D] -> [B, D], without the fc2 GEMM over all rows (ops.BlockPoolFn)"""
+        return self._fused(x, ops.block_pool_apply)
+
     def forward(self, x):
         if self._fusable() and ops.get_precision() == "precise":
             self.attn._check()
@@ -190,14 +210,7 @@ class Block(nn.Module):
                                      self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
                                      a.num_heads, a.scale, self.norm1.eps)
         if self._fusable():
-            self.attn._check()
-            dp = self.drop_path if isinstance(self.drop_path, DropPath) else None
-            s1 = dp.sample(x.shape[0], x.device) if dp is not None else None
-            s2 = dp.sample(x.shape[0], x.device) if dp is not None else None
-            a, m = self.attn, self.mlp
-            return ops.block_apply(x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.q_bias, a.v_bias, a.proj.weight,
-                                   a.proj.bias, self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight,
-                                   m.fc2.bias, s1, s2, a.num_heads, a.scale, self.norm1.eps)
+            return self._fused(x, ops.block_apply)
         # layer-scale / dropout variants: composed from the per-operator kernels
         n1 = ops.LayerNormFn.apply(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)
         n1 = self.attn(n1)
@@ -381,13 +394,24 @@ class VisionTransformer(nn.Module):
         else:
             x = self.patch_embed(x, pos_embed=pos)  # fused "+ pos_embed" epilogue
         x = self.pos_drop(x)
+        # fc_norm reads nothing but the token mean of the last block's output (self.norm is Identity then): that block runs as one
+        # function with the mean-pool, which needs no fc2 GEMM over all rows (ops.BlockPoolFn).  Under use_checkpoint the same function
+        # is the last checkpointed unit, so that both routes keep computing the same bits (tests pin their gradients against each other).
+        blocks = list(self.blocks)
+        last = None
+        if self.final_reduction == "fc_norm" and isinstance(self.norm, nn.Identity) and blocks and blocks[-1].pools_fused():
+            last = blocks.pop()
         if self.use_checkpoint:
-            for blk in self.blocks:
+            for blk in blocks:
                 x = checkpoint.checkpoint(blk, x, use_reentrant=False)
+            if last is not None:
+                return self._ln(self.fc_norm, checkpoint.checkpoint(last.forward_pooled, x, use_reentrant=False))
         else:
             self._presample_drop_path(x.shape[0], x.device)
-            for blk in self.blocks:
+            for blk in blocks:
                 x = blk(x)
+            if last is not None:
+                return self._ln(self.fc_norm, last.forward_pooled(x))
         x = self._ln(self.norm, x)
         if self.final_reduction == "fc_norm":
             return self._ln(self.fc_norm, ops.MeanPoolFn.apply(x))

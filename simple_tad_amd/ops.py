@@ -632,41 +632,19 @@ class BlockFn(_Fn):
     @staticmethod
     def forward(ctx, x, n1w, n1b, qkv_w, q_bias, v_bias, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, dp1, dp2, H, scale,
                 eps, prev_link=None, link=None):
-        _need_gpu(x, "Block")
+        train, x1, a = _block_fwd_to_fc1(ctx, x, n1w, n1b, qkv_w, q_bias, v_bias, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b,
+                                         dp1, dp2, H, scale, eps, prev_link, link)
         B, N, D = x.shape
-        M = B * N
-        train = _differentiated(ctx)
-        x0 = _f32c(x).reshape(M, D)
-        g1, b1, g2, b2 = _f32c(n1w), _f32c(n1b), _f32c(n2w), _f32c(n2b)
-        xn1, mean1, rstd1 = K.layernorm_fwd(x0, g1, b1, eps, save_stats=train)
-        qkv, ao, (lse, ao_lo) = _attn_fwd_core(xn1, qkv_w, q_bias, v_bias, B, N, H, scale, train, rowscale=_f32c(dp1))
-        ctx.qpre = _attn_q_prescale  # (the contract `qkv` was written under: read back by the backward)
-        x1, _ = K.linear_fwd(ao, w_bf16(proj_w, train), _f32c(proj_b), out_dtype=torch.float32, epilogue=EPI_BIAS_RESIDUAL, residual=x0,
-                             rowscale=_f32c(dp1), rows_per_scale=N)
-        xn2, mean2, rstd2 = K.layernorm_fwd(x1, g2, b2, eps, save_stats=train)
-        a, h = K.linear_fwd(xn2, w_bf16(fc1_w, train), _f32c(fc1_b), out_dtype=None, epilogue=EPI_BIAS_GELU, want_preact=train)
         x2, _ = K.linear_fwd(a, w_bf16(fc2_w, train), _f32c(fc2_b), out_dtype=torch.float32, epilogue=EPI_BIAS_RESIDUAL, residual=x1,
                              rowscale=_f32c(dp2), rows_per_scale=N)
-        if train:
-            ctx.save_for_backward(x0, g1, mean1, rstd1, xn1, qkv, ao, lse, x1, g2, mean2, rstd2, xn2, h, a, qkv_w, proj_w, fc1_w, fc2_w,
-                                  dp1 if dp1 is None else _f32c(dp1), dp2 if dp2 is None else _f32c(dp2), ao_lo)
-        ctx.meta = (B, N, D, H, scale, q_bias is not None)
-        ctx.biases = (proj_b, fc1_b, fc2_b)
-        ctx.norms = (n1w, n1b, n2w, n2b)
-        ctx.qv = (q_bias, v_bias)
-        # block chain (_ChainLink): where my backward deposits the bf16 gradient for the block before me / takes the one made for me
-        ctx.prev_link = prev_link if train else None
-        ctx.link = link if train else None
         return x2.reshape(B, N, D)
 
     @staticmethod
     def backward(ctx, g):
-        (x0, g1, mean1, rstd1, xn1, qkv, ao, lse, x1, g2, mean2, rstd2, xn2, h, a, qkv_w, proj_w, fc1_w, fc2_w, dp1,
-         dp2, ao_lo) = ctx.saved_tensors
-        proj_b, fc1_b, fc2_b = ctx.biases
-        B, N, D, H, scale, has_qb = ctx.meta
-        M = B * N
-        g = _f32c(g).reshape(M, D)
+        st = ctx.saved_tensors
+        h, a, fc2_w, dp2 = st[13], st[14], st[18], st[20]
+        B, N, D = ctx.meta[:3]
+        g = _f32c(g).reshape(B * N, D)
         # ---- MLP branch
         gb = None
         dep = ctx.link.deposit if ctx.link is not None else None
@@ -680,30 +658,159 @@ class BlockFn(_Fn):
         if gb is None:
             gb = K.cast_bf16(g) if dp2 is None else K.scale_cast_bf16(g, None, dp2, N)
         dh = K.linear_bwd_input(gb, wT_bf16(fc2_w, True), gelu_preact=h)
-        dW2, db2 = linear_dw(gb, a, fc2_w, fc2_b)
-        dxn2 = K.linear_bwd_input(dh, wT_bf16(fc1_w, True))
-        dW1, db1 = linear_dw(dh, xn2, fc1_w, fc1_b)
-        # LN2 backward also emits what the attention branch needs: bf16(drop-path scale * residual-stream grad) and its column
-        # sums (= proj bias gradient), so neither a cast pass nor a bias reduction in the dW GEMM is needed
-        n1w, n1b, n2w, n2b = ctx.norms
-        gmid, gpb, dg2, dbeta2, dbp = layernorm_bwd_sunk(dxn2, x1, g2, mean2, rstd2, n2w, n2b, colsum_param=proj_b, dres=g, want_bf16=True,
-                                                        rowscale=dp1, rows_per_scale=N)
-        # ---- attention branch
-        d_ao = K.linear_bwd_input(gpb, wT_bf16(proj_w, True))
-        # (the proj weight gradient rides with the qkv one: one launch for both, _attn_bwd_core)
-        dxn1, dWqkv, dqb, dvb, dWp = _attn_bwd_core(d_ao, xn1, qkv, ao, lse, qkv_w, has_qb, B, N, H, scale, None, ctx.qv, ao_lo=ao_lo, q_prescaled=ctx.qpre,
-                                                     pair=(gpb, ao, proj_w), rowscale=dp1)
-        prev = ctx.prev_link
-        if prev is not None:
-            gin, ginb, dg1, dbeta1, _ = layernorm_bwd_sunk(dxn1, x0, g1, mean1, rstd1, n1w, n1b, dres=gmid, want_bf16=True, rowscale=prev.dp2,
-                                                           rows_per_scale=N)
-            if prev.deposit is None:
-                _chain.pending += 1
-            prev.deposit = (ginb, gin, gin._version)
+        dW2, db2 = linear_dw(gb, a, fc2_w, ctx.biases[2])
+        return _block_bwd_from_dh(ctx, st, g, dh, dW2, db2)
+
+
+def _block_fwd_to_fc1(ctx, x, n1w, n1b, qkv_w, q_bias, v_bias, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, dp1, dp2, H, scale,
+                      eps, prev_link, link):
+    """the fused Block up to and including fc1 (+ GELU), and everything its backward needs; returns (train, x1 [M,D] f32, a [M,4D])"""
+    _need_gpu(x, "Block")
+    B, N, D = x.shape
+    M = B * N
+    train = _differentiated(ctx)
+    x0 = _f32c(x).reshape(M, D)
+    g1, b1, g2, b2 = _f32c(n1w), _f32c(n1b), _f32c(n2w), _f32c(n2b)
+    xn1, mean1, rstd1 = K.layernorm_fwd(x0, g1, b1, eps, save_stats=train)
+    qkv, ao, (lse, ao_lo) = _attn_fwd_core(xn1, qkv_w, q_bias, v_bias, B, N, H, scale, train, rowscale=_f32c(dp1))
+    ctx.qpre = _attn_q_prescale  # (the contract `qkv` was written under: read back by the backward)
+    x1, _ = K.linear_fwd(ao, w_bf16(proj_w, train), _f32c(proj_b), out_dtype=torch.float32, epilogue=EPI_BIAS_RESIDUAL, residual=x0,
+                         rowscale=_f32c(dp1), rows_per_scale=N)
+    xn2, mean2, rstd2 = K.layernorm_fwd(x1, g2, b2, eps, save_stats=train)
+    a, h = K.linear_fwd(xn2, w_bf16(fc1_w, train), _f32c(fc1_b), out_dtype=None, epilogue=EPI_BIAS_GELU, want_preact=train)
+    if train:
+        ctx.save_for_backward(x0, g1, mean1, rstd1, xn1, qkv, ao, lse, x1, g2, mean2, rstd2, xn2, h, a, qkv_w, proj_w, fc1_w, fc2_w,
+                              dp1 if dp1 is None else _f32c(dp1), dp2 if dp2 is None else _f32c(dp2), ao_lo)
+    ctx.meta = (B, N, D, H, scale, q_bias is not None)
+    ctx.biases = (proj_b, fc1_b, fc2_b)
+    ctx.norms = (n1w, n1b, n2w, n2b)
+    ctx.qv = (q_bias, v_bias)
+    # block chain (_ChainLink): where my backward deposits the bf16 gradient for the block before me / takes the one made for me
+    ctx.prev_link = prev_link if train else None
+    ctx.link = link if train else None
+    return train, x1, a
+
+
+def _block_bwd_from_dh(ctx, st, g, dh, dW2, db2):
+    """the fused Block's backward from the gradient dh of the MLP's hidden layer on: fc1, LN2, the attention branch, LN1 and the deposit
+    for the block before.  g [M,D] f32: the gradient of the block's output rows (LN2's residual term)."""
+    x0, g1, mean1, rstd1, xn1, qkv, ao, lse, x1, g2, mean2, rstd2, xn2, h, a, qkv_w, proj_w, fc1_w, fc2_w, dp1, dp2, ao_lo = st
+    proj_b, fc1_b, fc2_b = ctx.biases
+    B, N, D, H, scale, has_qb = ctx.meta
+    dxn2 = K.linear_bwd_input(dh, wT_bf16(fc1_w, True))
+    dW1, db1 = linear_dw(dh, xn2, fc1_w, fc1_b)
+    # LN2 backward also emits what the attention branch needs: bf16(drop-path scale * residual-stream grad) and its column
+    # sums (= proj bias gradient), so neither a cast pass nor a bias reduction in the dW GEMM is needed
+    n1w, n1b, n2w, n2b = ctx.norms
+    gmid, gpb, dg2, dbeta2, dbp = layernorm_bwd_sunk(dxn2, x1, g2, mean2, rstd2, n2w, n2b, colsum_param=proj_b, dres=g, want_bf16=True,
+                                                    rowscale=dp1, rows_per_scale=N)
+    # ---- attention branch
+    d_ao = K.linear_bwd_input(gpb, wT_bf16(proj_w, True))
+    # (the proj weight gradient rides with the qkv one: one launch for both, _attn_bwd_core)
+    dxn1, dWqkv, dqb, dvb, dWp = _attn_bwd_core(d_ao, xn1, qkv, ao, lse, qkv_w, has_qb, B, N, H, scale, None, ctx.qv, ao_lo=ao_lo, q_prescaled=ctx.qpre,
+                                                 pair=(gpb, ao, proj_w), rowscale=dp1)
+    prev = ctx.prev_link
+    if prev is not None:
+        gin, ginb, dg1, dbeta1, _ = layernorm_bwd_sunk(dxn1, x0, g1, mean1, rstd1, n1w, n1b, dres=gmid, want_bf16=True, rowscale=prev.dp2,
+                                                       rows_per_scale=N)
+        if prev.deposit is None:
+            _chain.pending += 1
+        prev.deposit = (ginb, gin, gin._version)
+    else:
+        gin, _, dg1, dbeta1, _ = layernorm_bwd_sunk(dxn1, x0, g1, mean1, rstd1, n1w, n1b, dres=gmid)
+    return (gin.reshape(B, N, D), dg1, dbeta1, dWqkv, dqb, dvb, dWp, dbp, dg2, dbeta2, dW1, db1, dW2, db2, None, None, None, None,
+            None, None, None)
+
+
+# --------------------------------------------------------------------------- last Block + mean-pool
+# The fine-tuning model ends with fc_norm(mean over tokens(last block's output)).  x2 = x1 + dp2 (a W2^T + b2) is linear in a and
+# nothing but the token mean reads it, so
+#   forward:  mean_n(x2)[b] = mean_n(x1)[b] + dp2[b] ((S[b] / N) W2^T + b2),  S[b] = sum_n a[b,n,:]     -- no fc2 GEMM, no x2;
+#   backward: every token of clip b receives dy[b] / N, so the fc2 input-gradient rows of a clip share ONE accumulator row
+#             t[b] = gb[b] W2 (gb[b] = op16(dy[b] / N * dp2[b])) and dh = op16(t[clip] * gelu'(h)) is one streaming pass;
+#             dW2 = sum_b gb[b]^T S[b], db2 = N sum_b gb[b].
+# dh -- and with it everything upstream of the MLP's hidden layer -- is bit-identical to BlockFn + MeanPoolFn (t[b] is the row the
+# B*N-row launch computes N times: every plan of gemm_nt sums K in the same order); the pooled output, dW2 and db2 are the same products
+# summed in another order (S is never rounded to 16 bits; dW2 / db2 in f32, the B x D pooled fc2 with f64 accumulation: K.pooled_linear).
+_pooled_tail = None
+
+
+def set_pooled_tail(enabled: bool):
+    """switch the last-block + mean-pool shortcut off / on (default on; TAD_POOLED_TAIL=0 in the environment, read once, turns it off)"""
+    global _pooled_tail
+    _pooled_tail = bool(enabled)
+
+
+def get_pooled_tail() -> bool:
+    global _pooled_tail
+    if _pooled_tail is None:
+        import os
+        v = os.environ.get("TAD_POOLED_TAIL", "1").strip()
+        _pooled_tail = not (v.isdigit() and int(v) == 0)
+    return _pooled_tail
+
+
+def pooled_tail_ok(fc2_w) -> bool:
+    """the switch is on, the precision mode has 16-bit operands, and the shapes are ones the pooled-tail kernels take"""
+    return get_pooled_tail() and _PRECISION in ("fast", "half") and K.colsum_segments_ok(fc2_w.shape[1])
+
+
+class _PoolStats:
+    calls = 0  # forwards taken through BlockPoolFn (tests)
+
+
+def block_pool_apply(x, *args):
+    """BlockPoolFn.apply plus the chain bookkeeping on the input tensor object (the pooled output has no successor block)"""
+    prev = getattr(x, "_tad_link", None) if _chain.enabled else None
+    _PoolStats.calls += 1
+    return BlockPoolFn.apply(x, *args, prev, None)
+
+
+class BlockPoolFn(_Fn):
+    """mean over tokens of BlockFn's output: [B, N, D] -> [B, D] f32 (see above)."""
+
+    @staticmethod
+    def forward(ctx, x, n1w, n1b, qkv_w, q_bias, v_bias, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, dp1, dp2, H, scale,
+                eps, prev_link=None, link=None):
+        train, x1, a = _block_fwd_to_fc1(ctx, x, n1w, n1b, qkv_w, q_bias, v_bias, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b,
+                                         dp1, dp2, H, scale, eps, prev_link, link)
+        B, N, D = x.shape
+        S = K.colsum_segments(a, B, N)
+        xbar = K.meanpool_fwd(x1.view(B, N, D))
+        ctx.pool_S = S if train else None
+        # xbar + dp2 ((S / N) W2^T + b2) on the VALUES of the 16-bit operand copy of W2: the pooled operand is never rounded to 16 bits
+        return K.pooled_linear(S, w_bf16(fc2_w, train), _f32c(fc2_b), _f32c(dp2), xbar, N)
+
+    @staticmethod
+    def backward(ctx, dy):
+        st = ctx.saved_tensors
+        h, fc2_w, dp2 = st[13], st[18], st[20]
+        S = ctx.pool_S
+        B, N, D = ctx.meta[:3]
+        fc2_b = ctx.biases[2]
+        # the gradient of every output row: dy[b] / N, materialised for LN2's residual term by the kernel MeanPoolFn's backward runs;
+        # gb[b] = op16(dy[b] / N * dp2[b]) through the kernels BlockFn's backward casts it with: a row of its operand bit for bit
+        g, _ = K.meanpool_bwd(_f32c(dy), N)
+        g_rows = g[:, 0, :].contiguous()
+        gb = K.cast_bf16(g_rows) if dp2 is None else K.scale_cast_bf16(g_rows, None, dp2, 1)
+        t = K.linear_bwd_input(gb, wT_bf16(fc2_w, True), out_dtype=torch.float32)
+        dh = K.gelu_grad_bcast(t, h, N)
+        # dW2 = gb^T S, db2 = N sum_b gb[b]: f32 products of the 16-bit gb values and the f32 sums, into the gradient sinks as linear_dw does
+        gbf = gb.float()
+        sw = _sink(fc2_w)
+        sb = _sink(fc2_b) if fc2_b is not None else None
+        if sw is not None and (fc2_b is None or sb is not None):
+            sw[1].view(fc2_w.shape[0], -1).addmm_(gbf.t(), S)
+            if sb is not None:
+                sb[1].add_(gbf.sum(0), alpha=float(N))
+            for ent, prm in ((sw, fc2_w), (sb, fc2_b)):
+                if ent is not None and ent[2] is not None:
+                    ent[2](prm)
+            dW2, db2 = None, None
         else:
-            gin, _, dg1, dbeta1, _ = layernorm_bwd_sunk(dxn1, x0, g1, mean1, rstd1, n1w, n1b, dres=gmid)
-        return (gin.reshape(B, N, D), dg1, dbeta1, dWqkv, dqb, dvb, dWp, dbp, dg2, dbeta2, dW1, db1, dW2, db2, None, None, None, None,
-                None, None, None)
+            dW2 = torch.matmul(gbf.t(), S)
+            db2 = gbf.sum(0) * float(N) if fc2_b is not None else None
+        return _block_bwd_from_dh(ctx, st, g.view(B * N, D), dh, dW2, db2)
 
 
 # --------------------------------------------------------------------------- plain Linear (f32 rows in / out)
