@@ -363,6 +363,39 @@ int tad_colsum_bf16(const uint16_t* a, float* out, int accumulate, void* ws, siz
 /* y_bf16 = bf16(rowscale[m/rows_per_scale] * gamma[n] * x_f32)  (backward of the residual-branch scale) */
 int tad_scale_cast_bf16(const float* x, uint16_t* y, const float* gamma, const float* rowscale,
                         int rows_per_scale, int64_t M, int N, tad_stream_t stream);
+
+/* ---- fused Block variants: layer-scale (gamma_1 / gamma_2) and proj / MLP dropout (csrc/layerscale.hip) -------------------------------
+ * A branch y = res + s[b] gamma[c] keep[m,c] / (1 - p) u with u = a W^T + bias (modeling_finetune.py:159-166: proj_drop / Mlp.drop, then
+ * gamma, then drop path, then the residual add).  Its backward carries gamma in the WEIGHT operand: with gb = op16(s keep / (1 - p) g),
+ *   d a = gb (diag(gamma) W),   T = gb^T a,  cs = colsum(gb)   (one tad_linear_bwd_weight),
+ *   dW = gamma[n] T[n,:],   dbias = gamma cs,   dgamma[n] = sum_k T[n,k] W[n,k] + bias[n] cs[n]      -- u is never stored or recomputed.
+ *
+ * tad_rowscale_transpose_cast: w [N,K] f32, gamma [N] f32 -> out [K,N] 16-bit, out[k,n] = op16(fl32(gamma[n] w[n,k])) (the product rounded
+ * to f32, then to the operand format, nearest even): the scaled twin of tad_transpose_cast_f32_bf16, the wT operand of tad_linear_bwd_input.
+ * Any N, K > 0. */
+int tad_rowscale_transpose_cast(const float* w, const float* gamma, uint16_t* out, int N, int K, tad_stream_t stream);
+/* tad_layerscale_grads: T, W [N,K] f32; bias (nullable), cs (nullable unless bias or dbias is given), gamma [N] f32.
+ *   dW[n,k] (+)= fl32(gamma[n] T[n,k]);  dbias[n] (+)= fl32(gamma[n] cs[n]) (dbias nullable);  dgamma[n] (+)= sum_k T[n,k] W[n,k] + bias[n] cs[n].
+ * accumulate = 0 writes, 1 adds to what dW / dbias / dgamma hold (gradient sinks).  One workgroup per row; the k reduction runs in a fixed
+ * order without atomics: the same inputs give the same bits.  Any N, K > 0; 16-byte accesses when K % 4 == 0 and T, W, dW are 16-byte
+ * aligned.  dW must not alias T or W. */
+int tad_layerscale_grads(const float* T, const float* W, const float* bias, const float* cs, const float* gamma, float* dW, float* dbias,
+                         float* dgamma, int accumulate, int N, int K, tad_stream_t stream);
+/* The dropout mask of a branch output [M,D]: element (m, c) is kept iff hash32(m, c, seed) >= p * 2^32 (csrc/common.h: Drop / drop_keep
+ * with row = m, key = c -- the contract of attention dropout), kept values are scaled by inv_keep = 1.f / (1.f - p).  p in [0, 1); M < 2^32.
+ * rowscale (nullable) f32 [ceil(M / rows_per_scale)]: the per-clip drop-path scale.
+ * tad_branch_dropout_fwd:  out[m,c] = res[m,c] + u[m,c] * f,  f = fl32(gamma[c] * fl32(rowscale * inv_keep)) (gamma nullable: f = fl32(rowscale *
+ *   inv_keep)), for kept elements of rows whose rowscale is not 0; every other element is res[m,c] bit for bit (a select, not a product with 0:
+ *   a non-finite u does not leak, as in TAD_EPI_BIAS_RESIDUAL).  u comes from tad_linear_fwd with TAD_EPI_BIAS and f32 output.  out must
+ *   not alias res or u.
+ * tad_branch_dropout_cast: y[m,c] = op16(fl32(g[m,c] * fl32(rowscale * inv_keep))) for the same elements, +0 for every other one: the masked
+ *   twin of tad_scale_cast_bf16 (no gamma: it is folded into the weights, see above).
+ * Streaming, grid-stride; 16-byte accesses when D % 4 == 0 and the f32 tensors are 16-byte aligned (y: 8), element-wise otherwise. */
+int tad_branch_dropout_fwd(const float* u, const float* res, float* out, const float* gamma, const float* rowscale, int rows_per_scale,
+                           float p, uint32_t seed, int64_t M, int D, tad_stream_t stream);
+int tad_branch_dropout_cast(const float* g, uint16_t* y, const float* rowscale, int rows_per_scale, float p, uint32_t seed, int64_t M, int D,
+                            tad_stream_t stream);
+
 /* sum of squares of an f32 vector, accumulated into *out (f32, device) -- get_grad_norm_ (utils.py:415-427).  Deterministic: block
  * partials in ws (tad_sumsq_workspace_bytes()), added in a fixed order; no atomics. */
 size_t tad_sumsq_workspace_bytes(void);
@@ -850,6 +883,9 @@ int tad_adamw_step_f16(float* param, const float* grad, float* exp_avg, float* e
                        const uint8_t* chunk_group, int64_t n, const float* group_lr, const float* group_wd, int n_groups,
                        const int32_t* group_step, float beta1, float beta2, float eps, const float* grad_scale,
                        float* sumsq_partials, tad_stream_t stream);
+int tad_rowscale_transpose_cast_f16(const float* w, const float* gamma, uint16_t* out, int N, int K, tad_stream_t stream);
+int tad_branch_dropout_cast_f16(const float* g, uint16_t* y, const float* rowscale, int rows_per_scale, float p, uint32_t seed, int64_t M,
+                                int D, tad_stream_t stream);
 
 #ifdef __cplusplus
 }

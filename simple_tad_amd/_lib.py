@@ -61,6 +61,10 @@ SIGNATURES = {
     "tad_colsum_bf16": (_i, [_vp, _vp, _i, _vp, _sz, _i64, _i, _vp]),
     "tad_colsum_window_f32": (_i, [_vp, _vp, _i, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
     "tad_scale_cast_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _vp]),
+    "tad_rowscale_transpose_cast": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "tad_layerscale_grads": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "tad_branch_dropout_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, C.c_uint32, _i64, _i, _vp]),
+    "tad_branch_dropout_cast": (_i, [_vp, _vp, _vp, _i, _f, C.c_uint32, _i64, _i, _vp]),
     "tad_sumsq_workspace_bytes": (_sz, []),
     "tad_sumsq_f32": (_i, [_vp, _i64, _vp, _vp, _sz, _vp]),
     "tad_grad_norm_coef": (_i, [_vp, _i64, _f, _f, _vp, _vp, _sz, _vp]),
@@ -132,7 +136,11 @@ F16_TWINS = {
     "tad_attn_fwd": "tad_attn_fwd_f16", "tad_attn_bwd": "tad_attn_bwd_f16",
     "tad_meanpool_bwd": "tad_meanpool_bwd_f16", "tad_adamw_step": "tad_adamw_step_f16",
 }
-for _bf, _h in F16_TWINS.items():
+# the twins of the fused Block variants' kernels (csrc/layerscale.hip), a table of their own beside the 23 of the plain block
+VARIANT_F16_TWINS = {
+    "tad_rowscale_transpose_cast": "tad_rowscale_transpose_cast_f16", "tad_branch_dropout_cast": "tad_branch_dropout_cast_f16",
+}
+for _bf, _h in (*F16_TWINS.items(), *VARIANT_F16_TWINS.items()):
     SIGNATURES[_h] = SIGNATURES[_bf]
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL = 0, 1, 2
 ABI_VERSION = 5

@@ -26,3 +26,5 @@
 #define tad_attn_bwd tad_attn_bwd_f16
 #define tad_meanpool_bwd tad_meanpool_bwd_f16
 #define tad_adamw_step tad_adamw_step_f16
+#define tad_rowscale_transpose_cast tad_rowscale_transpose_cast_f16
+#define tad_branch_dropout_cast tad_branch_dropout_cast_f16

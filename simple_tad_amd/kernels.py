@@ -134,7 +134,9 @@ def operand_dtype():
 
 def _fn(name: str, dtype):
     """the entry point `name` for 16-bit operands of `dtype` (its _f16 twin for torch.float16)"""
-    return getattr(_lib.load(), _lib.F16_TWINS[name] if dtype == torch.float16 else name)
+    if dtype == torch.float16:
+        name = _lib.F16_TWINS.get(name) or _lib.VARIANT_F16_TWINS[name]
+    return getattr(_lib.load(), name)
 
 
 def _req16(t: torch.Tensor, name: str, like=None):
@@ -258,6 +260,94 @@ def scale_cast_op16(x, gamma=None, rowscale=None, rows_per_scale=1, dtype=None):
 
 
 scale_cast_bf16 = scale_cast_op16
+
+
+# ----------------------------------------------------------------------------- fused Block variants (csrc/layerscale.hip)
+def rowscale_transpose_cast(w, gamma, dtype=None):
+    """w [N,K] f32, gamma [N] f32 -> [K,N] 16-bit: op16(gamma[n] * w[n,k]), the wT operand of linear_bwd_input of a layer-scaled Linear"""
+    _req(w, torch.float32, "rowscale_transpose_cast.w")
+    _req(gamma, torch.float32, "rowscale_transpose_cast.gamma")
+    N, Kk = w.shape
+    if gamma.numel() != N:
+        raise _lib.TadError(f"rowscale_transpose_cast: gamma has {gamma.numel()} elements, w {N} rows")
+    out = torch.empty((Kk, N), dtype=dtype or _op16, device=w.device)
+    with _timed("cast", 0.0, 6.0 * N * Kk):
+        check(_fn("tad_rowscale_transpose_cast", out.dtype)(w.data_ptr(), gamma.data_ptr(), out.data_ptr(), N, Kk, _stream()),
+              "tad_rowscale_transpose_cast")
+    return out
+
+
+def layerscale_grads(T, W, bias, cs, gamma, dW=None, dbias=None, dgamma=None, accumulate=False):
+    """dW = gamma[n] T[n,:], dbias = gamma * cs (None without a bias), dgamma[n] = <T[n,:], W[n,:]> + bias[n] cs[n]; with ``dW`` / ``dbias`` /
+    ``dgamma`` given (all of them: gradient sinks) and ``accumulate`` they are added to.  Returns (dW, dbias|None, dgamma)."""
+    _req(T, torch.float32, "layerscale_grads.T")
+    _req(W, torch.float32, "layerscale_grads.W")
+    _req(gamma, torch.float32, "layerscale_grads.gamma")
+    N, Kk = T.shape
+    if tuple(W.shape) != (N, Kk) or gamma.numel() != N:
+        raise _lib.TadError(f"layerscale_grads: T {tuple(T.shape)}, W {tuple(W.shape)}, gamma {gamma.numel()}")
+    if bias is not None:
+        _req(bias, torch.float32, "layerscale_grads.bias")
+        if cs is None or bias.numel() != N:
+            raise _lib.TadError("layerscale_grads: a bias needs the column sums cs, both [N]")
+    if cs is not None:
+        _req(cs, torch.float32, "layerscale_grads.cs")
+        assert cs.numel() == N
+    given = [t is not None for t in (dW, dgamma)] + ([dbias is not None] if bias is not None else [])
+    if any(given) and not all(given):
+        raise _lib.TadError("layerscale_grads: give all of dW, dbias, dgamma or none")
+    if not any(given):
+        accumulate = False
+        dW = torch.empty((N, Kk), dtype=torch.float32, device=T.device)
+        dgamma = torch.empty(N, dtype=torch.float32, device=T.device)
+        dbias = torch.empty(N, dtype=torch.float32, device=T.device) if bias is not None else None
+    for t, n in ((dW, N * Kk), (dgamma, N)) + (((dbias, N),) if bias is not None else ()):
+        _req(t, torch.float32, "layerscale_grads.out")
+        assert t.numel() == n
+    if bias is None:
+        dbias = None
+    with _timed("cast", 2.0 * N * Kk, (16.0 if accumulate else 12.0) * N * Kk):
+        check(_lib.load().tad_layerscale_grads(T.data_ptr(), W.data_ptr(), _p(bias), _p(cs), gamma.data_ptr(), dW.data_ptr(), _p(dbias),
+                                               dgamma.data_ptr(), int(bool(accumulate)), N, Kk, _stream()), "tad_layerscale_grads")
+    return dW, dbias, dgamma
+
+
+def _req_rowscale(rowscale, rows_per_scale, M, name):
+    if rowscale is not None:
+        _req(rowscale, torch.float32, name + ".rowscale")
+        if rows_per_scale <= 0 or rowscale.numel() * rows_per_scale < M:
+            raise _lib.TadError(f"{name}: rowscale has {rowscale.numel()} entries of {rows_per_scale} rows for {M} rows")
+
+
+def branch_dropout_fwd(u, res, gamma=None, rowscale=None, rows_per_scale=1, p: float = 0.0, seed: int = 0):
+    """out f32 [M,D] = res + rowscale * gamma * keep / (1 - p) * u; keep[m,c] = hash32(m, c, seed) >= p * 2^32.  Rows whose rowscale is 0 and
+    dropped elements are ``res`` bit for bit."""
+    _req(u, torch.float32, "branch_dropout_fwd.u")
+    _req(res, torch.float32, "branch_dropout_fwd.res")
+    M, D = u.shape
+    if tuple(res.shape) != (M, D):
+        raise _lib.TadError(f"branch_dropout_fwd: u {tuple(u.shape)} vs res {tuple(res.shape)}")
+    if gamma is not None:
+        _req(gamma, torch.float32, "branch_dropout_fwd.gamma")
+        assert gamma.numel() == D
+    _req_rowscale(rowscale, rows_per_scale, M, "branch_dropout_fwd")
+    out = torch.empty((M, D), dtype=torch.float32, device=u.device)
+    with _timed("cast", 0.0, 12.0 * M * D):
+        check(_lib.load().tad_branch_dropout_fwd(u.data_ptr(), res.data_ptr(), out.data_ptr(), _p(gamma), _p(rowscale), int(rows_per_scale),
+                                                 float(p), int(seed) & 0xFFFFFFFF, M, D, _stream()), "tad_branch_dropout_fwd")
+    return out
+
+
+def branch_dropout_cast(g, rowscale=None, rows_per_scale=1, p: float = 0.0, seed: int = 0, dtype=None):
+    """op16(rowscale * keep / (1 - p) * g) [M,D]: scale_cast_op16 under the mask of branch_dropout_fwd (no gamma)"""
+    _req(g, torch.float32, "branch_dropout_cast.g")
+    M, D = g.shape
+    _req_rowscale(rowscale, rows_per_scale, M, "branch_dropout_cast")
+    out = torch.empty((M, D), dtype=dtype or _op16, device=g.device)
+    with _timed("cast", 0.0, 6.0 * M * D):
+        check(_fn("tad_branch_dropout_cast", out.dtype)(g.data_ptr(), out.data_ptr(), _p(rowscale), int(rows_per_scale), float(p),
+                                                         int(seed) & 0xFFFFFFFF, M, D, _stream()), "tad_branch_dropout_cast")
+    return out
 
 
 # ----------------------------------------------------------------------------- patch embed

@@ -190,6 +190,37 @@ class Block(nn.Module):
                      a.proj.bias, self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight,
                      m.fc2.bias, s1, s2, a.num_heads, a.scale, self.norm1.eps)
 
+    forced_drop_seeds = None  # (seed of the attention branch's mask, seed of the MLP branch's): tests inject them, like DropPath.forced_mask
+
+    def _branch_dropout(self):
+        """p of proj_drop / Mlp.drop when they are active in this forward (training), else 0"""
+        return float(self.mlp.drop.p) if self.training and (self.mlp.drop.p > 0 or self.attn.proj_drop.p > 0) else 0.0
+
+    def _variant_fusable(self):
+        """layer-scale and / or proj / MLP dropout through ops.BlockVariantFn: what keeps ``_fusable`` false apart from these two -- other
+        norms, attention dropout in training -- and the precise mode stay composed"""
+        return (ops.get_block_variants() and ops.get_precision() != "precise"
+                and isinstance(self.norm1, nn.LayerNorm) and isinstance(self.norm2, nn.LayerNorm)
+                and self.norm1.elementwise_affine and self.norm2.elementwise_affine and self.norm1.eps == self.norm2.eps
+                and not (self.training and self.attn.attn_drop.p > 0)
+                and (self.gamma_1 is not None or self._branch_dropout() > 0)
+                and (self.gamma_1 is None) == (self.gamma_2 is None) and 0 <= self.mlp.drop.p < 1
+                and self.mlp.drop.p == self.attn.proj_drop.p)
+
+    def _fused_variant(self, x):
+        p = self._branch_dropout()
+        seeds = (0, 0)
+        if p > 0:
+            # one seed per branch from torch's default (CPU) generator, as Attention._dropout draws its own: reproducible under
+            # torch.manual_seed, and redrawn identically by a checkpoint's recomputation (it restores the generator's state)
+            seeds = self.forced_drop_seeds or tuple(int(v) for v in torch.randint(0, 2 ** 31 - 1, (2,)).tolist())
+
+        def apply(x, *args):
+            *params, s1, s2, H, scale, eps = args
+            return ops.block_variant_apply(x, *params, self.gamma_1, self.gamma_2, p, seeds[0], seeds[1], s1, s2, H, scale, eps)
+
+        return self._fused(x, apply)
+
     def pools_fused(self):
         """may ``forward_pooled`` stand for ``forward(x).mean(1)``?  The fused 16-bit block, the switch on (ops.set_pooled_tail), and
         no hook on this module that would have to see the [B, N, D] output that is never formed."""
@@ -211,7 +242,9 @@ class Block(nn.Module):
                                      a.num_heads, a.scale, self.norm1.eps)
         if self._fusable():
             return self._fused(x, ops.block_apply)
-        # layer-scale / dropout variants: composed from the per-operator kernels
+        if self._variant_fusable():
+            return self._fused_variant(x)
+        # attention dropout in training, other norms, the precise mode, ops.set_block_variants(False): composed from the per-operator kernels
         n1 = ops.LayerNormFn.apply(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)
         n1 = self.attn(n1)
         if self.gamma_1 is not None:

@@ -722,6 +722,135 @@ def _block_bwd_from_dh(ctx, st, g, dh, dW2, db2):
             None, None, None)
 
 
+# --------------------------------------------------------------------------- fused Block variants: layer-scale, proj / MLP dropout
+# Block.forward with gamma_1 / gamma_2 (init_values > 0) and / or proj_drop / Mlp.drop active (drop_rate > 0, training)
+# (modeling_finetune.py:159-166).  Each residual branch is  y = res + s[b] gamma[c] keep[m,c] / (1 - p) u,  u = a W^T + bias:
+#   forward   without dropout the residual epilogue of the GEMM takes gamma (TAD_EPI_BIAS_RESIDUAL); with dropout the GEMM writes u in
+#             f32 and K.branch_dropout_fwd combines -- the mask is the counter-based hash of attention dropout over (row, column, seed);
+#   backward  gb = op16(s keep / (1 - p) g) carries NO gamma: d a = gb (diag(gamma) W) (K.rowscale_transpose_cast writes the operand),
+#             T = gb^T a and cs = colsum(gb) from one K.linear_bwd_weight, and K.layerscale_grads turns them into
+#             dW = gamma T, dbias = gamma cs, dgamma[n] = <T[n,:], W[n,:]> + bias[n] cs[n] -- u is neither stored nor recomputed.
+# Not here: attention dropout in training, the pooled tail and the block-chain hand-off, the precise mode.
+_block_variants = True
+block_variant_calls = 0  # forwards taken through BlockVariantFn (tests)
+
+
+def set_block_variants(enabled: bool):
+    """layer-scale / proj-MLP-dropout Blocks through BlockVariantFn (default) or, off, composed from the per-operator Functions"""
+    global _block_variants
+    _block_variants = bool(enabled)
+
+
+def get_block_variants() -> bool:
+    return _block_variants
+
+
+def block_variant_apply(x, *args):
+    global block_variant_calls
+    block_variant_calls += 1
+    return BlockVariantFn.apply(x, *args)
+
+
+def _branch_fwd(a, w, b, res, gamma, dp, N, train, p, seed):
+    """res + dp gamma dropout(a w^T + b) -> f32 [M,D]"""
+    if p > 0.0:
+        u, _ = K.linear_fwd(a, w_bf16(w, train), _f32c(b), out_dtype=torch.float32)
+        return K.branch_dropout_fwd(u, res, gamma, dp, N, p, seed)
+    y, _ = K.linear_fwd(a, w_bf16(w, train), _f32c(b), out_dtype=torch.float32, epilogue=EPI_BIAS_RESIDUAL, residual=res, gamma=gamma,
+                        rowscale=dp, rows_per_scale=N)
+    return y
+
+
+def _branch_wT(w, gamma):
+    """the [K,N] operand of the branch's input gradient: W^T, with gamma folded in for a layer-scaled branch"""
+    return wT_bf16(w, True) if gamma is None else K.rowscale_transpose_cast(_w2d(w), gamma)
+
+
+def _branch_dw(gb, a, w, b, gamma_p, gamma):
+    """(dW, db, dgamma) of a branch's Linear and layer-scale from gb (16-bit, scaled and masked, without gamma) and the Linear's input a;
+    None for what went into gradient sinks"""
+    if gamma_p is None:
+        return linear_dw(gb, a, w, b) + (None,)
+    T, cs = K.linear_bwd_weight(gb, a, want_bias=b is not None)
+    prms = (w, gamma_p) + ((b,) if b is not None else ())
+    ents = [_sink(q) for q in prms]
+    if all(e is not None for e in ents):
+        K.layerscale_grads(T, _w2d(w), _f32c(b), cs, gamma, dW=ents[0][1].view(w.shape[0], -1), dgamma=ents[1][1],
+                           dbias=ents[2][1] if b is not None else None, accumulate=True)
+        for ent, prm in zip(ents, prms):
+            if ent[2] is not None:
+                ent[2](prm)
+        return None, None, None
+    dW, db, dg = K.layerscale_grads(T, _w2d(w), _f32c(b), cs, gamma)
+    return dW.reshape(w.shape), db, dg
+
+
+class BlockVariantFn(_Fn):
+    """Block.forward with layer-scale and / or proj / MLP dropout (modeling_finetune.py:153-166):
+         x = x + dp1 * gamma_1 * proj_drop(attn(norm1(x)));  x = x + dp2 * gamma_2 * mlp_drop(mlp(norm2(x)))
+    gamma_1 / gamma_2: [D] or None; drop_p in [0, 1) with one mask seed per branch; dp1 / dp2 as in BlockFn."""
+
+    @staticmethod
+    def forward(ctx, x, n1w, n1b, qkv_w, q_bias, v_bias, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, gamma_1, gamma_2, drop_p,
+                seed_attn, seed_mlp, dp1, dp2, H, scale, eps):
+        _need_gpu(x, "Block")
+        B, N, D = x.shape
+        M = B * N
+        train = _differentiated(ctx)
+        p = float(drop_p)
+        x0 = _f32c(x).reshape(M, D)
+        g1, b1, g2, b2 = _f32c(n1w), _f32c(n1b), _f32c(n2w), _f32c(n2b)
+        gm1, gm2, s1, s2 = _f32c(gamma_1), _f32c(gamma_2), _f32c(dp1), _f32c(dp2)
+        xn1, mean1, rstd1 = K.layernorm_fwd(x0, g1, b1, eps, save_stats=train)
+        qkv, ao, (lse, ao_lo) = _attn_fwd_core(xn1, qkv_w, q_bias, v_bias, B, N, H, scale, train, rowscale=s1)
+        ctx.qpre = _attn_q_prescale
+        x1 = _branch_fwd(ao, proj_w, proj_b, x0, gm1, s1, N, train, p, int(seed_attn))
+        xn2, mean2, rstd2 = K.layernorm_fwd(x1, g2, b2, eps, save_stats=train)
+        a, h = K.linear_fwd(xn2, w_bf16(fc1_w, train), _f32c(fc1_b), out_dtype=None, epilogue=EPI_BIAS_GELU, want_preact=train)
+        x2 = _branch_fwd(a, fc2_w, fc2_b, x1, gm2, s2, N, train, p, int(seed_mlp))
+        if train:
+            ctx.save_for_backward(x0, g1, mean1, rstd1, xn1, qkv, ao, lse, x1, g2, mean2, rstd2, xn2, h, a, qkv_w, proj_w, fc1_w, fc2_w,
+                                  s1, s2, ao_lo, gm1, gm2)
+        ctx.meta = (B, N, D, H, scale, q_bias is not None, p, int(seed_attn), int(seed_mlp))
+        ctx.biases = (proj_b, fc1_b, fc2_b)
+        ctx.norms = (n1w, n1b, n2w, n2b)
+        ctx.qv = (q_bias, v_bias)
+        ctx.gammas = (gamma_1, gamma_2)
+        return x2.reshape(B, N, D)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x0, g1, mean1, rstd1, xn1, qkv, ao, lse, x1, g2, mean2, rstd2, xn2, h, a, qkv_w, proj_w, fc1_w, fc2_w, dp1, dp2, ao_lo, gm1,
+         gm2) = ctx.saved_tensors
+        B, N, D, H, scale, has_qb, p, seed_attn, seed_mlp = ctx.meta
+        proj_b, fc1_b, fc2_b = ctx.biases
+        n1w, n1b, n2w, n2b = ctx.norms
+        gamma_1, gamma_2 = ctx.gammas
+        g = _f32c(g).reshape(B * N, D)
+        # ---- MLP branch
+        if p > 0.0:
+            gb = K.branch_dropout_cast(g, dp2, N, p, seed_mlp)
+        else:
+            gb = K.cast_bf16(g) if dp2 is None else K.scale_cast_bf16(g, None, dp2, N)
+        dh = K.linear_bwd_input(gb, _branch_wT(fc2_w, gm2), gelu_preact=h)
+        dW2, db2, dgm2 = _branch_dw(gb, a, fc2_w, fc2_b, gamma_2, gm2)
+        dxn2 = K.linear_bwd_input(dh, wT_bf16(fc1_w, True))
+        dW1, db1 = linear_dw(dh, xn2, fc1_w, fc1_b)
+        # LN2 backward emits op16(dp1 * residual-stream gradient) on the side; under dropout the masked copy needs a pass of its own
+        gmid, gpb, dg2, dbeta2, _ = layernorm_bwd_sunk(dxn2, x1, g2, mean2, rstd2, n2w, n2b, dres=g, want_bf16=p == 0.0, rowscale=dp1,
+                                                     rows_per_scale=N)
+        if p > 0.0:
+            gpb = K.branch_dropout_cast(gmid, dp1, N, p, seed_attn)
+        # ---- attention branch
+        d_ao = K.linear_bwd_input(gpb, _branch_wT(proj_w, gm1))
+        dWp, dbp, dgm1 = _branch_dw(gpb, ao, proj_w, proj_b, gamma_1, gm1)
+        dxn1, dWqkv, dqb, dvb = _attn_bwd_core(d_ao, xn1, qkv, ao, lse, qkv_w, has_qb, B, N, H, scale, None, ctx.qv, ao_lo=ao_lo,
+                                               q_prescaled=ctx.qpre, rowscale=dp1)
+        gin, _, dg1, dbeta1, _ = layernorm_bwd_sunk(dxn1, x0, g1, mean1, rstd1, n1w, n1b, dres=gmid)
+        return (gin.reshape(B, N, D), dg1, dbeta1, dWqkv, dqb, dvb, dWp, dbp, dg2, dbeta2, dW1, db1, dW2, db2, dgm1, dgm2, None, None,
+                None, None, None, None, None, None)
+
+
 # --------------------------------------------------------------------------- last Block + mean-pool
 # The fine-tuning model ends with fc_norm(mean over tokens(last block's output)).  x2 = x1 + dp2 (a W2^T + b2) is linear in a and
 # nothing but the token mean reads it, so
