@@ -80,6 +80,14 @@ int tad_im2col_tubelets(const float* x, uint16_t* cols, int B, int C, int T, int
 int tad_patch_embed_fwd(const float* x, const uint16_t* w_bf16, const float* bias, const float* pos,
                         float* out, uint16_t* cols, int B, int C, int T, int H, int W, int tubelet,
                         int patch, int D, tad_stream_t stream);
+/* The same patch matrix from a clip that already is in the 16-bit operand format (a loader that ships bf16 / half clips): x [B,C,T,H,W]
+ * 16-bit contiguous -> cols [B*N, tad_patch_embed_ldk(C, tubelet, patch)], word (b, c, t, h, w) at row n = ((b T' + t') H' + h') W' + w',
+ * column k = ((c*tub+kt)*p+kh)*p+kw, padding columns zero.  A MOVE of 16-bit words: no cast, every bit pattern (NaN payloads, subnormals)
+ * arrives unchanged, so one entry point serves both formats (there is no _f16 twin) and cols is bit-identical to tad_im2col_tubelets(_f16)
+ * on the upcast clip.  Patch sizes that are multiples of 8 move 16-byte chunks: x and cols 16-byte aligned; other even sizes move 4-byte
+ * words: x and cols 4-byte aligned (TAD_EINVAL otherwise). */
+int tad_im2col_tubelets_16(const uint16_t* x, uint16_t* cols, int B, int C, int T, int H, int W, int tubelet, int patch,
+                           tad_stream_t stream);
 /* The same forward as an IMPLICIT GEMM: the x operand is read straight from the f32 clip (register-staged, rounded to the
  * operand format as tad_im2col_tubelets rounds it), no patch matrix is written -- for forwards that keep nothing for a backward pass (eval,
  * no_grad, inference); the training step uses tad_patch_embed_fwd, whose patch matrix the weight gradient reads again.  Bit-identical to

@@ -1,6 +1,7 @@
 // The patch matrix of the tubelet embedding (Conv3d k = s = (tub, p, p) as a GEMM), every way the library builds it:
 //   tad_im2col_tubelets (+ _f16)     f32 clip  [B,C,T,H,W]                      -> 16-bit cols
 //   tad_im2col_tubelets_f32          f32 clip  [B,C,T,H,W]                      -> f32 cols (precise mode)
+//   tad_im2col_tubelets_16           16-bit clip [B,C,T,H,W] (either format)    -> the same 16-bit words in cols (a move: no cast, no twin)
 //   tad_im2col_tubelets_u8 (+ _f16)  uint8 clips [B,T,H,W,3], a ring per clip   -> normalised 16-bit cols
 //   tad_im2col_frame_windows         uint8 store [F,H,W,3] + slot table [B,T]   -> normalised 16-bit cols
 // cols [B*N, ldk]: pixel (b, t, h, w) of channel c lands in row n = ((b T' + t') H' + h') W' + w' (t' = t / tub, ...) at column
@@ -103,6 +104,46 @@ __global__ void f32_pairs_kernel(const float* __restrict__ x, out_t<FMT>* __rest
     if constexpr (FMT == TAD_F32) *reinterpret_cast<float2*>(row + k) = a;
     else *reinterpret_cast<uint32_t*>(row + k) = pack16x2<FMT>(a.x, a.y);
     if (k == 0) zero_padding<FMT>(row, K, ldk);
+  }
+}
+
+// ---------------------------------------------------------------- 16-bit clip
+// The clip already is in the operand format (a loader's wire format, prefetch.ClipPrefetcher wire="operand"): the patch matrix is a permutation
+// of its 16-bit words, so nothing here knows the format -- NaN payloads and subnormals pass as they are.  One item = 8 consecutive w of one
+// (b, c, t, h) row: one 16-byte load, one 16-byte store (item i is bytes [16 i, 16 i + 16) of the clip; the 8 words stay inside one patch row
+// because p % 8 == 0, so the store is 16-byte aligned in a row of K = C tub p p words, K % 64 == 0).
+__global__ void w16_wide_kernel(const uint16_t* __restrict__ x, uint16_t* __restrict__ cols, int B, int C, int T, int H, int W, int tub, int p) {
+  const int W8 = W >> 3;
+  const int64_t total = (int64_t)B * C * T * H * W8;
+  const PatchGrid g(T, H, W, tub, p);
+  const int K = C * tub * p * p;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    int64_t r = i;
+    const int w = peel(r, W8) * 8, h = peel(r, H), t = peel(r, T), c = peel(r, C), b = (int)r;
+    const uint4 a = reinterpret_cast<const uint4*>(x)[i];
+    const Cell q = g.cell(b, t, h, w);
+    *reinterpret_cast<uint4*>(cols + q.n * K + g.k(q, c)) = a;
+  }
+}
+
+// One item = 2 consecutive w = one 4-byte word in and out.
+__global__ void w16_pairs_kernel(const uint16_t* __restrict__ x, uint16_t* __restrict__ cols, int B, int C, int T, int H, int W, int tub, int p,
+                                 int ldk) {
+  const int W2 = W >> 1;
+  const int64_t total = (int64_t)B * C * T * H * W2;
+  const PatchGrid g(T, H, W, tub, p);
+  const int K = C * tub * p * p;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    int64_t r = i;
+    const int w = peel(r, W2) * 2, h = peel(r, H), t = peel(r, T), c = peel(r, C), b = (int)r;
+    const uint32_t a = reinterpret_cast<const uint32_t*>(x)[i];
+    const Cell q = g.cell(b, t, h, w);
+    const int k = g.k(q, c);
+    uint16_t* row = cols + q.n * ldk;
+    *reinterpret_cast<uint32_t*>(row + k) = a;
+    if (k == 0) zero_padding<TAD_BF16>(row, K, ldk);  // (zero words: the same in both 16-bit formats)
   }
 }
 
@@ -224,6 +265,22 @@ static int from_f32(const char* who, const float* x, void* cols, int B, int C, i
   return check_launch(who);
 }
 
+static int from_16(const char* who, const uint16_t* x, uint16_t* cols, int B, int C, int T, int H, int W, int tubelet, int patch,
+                   tad_stream_t stream) {
+  if (int rc = check_args(who, x, cols, B, C, T, H, W, tubelet, patch)) return rc;
+  const uintptr_t mask = patch % 8 ? 3 : 15;  // pairs move 4-byte words, wide items 16-byte chunks
+  TAD_REQUIRE((((uintptr_t)x) & mask) == 0 && (((uintptr_t)cols) & mask) == 0, "%s: misaligned buffers (x and cols %d bytes for patch %d)", who,
+              (int)mask + 1, patch);
+  const int64_t pixels = (int64_t)B * C * T * H * W;
+  if (patch % 8)
+    hipLaunchKernelGGL(w16_pairs_kernel, dim3(capped_grid(pixels / 2, 256)), dim3(256), 0, (hipStream_t)stream, x, cols, B, C, T, H, W, tubelet,
+                       patch, tad_patch_embed_ldk(C, tubelet, patch));
+  else
+    hipLaunchKernelGGL(w16_wide_kernel, dim3(capped_grid(pixels / 8, 256)), dim3(256), 0, (hipStream_t)stream, x, cols, B, C, T, H, W, tubelet,
+                       patch);
+  return check_launch(who);
+}
+
 // (the caller has checked its arguments)
 template <int FMT, typename Slots>
 static int from_u8(const char* who, const uint8_t* frames, Slots slots, uint16_t* cols, int B, int T, int H, int W, int tubelet, int patch,
@@ -262,6 +319,10 @@ int tad_im2col_tubelets_f16(const float* x, uint16_t* cols, int B, int C, int T,
 }
 int tad_im2col_tubelets_f32(const float* x, float* cols, int B, int C, int T, int H, int W, int tubelet, int patch, tad_stream_t stream) {
   return from_f32<TAD_F32>("im2col_f32", x, cols, B, C, T, H, W, tubelet, patch, stream);
+}
+
+int tad_im2col_tubelets_16(const uint16_t* x, uint16_t* cols, int B, int C, int T, int H, int W, int tubelet, int patch, tad_stream_t stream) {
+  return from_16("im2col_16", x, cols, B, C, T, H, W, tubelet, patch, stream);
 }
 
 int tad_im2col_tubelets_u8(const uint8_t* frames, uint16_t* cols, int B, int T, int H, int W, int tubelet, int patch, const float* mean3,

@@ -381,6 +381,21 @@ def im2col_tubelets(x: torch.Tensor, tubelet: int, patch: int, dtype=None) -> to
     return cols
 
 
+def im2col_tubelets_16(x: torch.Tensor, tubelet: int, patch: int) -> Optional[torch.Tensor]:
+    """x [B,C,T,H,W] bf16 / half -> the patch matrix in the same format, a move of 16-bit words (tad_im2col_tubelets_16).  Returns None
+    when x is a view whose address the kernel's loads cannot take (16 bytes for patch sizes that are multiples of 8, else 4): the caller
+    then goes through the f32 route, as for the implicit patch embedding -- it is a choice between two equal results, not an error."""
+    op = _req16(x, "im2col_16.x")
+    B, Cc, T, H, W = x.shape
+    if x.data_ptr() % (4 if patch % 8 else 16):
+        return None
+    _, cols = _patch_matrix(B, Cc, T, H, W, tubelet, patch, op, x.device)
+    with _timed("im2col_16", 0.0, 2.0 * x.numel() + 2.0 * cols.numel()):
+        check(_lib.load().tad_im2col_tubelets_16(x.data_ptr(), cols.data_ptr(), B, Cc, T, H, W, tubelet, patch, _stream()),
+              "tad_im2col_tubelets_16")
+    return cols
+
+
 def im2col_tubelets_u8(frames: torch.Tensor, tubelet: int, patch: int, mean, std, bgr: bool = False, t_offset: int = 0, dtype=None) -> torch.Tensor:
     """frames [B,T,H,W,3] uint8 -> normalised bf16 patch matrix [B*N, 3*tub*p*p] (tad_im2col_tubelets_u8)"""
     _req(frames, torch.uint8, "im2col_u8.frames")

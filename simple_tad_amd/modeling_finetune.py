@@ -316,6 +316,10 @@ class PatchEmbed(nn.Module):
             raise TadError("PatchEmbed: only square patches have a kernel")
         if ops.get_precision() == "precise":
             return ops.precise_patch_embed(x, self.proj.weight, self.proj.bias, pos_embed, self.tubelet_size, self.patch_size[0])
+        if x.dtype == ops.K.operand_dtype():
+            # a clip already in the operand format moves into the patch matrix as it is; the other 16-bit format (and any under
+            # "precise") takes the upcast route below
+            return ops.PatchEmbed16Fn.apply(x, self.proj.weight, self.proj.bias, pos_embed, self.tubelet_size, self.patch_size[0])
         return ops.PatchEmbedFn.apply(x, self.proj.weight, self.proj.bias, pos_embed, self.tubelet_size, self.patch_size[0])
 
 

@@ -361,6 +361,31 @@ class PatchEmbedFn(_Fn):
         return (None,) + _patch_embed_backward(ctx, dy, 3)  # x | weight, bias | pos, tubelet, patch
 
 
+class PatchEmbed16Fn(_Fn):
+    """PatchEmbed on a clip [B,C,T,H,W] that already is in the current 16-bit operand format (a loader that ships bf16 / half clips:
+    prefetch.ClipPrefetcher wire="operand"): the patch matrix is a move of the clip's words (K.im2col_tubelets_16) -- the same bits as
+    PatchEmbedFn on the upcast clip without its f32 round trip; the same saved ``cols`` and the same backward.  Always the explicit route:
+    the implicit GEMM reads f32 clips only."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, pos, tubelet, patch):
+        _need_gpu(x, "PatchEmbed")
+        xc = x.detach()
+        xc = xc if xc.is_contiguous() else xc.contiguous()
+        cols = K.im2col_tubelets_16(xc, tubelet, patch)
+        if cols is None:  # a misaligned view: the f32 route computes the same patch matrix
+            cols = K.im2col_tubelets(xc.float(), tubelet, patch, dtype=xc.dtype)
+        ntok = (xc.shape[2] // tubelet) * (xc.shape[3] // patch) * (xc.shape[4] // patch)
+        out = K.patch_embed_gemm(cols, K.pad_k(w_bf16(weight, _differentiated(ctx)), cols.shape[1]), _f32c(bias), _f32c(pos), ntok)
+        ctx.save_for_backward(cols)
+        ctx.params = (weight, bias)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        return (None,) + _patch_embed_backward(ctx, dy, 3)  # x | weight, bias | pos, tubelet, patch
+
+
 class PatchEmbedU8Fn(_Fn):
     """PatchEmbed on uint8 frames [B,T,H,W,3]: normalisation (run_inference.py:15-34; dota.py:443-460) fused into the im2col."""
 
