@@ -328,6 +328,17 @@ int tad_attn_debug_stamps(void* buf);
 int tad_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* out_lo, const uint16_t* dout, const float* lse,
                  const float* clip_scale, uint16_t* dqkv, float* delta, int B, int N, int H, int d, float scale, int q_prescaled,
                  float dropout_p, uint32_t seed, tad_stream_t stream);
+/* Weighted column sum of the softmax matrix, recomputed from qkv and lse with no N x N tensor (csrc/attn_colsum.hip):
+ *   out[b,h,j] = sum_{i<N} w[b,i] * exp(scale * q_{b,h,i} . k_{b,h,j} - lse[b,h,i])
+ * -- one step of attention rollout when only a row vector is propagated (simple_tad_amd/explain.py); w = 1/N gives the attention each
+ * token receives, a one-hot w one row of P.  qkv [B,N,3,H,d], d = 64 or 80, and q_prescaled exactly as tad_attn_fwd takes them (the v
+ * third is not read).  One entry point for both operand formats: op_dtype is TAD_BF16 or TAD_F16 (there is no _f16 twin).
+ * lse [B,H,N] f32 is used AS HANDED (tad_attn_fwd's, natural log); it is not recomputed.  w [B,N] f32, any sign.  out [B,H,N] f32, fully
+ * overwritten.  P and the sums stay f32 (no 16-bit rounding of P); fixed summation order, no atomics: bit-reproducible.  A clip is computed
+ * from its own rows of qkv, lse and w alone: nothing behind them is read, and a non-finite value in another clip cannot reach it.
+ * TAD_EINVAL: null pointer, d not 64 / 80, unknown op_dtype, B, N or H < 1, scale <= 0, qkv of 4 GiB or more. */
+int tad_attn_colsum(const uint16_t* qkv, int op_dtype, const float* lse, const float* w, float* out, int B, int N, int H, int d,
+                    float scale, int q_prescaled, tad_stream_t stream);
 
 /* ---- token mean-pool x.mean(1) (modeling_finetune.py:325-326) -------------------------
  * x [B,N,D] f32 -> y [B,D] f32.  ws: B*TAD_POOL_SPLIT*D floats. */

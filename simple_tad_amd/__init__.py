@@ -10,6 +10,8 @@ from . import mixup, loss, random_erasing, rand_augment, transforms, spatial_sam
 from .grad_norms import GradNormCollector
 from . import sequencing, frame_store, frame_resize, prefetch
 from .prefetch import ClipPrefetcher
+from . import explain
+from .explain import attention_rollout, attention_received, token_rollout, saliency_to_frames
 from .frame_resize import PadWideClips, resize_frames
 from .frame_store import FrameStore, FrameWindows, StoreViews
 from .mixup import Mixup
@@ -23,4 +25,4 @@ from .modeling_finetune import (VisionTransformer, PatchEmbed, Block, Attention,
                                 get_sinusoid_encoding_table)
 
 __all__ = ["set_precision", "get_precision", "TuningScope", "create_model", "register_model", "list_models", "modeling_finetune", "VisionTransformer", "PatchEmbed", "Block",
-           "Attention", "Mlp", "DropPath", "get_sinusoid_encoding_table", "mixup", "loss", "random_erasing", "rand_augment", "Mixup", "RandomErasing", "RandAugment", "create_random_augment", "rand_augment_transform", "frames_to_clip", "transforms", "GroupMultiScaleCrop", "DataAugmentationForVideoMAE", "DataAugmentationForVideoMAE_LightCrop", "spatial_sampling", "SpatialSampling", "SoftTargetCrossEntropy", "LabelSmoothingCrossEntropy", "FocalLoss", "FocalLoss2", "SmoothAPLoss", "TemporalExponentialLoss", "DoubleBCELoss", "build_criterion", "frame_targets", "grad_norms", "GradNormCollector", "sequencing", "frame_store", "frame_resize", "PadWideClips", "resize_frames", "FrameStore", "FrameWindows", "StoreViews", "prefetch", "ClipPrefetcher"]
+           "Attention", "Mlp", "DropPath", "get_sinusoid_encoding_table", "mixup", "loss", "random_erasing", "rand_augment", "Mixup", "RandomErasing", "RandAugment", "create_random_augment", "rand_augment_transform", "frames_to_clip", "transforms", "GroupMultiScaleCrop", "DataAugmentationForVideoMAE", "DataAugmentationForVideoMAE_LightCrop", "spatial_sampling", "SpatialSampling", "SoftTargetCrossEntropy", "LabelSmoothingCrossEntropy", "FocalLoss", "FocalLoss2", "SmoothAPLoss", "TemporalExponentialLoss", "DoubleBCELoss", "build_criterion", "frame_targets", "grad_norms", "GradNormCollector", "sequencing", "frame_store", "frame_resize", "PadWideClips", "resize_frames", "FrameStore", "FrameWindows", "StoreViews", "prefetch", "ClipPrefetcher", "explain", "attention_rollout", "attention_received", "token_rollout", "saliency_to_frames"]

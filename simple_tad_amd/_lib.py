@@ -53,6 +53,7 @@ SIGNATURES = {
     "tad_attn_bwd_scratch_bytes": (_sz, [_i, _i, _i]),
     "tad_attn_debug_stamps": (_i, [_vp]),
     "tad_attn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _f, C.c_uint32, _vp]),
+    "tad_attn_colsum": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
     "tad_meanpool_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "tad_meanpool_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "tad_colsum_segments": (_i, [_vp, _i, _vp, _vp, _sz, _i, _i, _i, _vp]),

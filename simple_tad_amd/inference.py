@@ -29,7 +29,7 @@ IMAGENET_STD = (0.229, 0.224, 0.225)
 
 @torch.no_grad()
 def score_video(model: torch.nn.Module, frames, *, orig_fps: int, target_fps: int, view_step: int = 1, sequencer=None, batch_size: int = 32,
-                mean=IMAGENET_MEAN, std=IMAGENET_STD, bgr: bool = False, resize: bool = False) -> dict:
+                mean=IMAGENET_MEAN, std=IMAGENET_STD, bgr: bool = False, resize: bool = False, saliency: Optional[str] = None) -> dict:
     """The anomaly score of every window of a video, batched: ``frames`` (uint8 [F,H,W,3], numpy or tensor, at the model's input size) is
     uploaded ONCE into a ``frame_store.FrameStore``; its windows come from ``sequencer`` (default: the reference datasets'
     ``RegularSequencer(target_fps, model.num_frames, view_step)``, dota.py:209) as a table of slots, and the model runs ``batch_size``
@@ -40,7 +40,11 @@ def score_video(model: torch.nn.Module, frames, *, orig_fps: int, target_fps: in
     the frames: F * H * W * 3, against S * T * H * W * 3 when every window is uploaded as a clip.  Each window's logits are those of running the model on that window's frames as a
     uint8 clip at the same batch size, bit for bit.  ``resize=True``: ``frames`` are as decoded, [F,h,w,3] of any size; they are uploaded
     raw and resized to the model's input size on the device (``FrameStore.append_resized``: run_inference.py:76's cv2 INTER_CUBIC
-    resize), and ``"bytes_uploaded"`` counts the raw bytes."""
+    resize), and ``"bytes_uploaded"`` counts the raw bytes.  ``saliency="rollout"`` | ``"received"``: the result gains ``"saliency"``, f32
+    [S, T/tubelet, gh, gw] on the host -- where each window looks (``explain.attention_rollout``; the attention received per token in the last
+    layer, averaged over the heads); the logits are those of the call without it, bit for bit."""
+    if saliency not in (None, "rollout", "received"):
+        raise ValueError(f'saliency must be None, "rollout" or "received", got {saliency!r}')
     from .frame_store import FrameStore
     from .sequencing import BasicLabeledSequencer_Abs, RegularSequencer
     pe = model.patch_embed
@@ -60,18 +64,33 @@ def score_video(model: torch.nn.Module, frames, *, orig_fps: int, target_fps: in
     nc = int(model.num_classes)
     if windows is None:
         return {"frame": torch.zeros(0, dtype=torch.int64), "logits": torch.zeros((0, nc), dtype=torch.float32),
-                "prob": torch.zeros(0, dtype=torch.float32), "bytes_uploaded": store.bytes_uploaded}
+                "prob": torch.zeros(0, dtype=torch.float32), "bytes_uploaded": store.bytes_uploaded,
+                **({"saliency": torch.zeros((0,) + _token_grid(model), dtype=torch.float32)} if saliency else {})}
     table = np.asarray(windows, dtype=np.int64)
     pe.set_input_normalization(mean, std, bgr=bgr)
     was_training = model.training
     model.eval()
     try:
-        outs = [model(store.windows(table[lo:lo + int(batch_size)])) for lo in range(0, len(table), int(batch_size))]
+        batches = (store.windows(table[lo:lo + int(batch_size)]) for lo in range(0, len(table), int(batch_size)))
+        if saliency is None:
+            outs, maps = [model(fw) for fw in batches], None
+        else:
+            from . import explain
+            run = explain.attention_rollout if saliency == "rollout" else explain.attention_received_map
+            outs, maps = (list(t) for t in zip(*(run(model, fw) for fw in batches)))
     finally:
         model.train(was_training)
     logits = torch.cat(outs, dim=0).float()
     prob = torch.softmax(logits, dim=1)[:, 1]
-    return {"frame": torch.from_numpy(table[:, -1].copy()), "logits": logits.cpu(), "prob": prob.cpu(), "bytes_uploaded": store.bytes_uploaded}
+    res = {"frame": torch.from_numpy(table[:, -1].copy()), "logits": logits.cpu(), "prob": prob.cpu(), "bytes_uploaded": store.bytes_uploaded}
+    if maps is not None:
+        res["saliency"] = torch.cat(maps, dim=0).float().cpu()
+    return res
+
+
+def _token_grid(model):
+    from .explain import token_grid
+    return token_grid(model)
 
 
 class SlidingWindow:

@@ -870,6 +870,25 @@ def attn_bwd(qkv, out, dout, lse, B: int, N: int, H: int, scale: float, out_lo=N
     return dqkv
 
 
+def attn_colsum(qkv, lse, w, B: int, N: int, H: int, scale: float, q_prescaled=False, d: int = 64):
+    """out[b,h,j] = sum_i w[b,i] * P[b,h,i,j] with P = exp(scale q.k - lse) recomputed from qkv [B*N, 3*H*d] (as attn_fwd takes it) and the
+    lse [B,H,N] it is handed; w [B,N] f32 -> out [B,H,N] f32.  No N x N tensor, f32 throughout, bit-reproducible (tad_attn_colsum)"""
+    op = _req16(qkv, "attn_colsum.qkv")
+    _req(lse, torch.float32, "attn_colsum.lse")
+    _req(w, torch.float32, "attn_colsum.w")
+    if qkv.numel() != B * N * 3 * H * d:
+        raise _lib.TadError(f"attn_colsum: qkv has {qkv.numel()} elements, expected {B * N * 3 * H * d}")
+    if lse.numel() != B * H * N or w.numel() != B * N:
+        raise _lib.TadError(f"attn_colsum: lse has {lse.numel()} elements and w {w.numel()}, expected {B * H * N} and {B * N}")
+    if lse.device != qkv.device or w.device != qkv.device:
+        raise _lib.TadError("attn_colsum: qkv, lse and w must live on one device")
+    out = torch.empty((B, H, N), dtype=torch.float32, device=qkv.device)
+    with _timed("attn_colsum", 2.0 * B * H * N * N * d, 2.0 * 2 * B * N * H * d + 4.0 * (2 * B * H * N + B * N)):
+        check(_lib.load().tad_attn_colsum(qkv.data_ptr(), _dt(qkv), lse.data_ptr(), w.data_ptr(), out.data_ptr(), B, N, H, int(d), float(scale),
+                                          int(bool(q_prescaled)), _stream()), "tad_attn_colsum")
+    return out
+
+
 # ----------------------------------------------------------------------------- mean-pool
 def meanpool_fwd(x):
     _req(x, torch.float32, "meanpool.x")

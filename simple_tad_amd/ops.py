@@ -11,6 +11,7 @@ The residual stream stays f32 (as under torch autocast); GEMM / attention operan
 """
 from __future__ import annotations
 
+import contextlib
 import threading
 import weakref
 from typing import Optional
@@ -466,14 +467,52 @@ def set_attn_hd80_f32(on: bool):
     _attn_hd80_f32 = bool(on)
 
 
+_attn_capture = None  # the list of the active capture_attention(), or None
+
+
+def attention_capture_active() -> bool:
+    return _attn_capture is not None
+
+
+@contextlib.contextmanager
+def capture_attention(model=None):
+    """Context manager that yields a list; while it is active every attention call of an evaluation forward (all block routes go through
+    ``_attn_fwd_core``) appends one record ``(qkv, lse, B, N, H, d, scale, q_prescaled)``: what ``kernels.attn_colsum`` needs to recompute
+    that layer's softmax (simple_tad_amd/explain.py).  lse is a nullable output of the same forward kernel, so the logits under capture are
+    those of the plain evaluation forward, bit for bit.  Evaluation only: raises TadError in "precise" mode, when grad is enabled, when the
+    model (``model``, if given, at entry; otherwise its attention modules as they run) is in training mode, on the set_attn_hd80_f32 route
+    (qkv is f32 there), and when a capture is already active (captures do not nest)."""
+    global _attn_capture
+    if _attn_capture is not None:
+        raise TadError("capture_attention: a capture is already active (captures do not nest)")
+    if _PRECISION == "precise":
+        raise TadError('capture_attention: precision "precise" runs the f32 attention kernels, which keep no 16-bit qkv to recompute from')
+    if torch.is_grad_enabled():
+        raise TadError("capture_attention: evaluation only; wrap the call in torch.no_grad()")
+    if model is not None and model.training:
+        raise TadError("capture_attention: the model is in training mode (call model.eval(): the records are those of the evaluation forward)")
+    records = []
+    _attn_capture = records
+    try:
+        yield records
+    finally:
+        _attn_capture = None
+
+
 def _attn_fwd_core(xn, qkv_w, q_bias, v_bias, B, N, H, scale, train, drop=(0.0, 0), rowscale=None):
     """returns qkv, attention output, (lse, rounding residual of the output | None).  drop = (p, seed) of attention dropout.
     rowscale: the per-clip drop-path scale [B] of the residual behind the branch (K.attn_fwd)."""
-    qb = None if q_bias is None else _f32c(q_bias.detach())
-    vb = None if v_bias is None else _f32c(v_bias.detach())
     hd = head_dim_of(qkv_w, H)
     if hd not in (64, 80):
         raise TadError(f"attention: head_dim {hd} has no kernel (64 and 80 do)")
+    cap = _attn_capture
+    if cap is not None:  # (refusals before any device work)
+        if train or _PRECISION == "precise" or drop[0] > 0:
+            raise TadError("capture_attention: evaluation only (no grad, no training mode, not the precise mode)")
+        if hd == 80 and _attn_hd80_f32:
+            raise TadError("capture_attention: the set_attn_hd80_f32 route keeps an f32 qkv; attn_colsum reads 16-bit operands")
+    qb = None if q_bias is None else _f32c(q_bias.detach())
+    vb = None if v_bias is None else _f32c(v_bias.detach())
     if hd == 80 and _attn_hd80_f32:
         # The round-3 route for the "huge" configurations (head_dim 80, modeling_finetune.py:390-398), kept for A/B runs
         # (set_attn_hd80_f32): the Linears stay on the 16-bit MFMA GEMMs, the scaled-dot-product core runs through the exact-f32 MFMA
@@ -485,8 +524,10 @@ def _attn_fwd_core(xn, qkv_w, q_bias, v_bias, B, N, H, scale, train, drop=(0.0, 
     # get their scores from the matrix pipe in log2 units and spend no vector instruction on the scale (the q third of `qkv` is NOT
     # the plain q; only tad_attn_fwd / tad_attn_bwd read it)
     qkv = K.linear_fwd_qkv(xn, w_bf16(qkv_w, train), qb, vb, out_dtype=None, q_prescale=K.q_prescale_of(scale) if _attn_q_prescale else 1.0)
-    r = K.attn_fwd(qkv, B, N, H, scale, out_dtype=None, want_lse=train, want_lo=train and _attn_exact_delta, q_prescaled=_attn_q_prescale,
-                   drop_p=drop[0], seed=drop[1], d=hd, rowscale=rowscale)
+    r = K.attn_fwd(qkv, B, N, H, scale, out_dtype=None, want_lse=train or cap is not None, want_lo=train and _attn_exact_delta,
+                   q_prescaled=_attn_q_prescale, drop_p=drop[0], seed=drop[1], d=hd, rowscale=rowscale)
+    if cap is not None:
+        cap.append((qkv, r[1], B, N, H, hd, float(scale), bool(_attn_q_prescale)))
     return qkv, r[0], (r[1], r[2] if len(r) > 2 else None)
 
 
