@@ -21,6 +21,22 @@
  *   - "bf16" = bfloat16 stored as uint16_t; "f32" = IEEE float.  Every uint16_t operand below is bf16 in the tad_* entry points and
  *     IEEE half in their tad_*_f16 twins (same kernels compiled for the other operand format; see the end of this header).
  *   - row-major everywhere; leading dimension == number of columns unless stated.
+ *
+ * Pointer alignment (what the caller owes for every device pointer; checked on the host before anything is launched):
+ *   - The general rule: a device pointer must be 16-byte aligned.  The kernels move tensors as 16-byte pieces (float4 / uint4 loads and
+ *     stores, 16-byte global -> LDS transfers).  A pointer that breaks its requirement is refused with TAD_EINVAL and a message
+ *     "<entry point>: <argument> is misaligned: it must be N-byte aligned"; nothing is launched and no output is touched.  NULL for an
+ *     optional argument passes.  Fresh allocations (hipMalloc, torch) are 256-byte aligned; what breaks the rule is a view that starts
+ *     inside one, e.g. buf + 1.
+ *   - Exceptions are stated where they apply, as "Alignment:" lines at the entry points below:
+ *       "N bytes"  a narrower requirement (the widest access through that pointer is N bytes), enforced the same way;
+ *       "any"      every address that is a multiple of the element size works and gives the same bits as an aligned one (the pointer
+ *                  is read or written one element at a time, or the kernel has a narrower path for it).  The three gradient-norm
+ *                  reductions (tad_sumsq_f32, tad_grad_norm_coef, tad_grad_segnorm) peel the head of x up to a 16-byte boundary: their
+ *                  result is the same sum taken in another order.
+ *   - Host arrays (mean3 / std3, group_lr ..., every *_host table) and handles (tad_comm_t, RCCL ids and buffers, debug buffers) are
+ *     outside the rule.
+ *   - The _f16 twins owe what their bf16 entry points owe.  tests/alignment_contract.py holds the whole contract as a table.
  */
 #ifndef TAD_MI355X_H
 #define TAD_MI355X_H
@@ -62,6 +78,7 @@ const char* tad_last_error_string(void);
  * fp32 master weights stay owned by the caller (torch nn.Parameter); the kernels consume
  * bf16 copies: W [N,K] for forward, W^T [K,N] for the input-gradient GEMM. */
 int tad_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, tad_stream_t stream);
+/* Alignment: src, dst: any. */
 int tad_transpose_cast_f32_bf16(const float* src /*[R,C]*/, uint16_t* dst /*[C,R]*/, int R, int C,
                                 tad_stream_t stream);
 
@@ -75,6 +92,8 @@ int tad_transpose_cast_f32_bf16(const float* src /*[R,C]*/, uint16_t* dst /*[C,R
  * (ViT-L/14: K = 1176 -> 1216) tad_im2col_tubelets writes rows of that stride with zeros in the padding columns and the caller
  * passes a zero-padded weight [D, ldk] -- the product is the un-padded one exactly, and /14 is a pure configuration change. */
 int tad_patch_embed_ldk(int C, int tubelet, int patch);
+/* Alignment: patch sizes that are not multiples of 8 move pairs: x 8 bytes, cols 4 bytes (tad_im2col_tubelets_f32: cols 8 bytes); so does x of
+ * tad_patch_embed_fwd (its cols stay at 16 bytes: the GEMM reads them). */
 int tad_im2col_tubelets(const float* x, uint16_t* cols, int B, int C, int T, int H, int W, int tubelet,
                         int patch, tad_stream_t stream);
 int tad_patch_embed_fwd(const float* x, const uint16_t* w_bf16, const float* bias, const float* pos,
@@ -101,6 +120,7 @@ int tad_patch_embed_fwd_implicit(const float* x, const uint16_t* w_bf16, const f
  * bgr != 0: channel c is stored at position 2-c (cv2 frames, replaces cv2.cvtColor(BGR2RGB)); t_offset: frame t of the clip is
  * slot (t + t_offset) % T of the buffer (ring buffer for the sliding window of run_inference.py:86-93).  Any even patch size: rows have
  * the stride tad_patch_embed_ldk(3, tubelet, patch) (= K for multiples of 8; /14: 1216, padding columns zeroed). */
+/* Alignment: frames: 4 bytes. */
 int tad_im2col_tubelets_u8(const uint8_t* frames, uint16_t* cols, int B, int T, int H, int W, int tubelet, int patch,
                            const float* mean3, const float* std3, int bgr, int t_offset, tad_stream_t stream);
 /* Patch matrix of B windows read from ONE frame store [F,H,W,3] uint8: frame t of window b is slot idx[b*T+t].
@@ -111,6 +131,7 @@ int tad_im2col_tubelets_u8(const uint8_t* frames, uint16_t* cols, int B, int T, 
  * cols 16-byte aligned.  The index table is on the device, so this call cannot check it: the CALLER guarantees 0 <= idx < F.  As a
  * defence the kernels clamp every slot into [0, F-1]: an index outside the store reads the first / last frame instead of memory outside
  * the store -- a wrong result, never a wild address.  Do not rely on the clamp as padding. */
+/* Alignment: store: 4 bytes; idx: any. */
 int tad_im2col_frame_windows(const uint8_t* store, int64_t F, const int32_t* idx, void* cols, int cols_dtype,
                              int B, int T, int H, int W, int tubelet, int patch,
                              const float* mean3, const float* std3, int bgr, tad_stream_t stream);
@@ -124,6 +145,7 @@ int tad_patch_embed_bwd(const uint16_t* dy_bf16, const uint16_t* cols, float* dW
 
 /* ---- nn.LayerNorm(D, eps) (modeling_finetune.py:143,149,270; eps=1e-6 at :342) -------
  * x [rows,D] f32; y [rows,D] in y_dtype; mean/rstd [rows] f32 saved for backward (nullable). */
+/* Alignment: a 16-bit y: 8 bytes; mean, rstd: any. */
 int tad_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* y, int y_dtype,
                       float* mean, float* rstd, int64_t rows, int D, float eps, tad_stream_t stream);
 /* dx = (dres ? dres : 0) + LN'(dy).  Optional outputs: dx_bf16 (copy of dx), colsum_dx [D]
@@ -133,6 +155,7 @@ int tad_layernorm_fwd(const float* x, const float* gamma, const float* beta, voi
  * accumulate != 0: dgamma, dbeta and colsum_dx are added to (gradient accumulation in place), else overwritten.
  * ws: tad_layernorm_bwd_workspace_bytes(rows, D). */
 size_t tad_layernorm_bwd_workspace_bytes(int64_t rows, int D);
+/* Alignment: a 16-bit dy and dx_bf16: 8 bytes; mean, rstd, rowscale: any. */
 int tad_layernorm_bwd(const void* dy, int dy_dtype, const float* x, const float* gamma, const float* mean,
                       const float* rstd, const float* dres, float* dx, uint16_t* dx_bf16, float* dgamma,
                       float* dbeta, float* colsum_dx, const float* rowscale, int rows_per_scale, int accumulate,
@@ -155,6 +178,7 @@ int tad_layernorm_bwd(const void* dy, int dy_dtype, const float* x, const float*
  * summation order over K.  tad_linear_workspace_bytes returns 0 for shapes whose plan never splits along K under the current
  * tad_linear_tuning knobs (every Linear of ViT-B by default; ViT-L's fc2 / dX(fc1) tails: 16 tiles x 8 shares = 33.5 MB). */
 size_t tad_linear_workspace_bytes(int64_t M, int N, int K);
+/* Alignment: gamma, rowscale: any (read one float at a time; bias is read as float4). */
 int tad_linear_fwd(const uint16_t* x, const uint16_t* w, const float* bias, void* y, int y_dtype,
                    int epilogue, uint16_t* preact, const float* residual, const float* gamma,
                    const float* rowscale, int rows_per_scale, void* ws, size_t ws_bytes, int64_t M, int N, int K,
@@ -284,6 +308,7 @@ int tad_linear_bwd_weight(const uint16_t* dy, const uint16_t* x, float* dW, floa
  * what the computation would have stored there in the backward's case, and values that only ever meet a zero factor in the forward's.  The
  * scale is read on the device (no host copy, no synchronisation).  head_dim 64 with pre-scaled q, 16-bit output and no attention dropout
  * takes the path; every other contract, and every call without a clip_scale, computes all clips (which kernel a call takes: tad_attn_plan). */
+/* Alignment: lse, clip_scale: any. */
 int tad_attn_fwd(const uint16_t* qkv, void* out, int out_dtype, uint16_t* out_lo, float* lse, const float* clip_scale, int B, int N, int H,
                  int d, float scale, int q_prescaled, float dropout_p, uint32_t seed, tad_stream_t stream);
 /* dqkv [B,N,3,H,d] bf16 (fully overwritten).  delta: scratch of tad_attn_bwd_scratch_bytes(B, N, H) bytes = 2*B*H*N floats (the
@@ -325,6 +350,7 @@ int tad_attn_debug_stamps(void* buf);
 /* out_lo (nullable): the forward's rounding residual; with it delta = rowsum(dout * (out + out_lo)), i.e. of the unrounded output, which
  * is what cancels against the dP the kernels recompute (without it the q / k gradients of near-uniform attention rows carry the
  * rounding of out amplified by |delta| / |dP - delta|). */
+/* Alignment: lse, clip_scale, delta: any. */
 int tad_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* out_lo, const uint16_t* dout, const float* lse,
                  const float* clip_scale, uint16_t* dqkv, float* delta, int B, int N, int H, int d, float scale, int q_prescaled,
                  float dropout_p, uint32_t seed, tad_stream_t stream);
@@ -337,14 +363,17 @@ int tad_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* out_l
  * overwritten.  P and the sums stay f32 (no 16-bit rounding of P); fixed summation order, no atomics: bit-reproducible.  A clip is computed
  * from its own rows of qkv, lse and w alone: nothing behind them is read, and a non-finite value in another clip cannot reach it.
  * TAD_EINVAL: null pointer, d not 64 / 80, unknown op_dtype, B, N or H < 1, scale <= 0, qkv of 4 GiB or more. */
+/* Alignment: lse, w, out: any. */
 int tad_attn_colsum(const uint16_t* qkv, int op_dtype, const float* lse, const float* w, float* out, int B, int N, int H, int d,
                     float scale, int q_prescaled, tad_stream_t stream);
 
 /* ---- token mean-pool x.mean(1) (modeling_finetune.py:325-326) -------------------------
  * x [B,N,D] f32 -> y [B,D] f32.  ws: B*TAD_POOL_SPLIT*D floats. */
 #define TAD_POOL_SPLIT 8
+/* Alignment: y: any. */
 int tad_meanpool_fwd(const float* x, float* y, float* ws, int B, int N, int D, tad_stream_t stream);
 /* dx[b,n,:] = dy[b,:]/N  (f32, plus optional bf16 copy) */
+/* Alignment: dx_bf16: 8 bytes. */
 int tad_meanpool_bwd(const float* dy, float* dx, uint16_t* dx_bf16, int B, int N, int D,
                      tad_stream_t stream);
 
@@ -362,6 +391,7 @@ int tad_colsum_segments(const uint16_t* a, int op_dtype, float* S, void* ws, siz
  * bias [D] (nullable), rowscale [B] (nullable), xbar and out [B,D] f32 (out must not alias xbar).  The B*D dot products run on the
  * f32 sums (the pooled operand is not rounded to 16 bits) with f64 accumulation and one rounding to f32 at the end.
  * K % 8 == 0 and S, w 16-byte aligned, else TAD_EINVAL. */
+/* Alignment: bias, rowscale, xbar, out: any. */
 int tad_pooled_linear(const float* S, const uint16_t* w, int op_dtype, const float* bias, const float* rowscale, const float* xbar,
                       float* out, int B, int N, int D, int K, tad_stream_t stream);
 /* dh[b*N+n,:] = op16(t[b,:] * gelu'(h[b*N+n,:])): t [B,K] f32, h and dh [B*N,K] 16-bit.  The arithmetic and the rounding are those
@@ -380,6 +410,7 @@ int tad_colsum_window_f32(const float* a, float* out, int accumulate, void* ws, 
 int tad_colsum_bf16(const uint16_t* a, float* out, int accumulate, void* ws, size_t ws_bytes, int64_t M,
                     int N, tad_stream_t stream);
 /* y_bf16 = bf16(rowscale[m/rows_per_scale] * gamma[n] * x_f32)  (backward of the residual-branch scale) */
+/* Alignment: y: 8 bytes; rowscale: any. */
 int tad_scale_cast_bf16(const float* x, uint16_t* y, const float* gamma, const float* rowscale,
                         int rows_per_scale, int64_t M, int N, tad_stream_t stream);
 
@@ -392,12 +423,14 @@ int tad_scale_cast_bf16(const float* x, uint16_t* y, const float* gamma, const f
  * tad_rowscale_transpose_cast: w [N,K] f32, gamma [N] f32 -> out [K,N] 16-bit, out[k,n] = op16(fl32(gamma[n] w[n,k])) (the product rounded
  * to f32, then to the operand format, nearest even): the scaled twin of tad_transpose_cast_f32_bf16, the wT operand of tad_linear_bwd_input.
  * Any N, K > 0. */
+/* Alignment: w, gamma, out: any. */
 int tad_rowscale_transpose_cast(const float* w, const float* gamma, uint16_t* out, int N, int K, tad_stream_t stream);
 /* tad_layerscale_grads: T, W [N,K] f32; bias (nullable), cs (nullable unless bias or dbias is given), gamma [N] f32.
  *   dW[n,k] (+)= fl32(gamma[n] T[n,k]);  dbias[n] (+)= fl32(gamma[n] cs[n]) (dbias nullable);  dgamma[n] (+)= sum_k T[n,k] W[n,k] + bias[n] cs[n].
  * accumulate = 0 writes, 1 adds to what dW / dbias / dgamma hold (gradient sinks).  One workgroup per row; the k reduction runs in a fixed
  * order without atomics: the same inputs give the same bits.  Any N, K > 0; 16-byte accesses when K % 4 == 0 and T, W, dW are 16-byte
  * aligned.  dW must not alias T or W. */
+/* Alignment: every pointer: any (the element-wise path keeps the vector path's order of additions: dgamma has the same bits). */
 int tad_layerscale_grads(const float* T, const float* W, const float* bias, const float* cs, const float* gamma, float* dW, float* dbias,
                          float* dgamma, int accumulate, int N, int K, tad_stream_t stream);
 /* The dropout mask of a branch output [M,D]: element (m, c) is kept iff hash32(m, c, seed) >= p * 2^32 (csrc/common.h: Drop / drop_keep
@@ -410,6 +443,7 @@ int tad_layerscale_grads(const float* T, const float* W, const float* bias, cons
  * tad_branch_dropout_cast: y[m,c] = op16(fl32(g[m,c] * fl32(rowscale * inv_keep))) for the same elements, +0 for every other one: the masked
  *   twin of tad_scale_cast_bf16 (no gamma: it is folded into the weights, see above).
  * Streaming, grid-stride; 16-byte accesses when D % 4 == 0 and the f32 tensors are 16-byte aligned (y: 8), element-wise otherwise. */
+/* Alignment: every pointer of tad_branch_dropout_fwd and tad_branch_dropout_cast: any. */
 int tad_branch_dropout_fwd(const float* u, const float* res, float* out, const float* gamma, const float* rowscale, int rows_per_scale,
                            float p, uint32_t seed, int64_t M, int D, tad_stream_t stream);
 int tad_branch_dropout_cast(const float* g, uint16_t* y, const float* rowscale, int rows_per_scale, float p, uint32_t seed, int64_t M, int D,
@@ -418,6 +452,7 @@ int tad_branch_dropout_cast(const float* g, uint16_t* y, const float* rowscale, 
 /* sum of squares of an f32 vector, accumulated into *out (f32, device) -- get_grad_norm_ (utils.py:415-427).  Deterministic: block
  * partials in ws (tad_sumsq_workspace_bytes()), added in a fixed order; no atomics. */
 size_t tad_sumsq_workspace_bytes(void);
+/* Alignment: x, out: any (see the general rule for the order of the sum); ws: 4 bytes. */
 int tad_sumsq_f32(const float* x, int64_t n, float* out, void* ws, size_t ws_bytes, tad_stream_t stream);
 /* NativeScalerWithGradNormCount's unscale + clip + overflow decision (utils.py:386-412: GradScaler.unscale_, clip_grad_norm_, the
  * "found inf" skip) as two launches on the flat gradient buffer, nothing read back by the host:
@@ -426,6 +461,7 @@ int tad_sumsq_f32(const float* x, int64_t n, float* out, void* ws, size_t ws_byt
  *             0 when the norm is inf / NaN: the optimizer kernel then skips the step
  *   out3[2] = 1 when the norm is inf / NaN, else 0                  (read by the host one step late)
  * ws: tad_sumsq_workspace_bytes().  Deterministic (fixed order, no atomics). */
+/* Alignment: x, out3: any; ws: 4 bytes. */
 int tad_grad_norm_coef(const float* x, int64_t n, float inv_scale, float max_norm, float* out3, void* ws, size_t ws_bytes,
                        tad_stream_t stream);
 
@@ -453,6 +489,7 @@ typedef struct { int64_t offset, length; } tad_segnorm_work;
 size_t tad_grad_segnorm_workspace_bytes(int nwork);
 int tad_grad_segnorm_plan_check(const tad_segnorm_seg* table_host, int nseg, const tad_segnorm_work* work_host, int nwork, int64_t n,
                                 int nslots);
+/* Alignment: table, work: 8 bytes; ws: 4 bytes; grad, coef, acc, last, counters: any. */
 int tad_grad_segnorm(const float* grad, int64_t n, const tad_segnorm_seg* table, int nseg, const tad_segnorm_work* work, int nwork,
                      const float* coef, double* acc, float* last, int32_t* counters, int nslots, void* ws, size_t ws_bytes,
                      tad_stream_t stream);
@@ -480,6 +517,7 @@ int tad_transpose_bf16_batched(const uint16_t* src, uint16_t* dst, const int32_t
  * sumsq_partials (or NULL): [ceil(n / CHUNK)] per-chunk sums of the UNSCALED g^2 (deterministic order). */
 #define TAD_ADAMW_CHUNK 4096
 #define TAD_ADAMW_MAX_GROUPS 128
+/* Alignment: param_bf16: 8 bytes; chunk_group, grad_scale, sumsq_partials: any. */
 int tad_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, uint16_t* param_bf16,
                    const uint8_t* chunk_group, int64_t n, const float* group_lr, const float* group_wd, int n_groups,
                    const int32_t* group_step, float beta1, float beta2, float eps, const float* grad_scale,
@@ -493,6 +531,7 @@ int tad_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_a
  * chunks (device, int32 [n_chunks][2]): {tensor index, chunk index within the tensor}, one workgroup per TAD_EMA_CHUNK elements;
  *   every chunk of every tensor listed once.  The tables are host-built and reused while the addresses stay the same. */
 #define TAD_EMA_CHUNK 8192
+/* Alignment: tensors: any (8-byte rows); chunks: 8 bytes; the addresses inside the table: see above. */
 int tad_ema_update(const int64_t* tensors, int n_tensors, const int32_t* chunks, int n_chunks, float decay, float one_minus_decay,
                    tad_stream_t stream);
 
@@ -513,6 +552,7 @@ int tad_ema_update(const int64_t* tensors, int n_tensors, const int32_t* chunks,
 #define TAD_MIX_BLEND 1
 #define TAD_MIX_PASTE 2
 int tad_mixup_plan_check(const int32_t* plan_host, int B, int T, int H, int W);
+/* Alignment: every pointer of tad_mixup_clips, tad_mixup_target, tad_soft_target_ce and tad_frame_loss: any. */
 int tad_mixup_clips(float* x, const int32_t* plan, int B, int C, int T, int H, int W, tad_stream_t stream);
 int tad_mixup_target(const int32_t* plan, const int64_t* labels, float* out, int B, int num_classes, float on_value, float off_value,
                      tad_stream_t stream);
@@ -575,6 +615,7 @@ int tad_frame_loss(int kind, const float* logits, const int64_t* labels, const f
 #define TAD_ERASE_PIXEL 2
 #define TAD_ERASE_MAX_BOXES 65535
 int tad_erase_plan_check(const int32_t* boxes_host, int n_boxes, int B, int T, int H, int W);
+/* Alignment: x, boxes: any. */
 int tad_erase_clips(float* x, const int32_t* boxes, int n_boxes, uint32_t seed, int B, int C, int T, int H, int W, tad_stream_t stream);
 
 /* RandAugment of the fine-tune recipe on the device (rand_augment.py of the reference: --aa rand-m6-n3-mstd0.5-inc1, applied by the
@@ -615,6 +656,7 @@ int tad_erase_clips(float* x, const int32_t* boxes, int n_boxes, uint32_t seed, 
 #define TAD_RA_AFFINE 11
 int tad_randaug_plan_check(const int32_t* table_host, int64_t n_words, int n_layers, int B, int T);
 size_t tad_randaug_workspace_bytes(int n_layers, int B, int T, int H, int W);
+/* Alignment: x, out, table: any; workspace: 256 bytes.  tad_frames_to_clip: x, out: any. */
 int tad_randaug_apply(const uint8_t* x, uint8_t* out, const int32_t* table, int n_layers, uint32_t stats_layers, void* workspace,
                       size_t workspace_bytes, int B, int T, int H, int W, tad_stream_t stream);
 int tad_frames_to_clip(const uint8_t* x, float* out, const float* mean, const float* std_, int B, int T, int H, int W, tad_stream_t stream);
@@ -648,6 +690,7 @@ int tad_frames_to_clip(const uint8_t* x, float* out, const float* mean, const fl
 size_t tad_multiscale_crop_workspace_bytes(int B, int n_hsets, int n_vsets, int S_h, int S_w);
 int tad_multiscale_crop_plan_check(const int32_t* table_host, int64_t n_words, int B, int n_hsets, int n_vsets, int Hs, int Ws, int S_h,
                                    int S_w);
+/* Alignment: x, out: any; workspace: 4 bytes. */
 int tad_multiscale_crop(const uint8_t* x, void* out, int out_f32, const float* mean, const float* std_, const void* workspace,
                         size_t workspace_bytes, int B, int T, int Hs, int Ws, int S_h, int S_w, int n_hsets, int n_vsets, tad_stream_t stream);
 
@@ -708,6 +751,7 @@ int tad_multiscale_crop(const uint8_t* x, void* out, int out_f32, const float* m
 #define TAD_FR_REPLICATE 3
 size_t tad_frame_resize_workspace_bytes(int B, int n_vsets, int S_h, int S_w);
 int tad_frame_resize_plan_check(const int32_t* table_host, int64_t n_words, int B, int n_vsets, int H, int W, int S_h, int S_w);
+/* Alignment: x, out: any; workspace: 4 bytes. */
 int tad_frame_resize(const uint8_t* x, void* out, int out_f32, const float* mean, const float* std_, const void* workspace,
                      size_t workspace_bytes, int B, int T, int H, int W, int S_h, int S_w, int n_vsets, tad_stream_t stream);
 
@@ -749,12 +793,14 @@ int tad_frame_resize(const uint8_t* x, void* out, int out_f32, const float* mean
 #define TAD_SS_ROW_WORDS 12
 size_t tad_spatial_sample_workspace_bytes(int B, int T);
 int tad_spatial_sample_plan_check(const int32_t* table_host, int64_t n_words, int B, int T, int H, int W, int S);
+/* Alignment: x, out: any; workspace: 4 bytes. */
 int tad_spatial_sample(const void* x, int x_u8, float* out, const float* mean, const float* std_, const void* workspace,
                        size_t workspace_bytes, int B, int T, int H, int W, int S, tad_stream_t stream);
 
 /* ---- MAE pre-training path: what modeling_pretrain.py / engine_for_pretraining.py add around the Block stack ----
  * Rows are D f32, D % 4 == 0.  idx arrays are int32 on the device. */
 /* out[r] = src[idx[r]], r < n_out: x[~mask].reshape(B,-1,C) (modeling_pretrain.py:98) with idx = b*N + visible token */
+/* Alignment: idx (here and in tad_scatter_rows_f32), vis_idx, mask_idx: any. */
 int tad_gather_rows_f32(const float* src, const int32_t* idx, float* out, int64_t n_out, int D, tad_stream_t stream);
 /* out[idx[r]] = src[r], r < n_in (unique indices; the caller zero-fills out): backward of the gather */
 int tad_scatter_rows_f32(const float* src, const int32_t* idx, float* out, int64_t n_in, int D, tad_stream_t stream);
@@ -766,11 +812,13 @@ int tad_mae_assemble(const float* x_vis, const float* mask_token, const float* p
  * tub*p*p*3] for the masked tokens: v = x*std + mean, patch layout 'b n (p0 p1 p2) c', and with normalize_target each
  * (patch, channel) is standardised over its pixels: (v - mean) / (sqrt(unbiased var) + 1e-6).  The mean is refined by the mean of
  * the residuals, so a constant (patch, channel) gives exactly 0 (the fp64 value), not f32 rounding noise.  mean3 / std3: HOST arrays. */
+/* Alignment: videos, mask_idx, labels: any. */
 int tad_mae_target(const float* videos, const int32_t* mask_idx, float* labels, int B, int n_mask, int T, int H, int W, int tubelet,
                    int patch, const float* mean3, const float* std3, int normalize_target, tad_stream_t stream);
 /* nn.MSELoss() (engine_for_pretraining.py:27,70): partials[tad_mse_loss_blocks(n)] = block sums of (pred-target)^2 (the loss is
  * their sum / n); grad (nullable) = 2 (pred - target) / n */
 int tad_mse_loss_blocks(int64_t n);
+/* Alignment: partials: any. */
 int tad_mse_loss(const float* pred, const float* target, int64_t n, float* partials, float* grad, tad_stream_t stream);
 
 /* ---- evaluation path -----------------------------------------------------------------------------------------
@@ -779,6 +827,7 @@ int tad_mse_loss(const float* pred, const float* target, int64_t n, float* parti
  * thresholds: ascending f32 [n_thresholds <= 255] (device); labels int32 (non-zero = positive);
  * hist int64 [2][n_thresholds+1] (device, overwritten): hist[l][k] = number of samples with label l and k = #{t : p >= t}.
  * The confusion matrix at threshold index i is then  TP = sum_{k>i} hist[1][k], FN = sum_{k<=i} hist[1][k], FP / TN likewise. */
+/* Alignment: every pointer of tad_threshold_histogram, tad_group_threshold_histogram and tad_group_rank_stats: any. */
 int tad_threshold_histogram(const float* probs, const int32_t* labels, const float* thresholds, int n_thresholds, int64_t n,
                             int64_t* hist, tad_stream_t stream);
 
@@ -807,6 +856,7 @@ int tad_group_rank_stats(const int32_t* labels_sorted, const uint64_t* member_so
  * x = hi + lo (bf16 each).  concat mode: out [M,3K] = [hi|hi|lo] (role_b=0) or [hi|lo|hi] (role_b=1); stack mode: out [3M,K]
  * with the three parts stacked along rows.  Feeding tad_linear_* with both operands split this way (K or M tripled) gives the
  * f32 product to ~2^-17 using the same MFMA kernels. */
+/* Alignment: out: 8 bytes. */
 int tad_split_bf16x3(const float* x, uint16_t* out, int64_t M, int K, int role_b, int stack, tad_stream_t stream);
 int tad_im2col_tubelets_f32(const float* x, float* cols, int B, int C, int T, int H, int W, int tubelet, int patch,
                             tad_stream_t stream);
@@ -814,15 +864,19 @@ int tad_im2col_tubelets_f32(const float* x, float* cols, int B, int C, int T, in
  * (nullable).  dropout_p in [0, 1): nn.Dropout on the softmax matrix (modeling_finetune.py:99-101; flash_attention_class.py:59-61) --
  * element (b, h, query, key) is kept iff lowbias32(row * 0x9E3779B1 + key * 0x85EBCA77 + seed) >= dropout_p * 2^32 with
  * row = (b H + h) N + query, kept probabilities scaled by 1 / (1 - dropout_p); the backward regenerates the same bits from (p, seed). */
+/* Alignment: lse: any. */
 int tad_attn_fwd_f32(const float* qkv, float* out, float* lse, int B, int N, int H, int d, float scale, float dropout_p, uint32_t seed,
                      tad_stream_t stream);
 
 /* precise-mode backward pieces: f32 attention backward (dqkv [B,N,3,H,64] f32 fully overwritten; delta [B,H,N] scratch),
  * erf-GELU forward / backward on f32, column sums of an f32 matrix (bias gradients). */
+/* Alignment: lse, delta: any. */
 int tad_attn_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, float* delta,
                      int B, int N, int H, int d, float scale, float dropout_p, uint32_t seed, tad_stream_t stream);
+/* Alignment: every pointer of tad_gelu_f32 and tad_gelu_bwd_f32: any. */
 int tad_gelu_f32(const float* h, float* a, int64_t n, tad_stream_t stream);
 int tad_gelu_bwd_f32(const float* dy, const float* h, float* dh, int64_t n, tad_stream_t stream);
+/* Alignment: a: any when N % 4 != 0 (16 bytes otherwise); out: any. */
 int tad_colsum_f32(const float* a, float* out, int64_t M, int N, tad_stream_t stream);
 
 /* ---- device info ------------------------------------------------------------------------ */

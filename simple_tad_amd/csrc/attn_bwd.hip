@@ -670,6 +670,12 @@ extern "C" int tad_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint
                             const float* clip_scale, uint16_t* dqkv, float* delta, int B, int N, int H, int d, float scale, int q_prescaled,
                             float dropout_p, uint32_t seed, tad_stream_t stream) {
   TAD_REQUIRE(qkv && out && dout && lse && dqkv && delta, "attn_bwd: null pointer");
+  // the 16-bit tensors move in 16-byte pieces (LDS-DMA, fragment loads, whole-row stores); lse, clip_scale and delta in 4-byte pieces
+  TAD_REQUIRE_ALIGNED("attn_bwd", qkv, 16);
+  TAD_REQUIRE_ALIGNED("attn_bwd", out, 16);
+  TAD_REQUIRE_ALIGNED("attn_bwd", out_lo, 16);
+  TAD_REQUIRE_ALIGNED("attn_bwd", dout, 16);
+  TAD_REQUIRE_ALIGNED("attn_bwd", dqkv, 16);
   AttnLaunch l[2];
   if (const int rc = attn_plan_bwd(AttnCall{B, N, H, d, TAD_OP16, TAD_OP16, q_prescaled, scale, dropout_p, clip_scale != nullptr, out_lo != nullptr}, l)) return rc;
   Drop drop;

@@ -184,6 +184,7 @@ using namespace tad;
 extern "C" int tad_attn_colsum(const uint16_t* qkv, int op_dtype, const float* lse, const float* w, float* out, int B, int N, int H, int d,
                                float scale, int q_prescaled, tad_stream_t stream) {
   TAD_REQUIRE(qkv && lse && w && out, "attn_colsum: null pointer");
+  TAD_REQUIRE_ALIGNED("attn_colsum", qkv, 16);  // (16-byte LDS-DMA pieces and fragment loads; lse, w and out move as single floats)
   TAD_REQUIRE(d == 64 || d == 80, "attn_colsum: head_dim must be 64 or 80 (got %d)", d);
   TAD_REQUIRE(op_dtype == TAD_BF16 || op_dtype == TAD_F16, "attn_colsum: op_dtype must be TAD_BF16 or TAD_F16");
   TAD_REQUIRE(B > 0 && N > 0 && H > 0 && H <= 65535 && B <= 65535, "attn_colsum: bad shape B=%d N=%d H=%d", B, N, H);

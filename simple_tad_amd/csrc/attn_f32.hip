@@ -301,6 +301,8 @@ extern "C" {
 int tad_attn_fwd_f32(const float* qkv, float* out, float* lse, int B, int N, int H, int d, float scale, float dropout_p, uint32_t seed,
                      tad_stream_t stream) {
   TAD_REQUIRE(qkv && out, "attn_fwd_f32: null pointer");
+  TAD_REQUIRE_ALIGNED("attn_fwd_f32", qkv, 16);
+  TAD_REQUIRE_ALIGNED("attn_fwd_f32", out, 16);  // (float4 rows; lse is written float by float)
   TAD_REQUIRE(d == 64 || d == 80, "attn_fwd_f32: head_dim must be 64 or 80 (got %d)", d);
   TAD_REQUIRE(B > 0 && N > 0 && H > 0 && H <= 65535 && B <= 65535 && (int64_t)B * H * N < (1ll << 32), "attn_fwd_f32: bad shape");
   TAD_REQUIRE(scale > 0.f, "attn_fwd_f32: scale must be positive");
@@ -317,6 +319,10 @@ int tad_attn_fwd_f32(const float* qkv, float* out, float* lse, int B, int N, int
 int tad_attn_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, float* delta, int B, int N, int H,
                      int d, float scale, float dropout_p, uint32_t seed, tad_stream_t stream) {
   TAD_REQUIRE(qkv && out && dout && lse && dqkv && delta, "attn_bwd_f32: null pointer");
+  TAD_REQUIRE_ALIGNED("attn_bwd_f32", qkv, 16);
+  TAD_REQUIRE_ALIGNED("attn_bwd_f32", out, 16);
+  TAD_REQUIRE_ALIGNED("attn_bwd_f32", dout, 16);
+  TAD_REQUIRE_ALIGNED("attn_bwd_f32", dqkv, 16);  // (float4 rows; lse and delta move float by float)
   TAD_REQUIRE(d == 64 || d == 80, "attn_bwd_f32: head_dim must be 64 or 80 (got %d)", d);
   TAD_REQUIRE(B > 0 && N > 0 && H > 0 && H <= 65535 && B <= 65535 && (int64_t)B * H * N < (1ll << 32), "attn_bwd_f32: bad shape");
   TAD_REQUIRE(scale > 0.f, "attn_bwd_f32: scale must be positive");

@@ -599,6 +599,10 @@ static FwdKernel fwd_kernel(const AttnLaunch& l, std::index_sequence<I...>) {
 extern "C" int tad_attn_fwd(const uint16_t* qkv, void* out, int out_dtype, uint16_t* out_lo, float* lse, const float* clip_scale, int B, int N, int H,
                             int d, float scale, int q_prescaled, float dropout_p, uint32_t seed, tad_stream_t stream) {
   TAD_REQUIRE(qkv && out, "attn_fwd: null pointer");
+  // qkv: 16-byte LDS-DMA pieces and fragment loads; out / out_lo: whole rows in 16-byte pieces; lse and clip_scale: one float at a time
+  TAD_REQUIRE_ALIGNED("attn_fwd", qkv, 16);
+  TAD_REQUIRE_ALIGNED("attn_fwd", out, 16);
+  TAD_REQUIRE_ALIGNED("attn_fwd", out_lo, 16);
   AttnLaunch l;
   if (const int rc = attn_plan_fwd(AttnCall{B, N, H, d, out_dtype, TAD_OP16, q_prescaled, scale, dropout_p, clip_scale != nullptr, out_lo != nullptr}, &l)) return rc;
   Drop drop;

@@ -94,6 +94,20 @@ constexpr int WAVE = 64;
     }                                         \
   } while (0)
 
+// The pointer alignment contract (include/tad_mi355x.h, "Pointer alignment"): `ptr` must lie on a multiple of `bytes` (a power of two: the
+// widest access the entry point's kernels make through it), else TAD_EINVAL with a message that names the argument.  nullptr passes: an
+// optional argument is checked for presence where it is required, not here.  `who` is the entry point's name in its other messages.
+#define TAD_REQUIRE_ALIGNED_AS(who, ptr, bytes, name)                                                                     \
+  do {                                                                                                                    \
+    if ((reinterpret_cast<uintptr_t>(ptr) & (uintptr_t)((bytes) - 1)) != 0) {                                             \
+      tad::set_error("%s: %s is misaligned: it must be %d-byte aligned (the address ends in 0x%02x)", who, name, (int)(bytes), \
+                     (unsigned)(reinterpret_cast<uintptr_t>(ptr) & 0xffu));                                               \
+      return TAD_EINVAL;                                                                                                  \
+    }                                                                                                                     \
+  } while (0)
+// (the argument's name is the expression itself)
+#define TAD_REQUIRE_ALIGNED(who, ptr, bytes) TAD_REQUIRE_ALIGNED_AS(who, ptr, bytes, #ptr)
+
 // 16-bit operand <-> f32.  bf16: the upper half of the f32 pattern; f16: v_cvt_f32_f16.  Round-to-nearest-even on the way down.
 __device__ __forceinline__ float op16_to_f32(uint16_t v) {
 #ifdef TAD_OPND_F16

@@ -513,7 +513,8 @@ extern "C" {
 int tad_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, tad_stream_t stream) {
   TAD_REQUIRE(src && dst && n >= 0, "cast: null pointer");
   if (n == 0) return TAD_OK;
-  TAD_REQUIRE((((uintptr_t)src) & 15) == 0 && (((uintptr_t)dst) & 15) == 0, "cast: pointers must be 16-byte aligned");
+  TAD_REQUIRE_ALIGNED("cast", src, 16);
+  TAD_REQUIRE_ALIGNED("cast", dst, 16);
   hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(capped_grid((n + 7) / 8, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, n);
   return check_launch("cast_f32_bf16");
 }
@@ -527,7 +528,9 @@ int tad_transpose_cast_f32_bf16(const float* src, uint16_t* dst, int R, int C, t
 #ifndef TAD_OPND_F16  // format-independent: one copy for the library (bf16 pass)
 int tad_transpose_bf16_batched(const uint16_t* src, uint16_t* dst, const int32_t* table, int n_tiles, tad_stream_t stream) {
   TAD_REQUIRE(src && dst && table && n_tiles > 0, "transpose_bf16_batched: bad args");
-  TAD_REQUIRE((((uintptr_t)src | (uintptr_t)dst | (uintptr_t)table) & 15) == 0, "transpose_bf16_batched: buffers must be 16-byte aligned");
+  TAD_REQUIRE_ALIGNED("transpose_bf16_batched", src, 16);
+  TAD_REQUIRE_ALIGNED("transpose_bf16_batched", dst, 16);
+  TAD_REQUIRE_ALIGNED("transpose_bf16_batched", table, 16);
   hipLaunchKernelGGL(transpose_bf16_batched_kernel, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, src, dst,
                      reinterpret_cast<const int4*>(table));
   return check_launch("transpose_bf16_batched");
@@ -542,6 +545,8 @@ int tad_patch_embed_ldk(int C, int tubelet, int patch) {
 #ifndef TAD_OPND_F16  // format-independent: one copy for the library (bf16 pass)
 int tad_meanpool_fwd(const float* x, float* y, float* ws, int B, int N, int D, tad_stream_t stream) {
   TAD_REQUIRE(x && y && ws && B > 0 && N > 0 && D > 0 && D % 4 == 0, "meanpool_fwd: bad args (D must be a multiple of 4)");
+  TAD_REQUIRE_ALIGNED("meanpool_fwd", x, 16);
+  TAD_REQUIRE_ALIGNED("meanpool_fwd", ws, 16);  // (float4 rows and partials; y is written float by float)
   hipLaunchKernelGGL(meanpool_partial_kernel, dim3((D / 4 + 63) / 64, TAD_POOL_SPLIT, B), dim3(256), 0, (hipStream_t)stream, x, ws, N, D);
   hipLaunchKernelGGL(meanpool_final_kernel, dim3((B * D + 255) / 256), dim3(256), 0, (hipStream_t)stream, ws, y, B, N, D);
   return check_launch("meanpool_fwd");
@@ -550,6 +555,9 @@ int tad_meanpool_fwd(const float* x, float* y, float* ws, int B, int N, int D, t
 
 int tad_meanpool_bwd(const float* dy, float* dx, uint16_t* dx_bf16, int B, int N, int D, tad_stream_t stream) {
   TAD_REQUIRE(dy && (dx || dx_bf16) && B > 0 && N > 0 && D % 4 == 0, "meanpool_bwd: bad args");
+  TAD_REQUIRE_ALIGNED("meanpool_bwd", dy, 16);
+  TAD_REQUIRE_ALIGNED("meanpool_bwd", dx, 16);
+  TAD_REQUIRE_ALIGNED("meanpool_bwd", dx_bf16, 8);  // (float4 loads and stores, 8-byte packed 16-bit stores)
   hipLaunchKernelGGL(meanpool_bwd_kernel, dim3(capped_grid((int64_t)B * N * D / 4, 256)), dim3(256), 0, (hipStream_t)stream, dy, dx,
                      dx_bf16, B, N, D);
   return check_launch("meanpool_bwd");
@@ -568,6 +576,9 @@ size_t tad_colsum_workspace_bytes(int64_t M, int N) { return (size_t)colsum_spli
 int tad_colsum_bf16(const uint16_t* a, float* out, int accumulate, void* ws, size_t ws_bytes, int64_t M, int N,
                     tad_stream_t stream) {
   TAD_REQUIRE(a && out && ws && M > 0 && N > 0 && N % 8 == 0, "colsum: bad args (N must be a multiple of 8)");
+  TAD_REQUIRE_ALIGNED("colsum", a, 16);
+  TAD_REQUIRE_ALIGNED("colsum", out, 16);
+  TAD_REQUIRE_ALIGNED("colsum", ws, 16);  // (16-byte row chunks; the reduction reads ws and writes out as float4)
   const int splits = colsum_splits(M);
   if (ws_bytes < (size_t)splits * N * sizeof(float)) { set_error("colsum: workspace too small"); return TAD_ENOSPACE; }
   const int rows_per = (int)((M + splits - 1) / splits);
@@ -580,6 +591,9 @@ int tad_colsum_window_f32(const float* a, float* out, int accumulate, void* ws, 
                           tad_stream_t stream) {
   TAD_REQUIRE(a && out && ws && B > 0 && R > 0 && N > 0 && N % 4 == 0, "colsum_window: bad args (N must be a multiple of 4)");
   TAD_REQUIRE(r0 >= 0 && rc > 0 && r0 + rc <= R, "colsum_window: rows [%d, %d) outside [0, %d)", r0, r0 + rc, R);
+  TAD_REQUIRE_ALIGNED("colsum_window", a, 16);
+  TAD_REQUIRE_ALIGNED("colsum_window", out, 16);
+  TAD_REQUIRE_ALIGNED("colsum_window", ws, 16);
   const int64_t total = (int64_t)B * rc;
   const int splits = colsum_splits(total);
   if (ws_bytes < (size_t)splits * N * sizeof(float)) { set_error("colsum_window: workspace too small"); return TAD_ENOSPACE; }
@@ -596,6 +610,9 @@ int tad_scale_cast_bf16(const float* x, uint16_t* y, const float* gamma, const f
                         int N, tad_stream_t stream) {
   TAD_REQUIRE(x && y && M > 0 && N > 0 && N % 4 == 0, "scale_cast: bad args");
   TAD_REQUIRE(!rowscale || rows_per_scale > 0, "scale_cast: rows_per_scale must be > 0");
+  TAD_REQUIRE_ALIGNED("scale_cast", x, 16);
+  TAD_REQUIRE_ALIGNED("scale_cast", y, 8);
+  TAD_REQUIRE_ALIGNED("scale_cast", gamma, 16);  // (float4 loads of x and gamma, 8-byte packed stores; rowscale is read float by float)
   hipLaunchKernelGGL(scale_cast_kernel, dim3(capped_grid(M * N / 4, 256)), dim3(256), 0, (hipStream_t)stream, x, y, gamma, rowscale,
                      rows_per_scale, M, N);
   return check_launch("scale_cast");
@@ -607,6 +624,7 @@ size_t tad_sumsq_workspace_bytes(void) { return (size_t)SUMSQ_MAX_BLOCKS * sizeo
 int tad_sumsq_f32(const float* x, int64_t n, float* out, void* ws, size_t ws_bytes, tad_stream_t stream) {
   TAD_REQUIRE(x && out && ws && n >= 0, "sumsq: bad args");
   TAD_REQUIRE(ws_bytes >= tad_sumsq_workspace_bytes(), "sumsq: workspace too small");
+  TAD_REQUIRE_ALIGNED("sumsq", ws, 4);  // (the block partials are floats; x is peeled to its first 16-byte boundary: any float address)
   if (n == 0) return TAD_OK;
   int blocks = capped_grid(n, 256 * 16);
   if (blocks > SUMSQ_MAX_BLOCKS) blocks = SUMSQ_MAX_BLOCKS;
@@ -618,6 +636,7 @@ int tad_sumsq_f32(const float* x, int64_t n, float* out, void* ws, size_t ws_byt
 int tad_grad_norm_coef(const float* x, int64_t n, float inv_scale, float max_norm, float* out3, void* ws, size_t ws_bytes, tad_stream_t stream) {
   TAD_REQUIRE(x && out3 && ws && n > 0, "grad_norm_coef: bad args");
   TAD_REQUIRE(ws_bytes >= tad_sumsq_workspace_bytes(), "grad_norm_coef: workspace too small");
+  TAD_REQUIRE_ALIGNED("grad_norm_coef", ws, 4);  // (the block partials are floats; x is peeled to its first 16-byte boundary: any float address)
   int blocks = capped_grid(n, 256 * 16);
   if (blocks > SUMSQ_MAX_BLOCKS) blocks = SUMSQ_MAX_BLOCKS;
   hipLaunchKernelGGL(sumsq_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, n, (float*)ws);
@@ -628,6 +647,8 @@ int tad_grad_norm_coef(const float* x, int64_t n, float inv_scale, float max_nor
 
 int tad_split_bf16x3(const float* x, uint16_t* out, int64_t M, int K, int role_b, int stack, tad_stream_t stream) {
   TAD_REQUIRE(x && out && M > 0 && K > 0 && K % 4 == 0, "split_bf16x3: bad args (K must be a multiple of 4)");
+  TAD_REQUIRE_ALIGNED("split_bf16x3", x, 16);
+  TAD_REQUIRE_ALIGNED("split_bf16x3", out, 8);  // (float4 loads, 8-byte packed stores)
   hipLaunchKernelGGL(split_bf16x3_kernel, dim3(capped_grid(M * (K / 4), 256)), dim3(256), 0, (hipStream_t)stream, x, out, M, K, role_b, stack);
   return check_launch("split_bf16x3");
 }

@@ -78,8 +78,8 @@ extern "C" int tad_ema_update(const int64_t* tensors, int n_tensors, const int32
   TAD_REQUIRE(isfinite(decay) && isfinite(one_minus_decay) && decay >= 0.f && decay <= 1.f && one_minus_decay >= 0.f &&
                   one_minus_decay <= 1.f,
               "ema_update: decay=%g / one_minus_decay=%g must be finite and in [0, 1]", (double)decay, (double)one_minus_decay);
-  TAD_REQUIRE(((reinterpret_cast<uintptr_t>(tensors) | reinterpret_cast<uintptr_t>(chunks)) & 7) == 0,
-              "ema_update: tables must be 8-byte aligned");
+  TAD_REQUIRE_ALIGNED("ema_update", tensors, 8);
+  TAD_REQUIRE_ALIGNED("ema_update", chunks, 8);
   hipLaunchKernelGGL(ema_update_kernel, dim3((unsigned)n_chunks), dim3(EMA_THREADS), 0, (hipStream_t)stream, tensors, n_tensors,
                      reinterpret_cast<const int2*>(chunks), decay, one_minus_decay);
   return check_launch("ema_update");

@@ -309,7 +309,7 @@ extern "C" int tad_frame_resize(const uint8_t* x, void* out, int out_f32, const 
   TAD_REQUIRE(x && out && workspace, "frame_resize: null pointer");
   if (int rc = fr_shape_ok(B, n_vsets, H, W, S_h, S_w, "frame_resize")) return rc;
   TAD_REQUIRE(T > 0 && T <= 65535, "frame_resize: T=%d must be in [1, 65535]", T);
-  TAD_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "frame_resize: workspace must be 4-byte aligned");
+  TAD_REQUIRE_ALIGNED("frame_resize", workspace, 4);
   TAD_REQUIRE(workspace_bytes >= tad_frame_resize_workspace_bytes(B, n_vsets, S_h, S_w), "frame_resize: workspace of %zu bytes, need %zu",
               workspace_bytes, tad_frame_resize_workspace_bytes(B, n_vsets, S_h, S_w));
   FrNorm nm = {{0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}};

@@ -176,6 +176,14 @@ int tad_linear_fwd(const uint16_t* x, const uint16_t* w, const float* bias, void
   TAD_REQUIRE(epilogue >= TAD_EPI_BIAS && epilogue <= TAD_EPI_BIAS_RESIDUAL, "linear_fwd: bad epilogue %d", epilogue);
   TAD_REQUIRE(!rowscale || rows_per_scale > 0, "linear_fwd: rows_per_scale must be positive");
   TAD_REQUIRE(M > 0 && M < (1ll << 31), "linear_fwd: bad M");
+  // x, w: 16-byte LDS-DMA pieces; bias, y, preact, residual: 16-byte epilogue accesses; ws: 16-byte partial tiles; gamma, rowscale: scalar reads
+  TAD_REQUIRE_ALIGNED("linear_fwd", x, 16);
+  TAD_REQUIRE_ALIGNED("linear_fwd", w, 16);
+  TAD_REQUIRE_ALIGNED("linear_fwd", bias, 16);
+  TAD_REQUIRE_ALIGNED("linear_fwd", y, 16);
+  TAD_REQUIRE_ALIGNED("linear_fwd", preact, 16);
+  TAD_REQUIRE_ALIGNED("linear_fwd", residual, 16);
+  TAD_REQUIRE_ALIGNED("linear_fwd", ws, 16);
   GemmNT p{};
   p.A = x; p.B = w; p.C = y; p.bias = bias; p.c_bf16 = (y_dtype == TAD_OP16);
   p.M = (int)M; p.N = N; p.K = K;
@@ -195,6 +203,11 @@ int tad_linear_fwd_qkv(const uint16_t* x, const uint16_t* w, const float* q_bias
   TAD_REQUIRE(M > 0 && M < (1ll << 31), "linear_fwd_qkv: bad M");
   TAD_REQUIRE(q_prescale > 0.f, "linear_fwd_qkv: q_prescale must be positive (1 = plain)");
   TAD_REQUIRE(q_prescale == 1.f || N % 24 == 0, "linear_fwd_qkv: q_prescale needs N/3 = %d to be a multiple of 8", N / 3);
+  TAD_REQUIRE_ALIGNED("linear_fwd_qkv", x, 16);
+  TAD_REQUIRE_ALIGNED("linear_fwd_qkv", w, 16);
+  TAD_REQUIRE_ALIGNED("linear_fwd_qkv", q_bias, 16);
+  TAD_REQUIRE_ALIGNED("linear_fwd_qkv", v_bias, 16);
+  TAD_REQUIRE_ALIGNED("linear_fwd_qkv", y, 16);
   GemmNT p{};
   p.A = x; p.B = w; p.C = y; p.c_bf16 = (y_dtype == TAD_OP16);
   p.bias = q_bias; p.bias2 = v_bias; p.bias_seg = q_bias ? N / 3 : 0;
@@ -209,6 +222,13 @@ int tad_linear_bwd_weight_qkv(const uint16_t* dy, const uint16_t* x, float* dW, 
                               size_t ws_bytes, int64_t M, int N, int K, tad_stream_t stream) {
   TAD_REQUIRE(dy && x && dW && ws && dq_bias && dv_bias, "linear_bwd_weight_qkv: null pointer");
   TAD_REQUIRE(N > 0 && N % 12 == 0, "linear_bwd_weight_qkv: N=%d must be 3 x a multiple of 4", N);
+  // dy, x: 16-byte LDS-DMA pieces; the slab reduction reads ws and reads / writes every output as float4
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight_qkv", dy, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight_qkv", x, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight_qkv", dW, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight_qkv", dq_bias, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight_qkv", dv_bias, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight_qkv", ws, 16);
   return launch_gemm_tn(dy, x, dW, dq_bias, dv_bias, accumulate, ws, ws_bytes, M, N, K, (hipStream_t)stream);
 }
 
@@ -218,7 +238,15 @@ int tad_linear_bwd_weight_pair(const uint16_t* dy1, const uint16_t* x1, float* d
   TAD_REQUIRE(!db1b || db1, "linear_bwd_weight_pair: db1b (the v_bias third) comes with db1 (the q_bias third)");
   TAD_REQUIRE(!db1b || (N1 > 0 && N1 % 12 == 0), "linear_bwd_weight_pair: N1=%d must be 3 x a multiple of 4 for the split bias sums", N1);
   // the slab reduction reads and writes float4s through every output (dW2 is usually a view into the flat gradient buffer)
-  TAD_REQUIRE(((uintptr_t)dW1 | (uintptr_t)dW2 | (uintptr_t)db1 | (uintptr_t)db1b) % 16 == 0, "linear_bwd_weight_pair: dW1, dW2, db1 and db1b must be 16-byte aligned");
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight_pair", dW1, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight_pair", dW2, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight_pair", db1, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight_pair", db1b, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight_pair", dy1, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight_pair", x1, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight_pair", dy2, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight_pair", x2, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight_pair", ws, 16);
   return launch_gemm_tn_pair(dy1, x1, dW1, db1, db1b, N1, dy2, x2, dW2, N2, accumulate, ws, ws_bytes, M, K, (hipStream_t)stream);
 }
 
@@ -227,6 +255,11 @@ int tad_linear_bwd_input(const uint16_t* dy, const uint16_t* wT, void* dx, int d
   TAD_REQUIRE(dy && wT && dx, "linear_bwd_input: null pointer");
   TAD_REQUIRE(dx_dtype == TAD_F32 || dx_dtype == TAD_OP16, "linear_bwd_input: bad dx_dtype %d", dx_dtype);
   TAD_REQUIRE(M > 0 && M < (1ll << 31), "linear_bwd_input: bad M");
+  TAD_REQUIRE_ALIGNED("linear_bwd_input", dy, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_input", wT, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_input", dx, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_input", gelu_preact, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_input", ws, 16);
   GemmNT p{};
   p.A = dy; p.B = wT; p.C = dx; p.c_bf16 = (dx_dtype == TAD_OP16);
   p.M = (int)M; p.N = K; p.K = N;  // dx[M,K] = dy[M,N] * (wT[K,N])^T
@@ -239,6 +272,11 @@ int tad_linear_bwd_input(const uint16_t* dy, const uint16_t* wT, void* dx, int d
 int tad_linear_bwd_weight(const uint16_t* dy, const uint16_t* x, float* dW, float* db, int accumulate, void* ws, size_t ws_bytes,
                           int64_t M, int N, int K, tad_stream_t stream) {
   TAD_REQUIRE(dy && x && dW && ws, "linear_bwd_weight: null pointer");
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight", dy, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight", x, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight", dW, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight", db, 16);
+  TAD_REQUIRE_ALIGNED("linear_bwd_weight", ws, 16);
   return launch_gemm_tn(dy, x, dW, db, nullptr, accumulate, ws, ws_bytes, M, N, K, (hipStream_t)stream);
 }
 
@@ -246,6 +284,12 @@ int tad_linear_bwd_weight(const uint16_t* dy, const uint16_t* x, float* dW, floa
 int tad_patch_embed_fwd(const float* x, const uint16_t* w_bf16, const float* bias, const float* pos, float* out, uint16_t* cols, int B,
                         int C, int T, int H, int W, int tubelet, int patch, int D, tad_stream_t stream) {
   TAD_REQUIRE(x && w_bf16 && out && cols, "patch_embed_fwd: null pointer");
+  // (x: tad_im2col_tubelets answers for it; cols is also the GEMM's x operand: 16-byte LDS-DMA pieces whatever the patch size)
+  TAD_REQUIRE_ALIGNED("patch_embed_fwd", cols, 16);
+  TAD_REQUIRE_ALIGNED("patch_embed_fwd", w_bf16, 16);
+  TAD_REQUIRE_ALIGNED("patch_embed_fwd", bias, 16);
+  TAD_REQUIRE_ALIGNED("patch_embed_fwd", pos, 16);
+  TAD_REQUIRE_ALIGNED("patch_embed_fwd", out, 16);
   int rc = tad_im2col_tubelets(x, cols, B, C, T, H, W, tubelet, patch, stream);
   if (rc) return rc;
   const int ntok = (T / tubelet) * (H / patch) * (W / patch);
@@ -264,6 +308,11 @@ int tad_patch_embed_gemm(const uint16_t* cols, const uint16_t* w_bf16, const flo
   TAD_REQUIRE(cols && w_bf16 && out, "patch_embed_gemm: null pointer");
   TAD_REQUIRE(M > 0 && M < (1ll << 31) && ntok > 0 && M % ntok == 0, "patch_embed_gemm: M=%lld must be a positive multiple of ntok=%d",
               (long long)M, ntok);
+  TAD_REQUIRE_ALIGNED("patch_embed_gemm", cols, 16);
+  TAD_REQUIRE_ALIGNED("patch_embed_gemm", w_bf16, 16);
+  TAD_REQUIRE_ALIGNED("patch_embed_gemm", bias, 16);
+  TAD_REQUIRE_ALIGNED("patch_embed_gemm", pos, 16);
+  TAD_REQUIRE_ALIGNED("patch_embed_gemm", out, 16);
   GemmNT p{};
   p.A = cols; p.B = w_bf16; p.C = out; p.bias = bias; p.c_bf16 = 0;
   p.M = (int)M; p.N = D; p.K = K;
@@ -276,6 +325,12 @@ int tad_patch_embed_gemm(const uint16_t* cols, const uint16_t* w_bf16, const flo
 
 int tad_patch_embed_bwd(const uint16_t* dy_bf16, const uint16_t* cols, float* dW, float* db, void* ws, size_t ws_bytes, int64_t M, int D,
                         int K, tad_stream_t stream) {
+  TAD_REQUIRE(dy_bf16 && cols && dW && ws, "patch_embed_bwd: null pointer");
+  TAD_REQUIRE_ALIGNED("patch_embed_bwd", dy_bf16, 16);
+  TAD_REQUIRE_ALIGNED("patch_embed_bwd", cols, 16);
+  TAD_REQUIRE_ALIGNED("patch_embed_bwd", dW, 16);
+  TAD_REQUIRE_ALIGNED("patch_embed_bwd", db, 16);
+  TAD_REQUIRE_ALIGNED("patch_embed_bwd", ws, 16);
   return tad_linear_bwd_weight(dy_bf16, cols, dW, db, 0, ws, ws_bytes, M, D, K, stream);
 }
 

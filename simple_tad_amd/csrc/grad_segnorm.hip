@@ -174,12 +174,13 @@ extern "C" int tad_grad_segnorm(const float* grad, int64_t n, const tad_segnorm_
               nslots);
   TAD_REQUIRE(ws_bytes >= tad_grad_segnorm_workspace_bytes(nwork), "grad_segnorm: workspace of %zu bytes, need %zu", ws_bytes,
               tad_grad_segnorm_workspace_bytes(nwork));
-  TAD_REQUIRE((reinterpret_cast<uintptr_t>(grad) & 3) == 0 && (reinterpret_cast<uintptr_t>(ws) & 3) == 0 &&
-                  (reinterpret_cast<uintptr_t>(last) & 3) == 0 && (reinterpret_cast<uintptr_t>(counters) & 3) == 0,
-              "grad_segnorm: grad, last, counters and workspace must be 4-byte aligned");
-  TAD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 7) == 0 && (reinterpret_cast<uintptr_t>(work) & 7) == 0 &&
-                  (reinterpret_cast<uintptr_t>(acc) & 7) == 0,
-              "grad_segnorm: the tables and acc must be 8-byte aligned");
+  TAD_REQUIRE_ALIGNED("grad_segnorm", grad, 4);
+  TAD_REQUIRE_ALIGNED("grad_segnorm", ws, 4);
+  TAD_REQUIRE_ALIGNED("grad_segnorm", last, 4);
+  TAD_REQUIRE_ALIGNED("grad_segnorm", counters, 4);
+  TAD_REQUIRE_ALIGNED("grad_segnorm", table, 8);
+  TAD_REQUIRE_ALIGNED("grad_segnorm", work, 8);
+  TAD_REQUIRE_ALIGNED("grad_segnorm", acc, 8);
   hipStream_t st = (hipStream_t)stream;
   float* partial = static_cast<float*>(ws);
   hipLaunchKernelGGL(segnorm_reduce_kernel, dim3((unsigned)nwork), dim3(SEGNORM_THREADS), 0, st, grad, n, work, partial);

@@ -237,16 +237,18 @@ __global__ void u8_pairs_kernel(const uint8_t* __restrict__ frames, uint16_t* __
 
 // ---------------------------------------------------------------- host side
 // The one argument check of the family; `who` is the name the entry point's messages carry.  The uint8 entry points (mean3 / std3
-// given) also answer for their normalisation constants and for the alignment their 4-byte loads and 16-byte stores need.
+// given) also answer for their normalisation constants and for the alignment their 4-byte loads and 16-byte stores need (`src_name`: what
+// the entry point calls its source).
 static int check_args(const char* who, const void* src, const void* cols, int B, int C, int T, int H, int W, int tubelet, int patch,
-                      bool u8 = false, const float* mean3 = nullptr, const float* std3 = nullptr) {
+                      bool u8 = false, const float* mean3 = nullptr, const float* std3 = nullptr, const char* src_name = "x") {
   TAD_REQUIRE(src && cols && (!u8 || (mean3 && std3)), "%s: null pointer", who);
   TAD_REQUIRE(B > 0 && C > 0 && tubelet > 0 && patch > 0 && T % tubelet == 0 && H % patch == 0 && W % patch == 0,
               "%s: T/H/W must be multiples of tubelet/patch (got B=%d T=%d H=%d W=%d tub=%d p=%d)", who, B, T, H, W, tubelet, patch);
   TAD_REQUIRE(patch % 2 == 0, "%s: patch size must be even (got %d)", who, patch);
   if (u8) {
     TAD_REQUIRE(std3[0] != 0.f && std3[1] != 0.f && std3[2] != 0.f, "%s: zero std", who);
-    TAD_REQUIRE((((uintptr_t)src) & 3) == 0 && (((uintptr_t)cols) & 15) == 0, "%s: misaligned buffers (source 4 bytes, cols 16 bytes)", who);
+    TAD_REQUIRE_ALIGNED_AS(who, src, 4, src_name);
+    TAD_REQUIRE_ALIGNED(who, cols, 16);
   }
   return TAD_OK;
 }
@@ -255,6 +257,9 @@ template <int FMT>
 static int from_f32(const char* who, const float* x, void* cols, int B, int C, int T, int H, int W, int tubelet, int patch,
                     tad_stream_t stream) {
   if (int rc = check_args(who, x, cols, B, C, T, H, W, tubelet, patch)) return rc;
+  // wide items: float4 loads, 16-byte stores; pairs: float2 loads, one 4-byte word (16-bit formats) or a float2 (f32) per store
+  TAD_REQUIRE_ALIGNED(who, x, patch % 8 ? 8 : 16);
+  TAD_REQUIRE_ALIGNED(who, cols, patch % 8 ? (FMT == TAD_F32 ? 8 : 4) : 16);
   const int64_t pixels = (int64_t)B * C * T * H * W;  // (W is a multiple of every item width used: W % patch == 0)
   if (patch % 8)
     hipLaunchKernelGGL(f32_pairs_kernel<FMT>, dim3(capped_grid(pixels / 2, 256)), dim3(256), 0, (hipStream_t)stream, x, (out_t<FMT>*)cols, B,
@@ -268,9 +273,8 @@ static int from_f32(const char* who, const float* x, void* cols, int B, int C, i
 static int from_16(const char* who, const uint16_t* x, uint16_t* cols, int B, int C, int T, int H, int W, int tubelet, int patch,
                    tad_stream_t stream) {
   if (int rc = check_args(who, x, cols, B, C, T, H, W, tubelet, patch)) return rc;
-  const uintptr_t mask = patch % 8 ? 3 : 15;  // pairs move 4-byte words, wide items 16-byte chunks
-  TAD_REQUIRE((((uintptr_t)x) & mask) == 0 && (((uintptr_t)cols) & mask) == 0, "%s: misaligned buffers (x and cols %d bytes for patch %d)", who,
-              (int)mask + 1, patch);
+  TAD_REQUIRE_ALIGNED(who, x, patch % 8 ? 4 : 16);  // pairs move 4-byte words, wide items 16-byte chunks
+  TAD_REQUIRE_ALIGNED(who, cols, patch % 8 ? 4 : 16);
   const int64_t pixels = (int64_t)B * C * T * H * W;
   if (patch % 8)
     hipLaunchKernelGGL(w16_pairs_kernel, dim3(capped_grid(pixels / 2, 256)), dim3(256), 0, (hipStream_t)stream, x, cols, B, C, T, H, W, tubelet,
@@ -298,7 +302,7 @@ static int from_u8(const char* who, const uint8_t* frames, Slots slots, uint16_t
 template <int FMT>
 static int from_ring(const uint8_t* frames, uint16_t* cols, int B, int T, int H, int W, int tubelet, int patch, const float* mean3,
                      const float* std3, int bgr, int t_offset, tad_stream_t stream) {
-  if (int rc = check_args("im2col_u8", frames, cols, B, 3, T, H, W, tubelet, patch, true, mean3, std3)) return rc;
+  if (int rc = check_args("im2col_u8", frames, cols, B, 3, T, H, W, tubelet, patch, true, mean3, std3, "frames")) return rc;
   TAD_REQUIRE(t_offset >= 0 && t_offset < T, "im2col_u8: t_offset=%d outside [0, %d)", t_offset, T);
   return from_u8<FMT>("im2col_u8", frames, RingSlots{t_offset}, cols, B, T, H, W, tubelet, patch, mean3, std3, bgr, stream);
 }
@@ -341,8 +345,8 @@ int tad_im2col_frame_windows(const uint8_t* store, int64_t F, const int32_t* idx
   TAD_REQUIRE(F > 0, "%s: the store holds F=%lld frames (must be positive)", who, (long long)F);
   TAD_REQUIRE(cols_dtype == TAD_BF16 || cols_dtype == TAD_F16, "%s: cols_dtype=%d must be TAD_BF16 or TAD_F16", who, cols_dtype);
   TAD_REQUIRE(T > 0 && H > 0 && W > 0, "%s: T/H/W must be multiples of tubelet/patch (got T=%d H=%d W=%d)", who, T, H, W);
-  if (int rc = check_args(who, store, cols, B, 3, T, H, W, tubelet, patch, true, mean3, std3)) return rc;
-  TAD_REQUIRE((((uintptr_t)idx) & 3) == 0, "%s: misaligned buffers (idx 4 bytes)", who);
+  if (int rc = check_args(who, store, cols, B, 3, T, H, W, tubelet, patch, true, mean3, std3, "store")) return rc;
+  TAD_REQUIRE_ALIGNED(who, idx, 4);
   const TableSlots slots = {idx, F};
   if (cols_dtype == TAD_F16) return from_u8<TAD_F16>(who, store, slots, (uint16_t*)cols, B, T, H, W, tubelet, patch, mean3, std3, bgr, stream);
   return from_u8<TAD_BF16>(who, store, slots, (uint16_t*)cols, B, T, H, W, tubelet, patch, mean3, std3, bgr, stream);

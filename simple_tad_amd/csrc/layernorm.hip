@@ -225,6 +225,11 @@ int tad_layernorm_fwd(const float* x, const float* gamma, const float* beta, voi
   TAD_REQUIRE(rows > 0 && D > 0 && D % 4 == 0 && D <= 64 * 4 * LN_MAX_V, "layernorm_fwd: D=%d must be a multiple of 4 and <= %d", D,
               64 * 4 * LN_MAX_V);
   TAD_REQUIRE(y_dtype == TAD_F32 || y_dtype == TAD_OP16, "layernorm_fwd: bad y_dtype %d", y_dtype);
+  // float4 loads of x, gamma and beta; y: float4 stores (f32) or 8-byte packed stores (16-bit); mean and rstd are written float by float
+  TAD_REQUIRE_ALIGNED("layernorm_fwd", x, 16);
+  TAD_REQUIRE_ALIGNED("layernorm_fwd", gamma, 16);
+  TAD_REQUIRE_ALIGNED("layernorm_fwd", beta, 16);
+  TAD_REQUIRE_ALIGNED("layernorm_fwd", y, y_dtype == TAD_F32 ? 16 : 8);
   const int nv = (D / 4 + 63) / 64;
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   hipStream_t st = (hipStream_t)stream;
@@ -258,6 +263,18 @@ int tad_layernorm_bwd(const void* dy, int dy_dtype, const float* x, const float*
   TAD_REQUIRE(rows > 0 && D > 0 && D % 4 == 0 && D <= 64 * 4 * LN_MAX_V, "layernorm_bwd: unsupported D=%d", D);
   TAD_REQUIRE(dy_dtype == TAD_F32 || dy_dtype == TAD_OP16, "layernorm_bwd: bad dy_dtype %d", dy_dtype);
   TAD_REQUIRE(!rowscale || rows_per_scale > 0, "layernorm_bwd: rows_per_scale must be positive");
+  // float4 accesses to every row operand, the partials in ws and (in the reduction) dgamma / dbeta / colsum_dx; 8-byte pieces of the 16-bit
+  // tensors; mean, rstd and rowscale are read float by float
+  TAD_REQUIRE_ALIGNED("layernorm_bwd", dy, dy_dtype == TAD_F32 ? 16 : 8);
+  TAD_REQUIRE_ALIGNED("layernorm_bwd", x, 16);
+  TAD_REQUIRE_ALIGNED("layernorm_bwd", gamma, 16);
+  TAD_REQUIRE_ALIGNED("layernorm_bwd", dres, 16);
+  TAD_REQUIRE_ALIGNED("layernorm_bwd", dx, 16);
+  TAD_REQUIRE_ALIGNED("layernorm_bwd", dx_bf16, 8);
+  TAD_REQUIRE_ALIGNED("layernorm_bwd", dgamma, 16);
+  TAD_REQUIRE_ALIGNED("layernorm_bwd", dbeta, 16);
+  TAD_REQUIRE_ALIGNED("layernorm_bwd", colsum_dx, 16);
+  TAD_REQUIRE_ALIGNED("layernorm_bwd", ws, 16);
   const int blocks = ln_bwd_blocks(rows);
   if (ws_bytes < (size_t)3 * blocks * D * sizeof(float)) { set_error("layernorm_bwd: workspace too small"); return TAD_ENOSPACE; }
   const int rows_per_block = (int)((rows + blocks - 1) / blocks);

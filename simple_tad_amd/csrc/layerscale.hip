@@ -121,6 +121,26 @@ __global__ void branch_dropout_fwd_kernel(const float* __restrict__ u, const flo
 // 16-byte pieces); the 256 partial sums meet in a fixed tree (wave_sum inside each wave, then wave 0 .. 3 in order): no atomics, the same bits
 // every run.
 constexpr int LSG_BLOCK = 256;
+// four consecutive floats as one 16-byte access (VEC: p is 16-byte aligned) or one float at a time
+template <bool VEC>
+__device__ __forceinline__ void lsg_load4(const float* p, float (&v)[4]) {
+  if constexpr (VEC) {
+    const float4 q = *reinterpret_cast<const float4*>(p);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = p[e];
+  }
+}
+template <bool VEC>
+__device__ __forceinline__ void lsg_store4(float* p, const float (&v)[4]) {
+  if constexpr (VEC) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) p[e] = v[e];
+  }
+}
 template <bool VEC>
 __global__ __launch_bounds__(LSG_BLOCK) void layerscale_grads_kernel(const float* __restrict__ T, const float* __restrict__ W,
                                                                      const float* __restrict__ bias, const float* __restrict__ cs,
@@ -132,23 +152,29 @@ __global__ __launch_bounds__(LSG_BLOCK) void layerscale_grads_kernel(const float
   const float gm = gamma[n];
   const int64_t base = (int64_t)n * K;
   float acc = 0.f;
-  if constexpr (VEC) {
-    const float4* T4 = reinterpret_cast<const float4*>(T + base);
-    const float4* W4 = reinterpret_cast<const float4*>(W + base);
-    float4* dW4 = reinterpret_cast<float4*>(dW + base);
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  if (VEC || (K & 3) == 0) {
+    // Lane t owns the four-element pieces t, t + 256, ... of the row and keeps one partial sum per position inside a piece.  ONE loop body
+    // for both access widths (lsg_load4 / lsg_store4: a float4, or four floats when T, W or dW is not on 16 bytes), so that dgamma has the
+    // same bits wherever the tensors lie.
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
     for (int k = threadIdx.x; k < (K >> 2); k += LSG_BLOCK) {
-      const float4 t = T4[k];
-      const float4 w = W4[k];
-      float4 o = make_float4(gm * t.x, gm * t.y, gm * t.z, gm * t.w);
+      const int64_t at = base + 4 * (int64_t)k;
+      float t[4], w[4], o[4];
+      lsg_load4<VEC>(T + at, t);
+      lsg_load4<VEC>(W + at, w);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = gm * t[e];
       if (accumulate) {
-        const float4 p = dW4[k];
-        o.x += p.x; o.y += p.y; o.z += p.z; o.w += p.w;
+        float p[4];
+        lsg_load4<VEC>(dW + at, p);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] += p[e];
       }
-      dW4[k] = o;
-      a0 += t.x * w.x; a1 += t.y * w.y; a2 += t.z * w.z; a3 += t.w * w.w;
+      lsg_store4<VEC>(dW + at, o);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) a[e] += t[e] * w[e];
     }
-    acc = (a0 + a1) + (a2 + a3);
+    acc = (a[0] + a[1]) + (a[2] + a[3]);
   } else {
     for (int k = threadIdx.x; k < K; k += LSG_BLOCK) {
       const float t = T[base + k];

@@ -142,12 +142,16 @@ extern "C" {
 
 int tad_gather_rows_f32(const float* src, const int32_t* idx, float* out, int64_t n_out, int D, tad_stream_t stream) {
   TAD_REQUIRE(src && idx && out && n_out > 0 && D > 0 && D % 4 == 0, "gather_rows: bad args (D must be a multiple of 4)");
+  TAD_REQUIRE_ALIGNED("gather_rows", src, 16);
+  TAD_REQUIRE_ALIGNED("gather_rows", out, 16);  // (rows move as float4)
   hipLaunchKernelGGL(gather_rows_kernel, dim3(rows_grid(n_out)), dim3(256), 0, (hipStream_t)stream, src, idx, out, n_out, D / 4);
   return check_launch("gather_rows");
 }
 
 int tad_scatter_rows_f32(const float* src, const int32_t* idx, float* out, int64_t n_in, int D, tad_stream_t stream) {
   TAD_REQUIRE(src && idx && out && n_in > 0 && D > 0 && D % 4 == 0, "scatter_rows: bad args (D must be a multiple of 4)");
+  TAD_REQUIRE_ALIGNED("scatter_rows", src, 16);
+  TAD_REQUIRE_ALIGNED("scatter_rows", out, 16);
   hipLaunchKernelGGL(scatter_rows_kernel, dim3(rows_grid(n_in)), dim3(256), 0, (hipStream_t)stream, src, idx, out, n_in, D / 4);
   return check_launch("scatter_rows");
 }
@@ -156,6 +160,10 @@ int tad_mae_assemble(const float* x_vis, const float* mask_token, const float* p
                      float* out, int B, int n_vis, int n_mask, int D, tad_stream_t stream) {
   TAD_REQUIRE(x_vis && mask_token && pos && vis_idx && mask_idx && out, "mae_assemble: null pointer");
   TAD_REQUIRE(B > 0 && n_vis > 0 && n_mask > 0 && D > 0 && D % 4 == 0, "mae_assemble: bad shape");
+  TAD_REQUIRE_ALIGNED("mae_assemble", x_vis, 16);
+  TAD_REQUIRE_ALIGNED("mae_assemble", mask_token, 16);
+  TAD_REQUIRE_ALIGNED("mae_assemble", pos, 16);
+  TAD_REQUIRE_ALIGNED("mae_assemble", out, 16);
   hipLaunchKernelGGL(mae_assemble_kernel, dim3(rows_grid((int64_t)B * (n_vis + n_mask))), dim3(256), 0, (hipStream_t)stream, x_vis,
                      mask_token, pos, vis_idx, mask_idx, out, B, n_vis, n_mask, D / 4);
   return check_launch("mae_assemble");
@@ -186,6 +194,9 @@ int tad_mse_loss_blocks(int64_t n) {
 
 int tad_mse_loss(const float* pred, const float* target, int64_t n, float* partials, float* grad, tad_stream_t stream) {
   TAD_REQUIRE(pred && target && partials && n > 0 && n % 4 == 0, "mse_loss: bad args (n must be a positive multiple of 4)");
+  TAD_REQUIRE_ALIGNED("mse_loss", pred, 16);
+  TAD_REQUIRE_ALIGNED("mse_loss", target, 16);
+  TAD_REQUIRE_ALIGNED("mse_loss", grad, 16);  // (float4 accesses; partials is written float by float)
   hipLaunchKernelGGL(mse_kernel, dim3(tad_mse_loss_blocks(n)), dim3(256), 0, (hipStream_t)stream, pred, target, n / 4, 1.0f / (float)n,
                      partials, grad);
   return check_launch("mse_loss");

@@ -250,7 +250,7 @@ extern "C" int tad_multiscale_crop(const uint8_t* x, void* out, int out_f32, con
   TAD_REQUIRE(x && out && workspace, "multiscale_crop: null pointer");
   if (int rc = mc_shape_ok(B, n_hsets, n_vsets, Hs, Ws, S_h, S_w, "multiscale_crop")) return rc;
   TAD_REQUIRE(T > 0 && T <= 65535, "multiscale_crop: T=%d must be in [1, 65535]", T);
-  TAD_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "multiscale_crop: workspace must be 4-byte aligned");
+  TAD_REQUIRE_ALIGNED("multiscale_crop", workspace, 4);
   TAD_REQUIRE(workspace_bytes >= tad_multiscale_crop_workspace_bytes(B, n_hsets, n_vsets, S_h, S_w),
               "multiscale_crop: workspace of %zu bytes, need %zu", workspace_bytes,
               tad_multiscale_crop_workspace_bytes(B, n_hsets, n_vsets, S_h, S_w));

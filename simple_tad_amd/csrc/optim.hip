@@ -91,9 +91,11 @@ extern "C" int tad_adamw_step(float* param, const float* grad, float* exp_avg, f
   TAD_REQUIRE(n_groups > 0 && n_groups <= TAD_ADAMW_MAX_GROUPS, "adamw_step: n_groups=%d out of range (1..%d)", n_groups,
               TAD_ADAMW_MAX_GROUPS);
   TAD_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "adamw_step: bad betas / eps");
-  TAD_REQUIRE(((((uintptr_t)param) | ((uintptr_t)grad) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq)) & 15) == 0 &&
-                  (((uintptr_t)param_bf16) & 7) == 0,
-              "adamw_step: buffers must be 16-byte aligned");
+  TAD_REQUIRE_ALIGNED("adamw_step", param, 16);
+  TAD_REQUIRE_ALIGNED("adamw_step", grad, 16);
+  TAD_REQUIRE_ALIGNED("adamw_step", exp_avg, 16);
+  TAD_REQUIRE_ALIGNED("adamw_step", exp_avg_sq, 16);
+  TAD_REQUIRE_ALIGNED("adamw_step", param_bf16, 8);
   AdamGroups hp;
   for (int i = 0; i < n_groups; ++i) {
     TAD_REQUIRE(group_lr[i] >= 0.f && group_wd[i] >= 0.f, "adamw_step: negative lr / weight decay in group %d", i);

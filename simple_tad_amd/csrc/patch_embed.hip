@@ -174,8 +174,11 @@ extern "C" int tad_patch_embed_fwd_implicit(const float* x, const uint16_t* w_bf
   TAD_REQUIRE(patch == 16, "patch_embed_fwd_implicit: patch size %d (the implicit kernel is written for 16; use tad_patch_embed_fwd)", patch);
   TAD_REQUIRE(B > 0 && C > 0 && tubelet > 0 && T % tubelet == 0 && H % 16 == 0 && W % 16 == 0, "patch_embed_fwd_implicit: T/H/W must be multiples of tubelet/16 (got T=%d H=%d W=%d tub=%d)", T, H, W, tubelet);
   TAD_REQUIRE(D > 0 && D % 4 == 0, "patch_embed_fwd_implicit: D=%d must be a multiple of 4", D);
-  TAD_REQUIRE((((uintptr_t)x) & 15) == 0 && (((uintptr_t)w_bf16) & 15) == 0 && (((uintptr_t)out) & 15) == 0 && (((uintptr_t)bias) & 15) == 0 && (((uintptr_t)pos) & 15) == 0,
-              "patch_embed_fwd_implicit: buffers must be 16-byte aligned");
+  TAD_REQUIRE_ALIGNED("patch_embed_fwd_implicit", x, 16);
+  TAD_REQUIRE_ALIGNED("patch_embed_fwd_implicit", w_bf16, 16);
+  TAD_REQUIRE_ALIGNED("patch_embed_fwd_implicit", out, 16);
+  TAD_REQUIRE_ALIGNED("patch_embed_fwd_implicit", bias, 16);
+  TAD_REQUIRE_ALIGNED("patch_embed_fwd_implicit", pos, 16);
   PatchEmbedImplicit p{};
   p.x = x; p.w = w_bf16; p.bias = bias; p.pos = pos; p.out = out;
   p.C = C; p.T = T; p.H = H; p.W = W; p.tub = tubelet;

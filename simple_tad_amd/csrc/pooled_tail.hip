@@ -195,7 +195,9 @@ int tad_colsum_segments(const uint16_t* a, int op_dtype, float* S, void* ws, siz
   TAD_REQUIRE(B > 0 && N > 0 && K > 0 && B <= 65535, "colsum_segments: bad shape B=%d N=%d K=%d (B in 1..65535, N > 0, K > 0)", B, N, K);
   TAD_REQUIRE(K % 8 == 0, "colsum_segments: K=%d must be a multiple of 8", K);
   TAD_REQUIRE((int64_t)B * K < (int64_t)1 << 31, "colsum_segments: B * K exceeds 2^31");
-  TAD_REQUIRE(((uintptr_t)a & 15) == 0 && (((uintptr_t)S | (uintptr_t)ws) & 15) == 0, "colsum_segments: misaligned pointer (16 bytes)");
+  TAD_REQUIRE_ALIGNED("colsum_segments", a, 16);
+  TAD_REQUIRE_ALIGNED("colsum_segments", S, 16);
+  TAD_REQUIRE_ALIGNED("colsum_segments", ws, 16);
   if (ws_bytes < (size_t)B * TAD_POOL_SPLIT * (size_t)K * sizeof(float)) { set_error("colsum_segments: workspace too small"); return TAD_ENOSPACE; }
   if (op_dtype == TAD_F16) tad::op_f16::launch_colsum_segments_partial(a, (float*)ws, B, N, K, (hipStream_t)stream);
   else tad::op_bf16::launch_colsum_segments_partial(a, (float*)ws, B, N, K, (hipStream_t)stream);
@@ -209,8 +211,12 @@ int tad_pooled_linear(const float* S, const uint16_t* w, int op_dtype, const flo
   TAD_REQUIRE(op_dtype == TAD_BF16 || op_dtype == TAD_F16, "pooled_linear: op_dtype must be TAD_BF16 or TAD_F16");
   TAD_REQUIRE(B > 0 && N > 0 && D > 0 && K > 0, "pooled_linear: bad shape B=%d N=%d D=%d K=%d (all > 0)", B, N, D, K);
   TAD_REQUIRE(K % 8 == 0, "pooled_linear: K=%d must be a multiple of 8", K);
-  TAD_REQUIRE((((uintptr_t)S | (uintptr_t)w) & 15) == 0 && (((uintptr_t)xbar | (uintptr_t)out | (uintptr_t)bias | (uintptr_t)rowscale) & 3) == 0,
-              "pooled_linear: misaligned pointer (S, w: 16 bytes; the others: 4)");
+  TAD_REQUIRE_ALIGNED("pooled_linear", S, 16);
+  TAD_REQUIRE_ALIGNED("pooled_linear", w, 16);
+  TAD_REQUIRE_ALIGNED("pooled_linear", xbar, 4);
+  TAD_REQUIRE_ALIGNED("pooled_linear", out, 4);
+  TAD_REQUIRE_ALIGNED("pooled_linear", bias, 4);
+  TAD_REQUIRE_ALIGNED("pooled_linear", rowscale, 4);
   TAD_REQUIRE(xbar != out, "pooled_linear: out must not alias xbar");
   if (op_dtype == TAD_F16) tad::op_f16::launch_pooled_linear(S, w, bias, rowscale, xbar, out, B, N, D, K, (hipStream_t)stream);
   else tad::op_bf16::launch_pooled_linear(S, w, bias, rowscale, xbar, out, B, N, D, K, (hipStream_t)stream);
@@ -223,7 +229,9 @@ int tad_gelu_grad_bcast(const float* t, const uint16_t* h, uint16_t* dh, int op_
   TAD_REQUIRE(B > 0 && N > 0 && K > 0 && B <= 65535 && (N + GG_ROWS - 1) / GG_ROWS <= 65535,
               "gelu_grad_bcast: bad shape B=%d N=%d K=%d (B in 1..65535, N > 0, K > 0)", B, N, K);
   TAD_REQUIRE(K % 8 == 0, "gelu_grad_bcast: K=%d must be a multiple of 8", K);
-  TAD_REQUIRE((((uintptr_t)t | (uintptr_t)h | (uintptr_t)dh) & 15) == 0, "gelu_grad_bcast: misaligned pointer (16 bytes)");
+  TAD_REQUIRE_ALIGNED("gelu_grad_bcast", t, 16);
+  TAD_REQUIRE_ALIGNED("gelu_grad_bcast", h, 16);
+  TAD_REQUIRE_ALIGNED("gelu_grad_bcast", dh, 16);
   if (op_dtype == TAD_F16) tad::op_f16::launch_gelu_grad_bcast(t, h, dh, B, N, K, (hipStream_t)stream);
   else tad::op_bf16::launch_gelu_grad_bcast(t, h, dh, B, N, K, (hipStream_t)stream);
   return check_launch("gelu_grad_bcast");

@@ -94,6 +94,7 @@ int tad_gelu_bwd_f32(const float* dy, const float* h, float* dh, int64_t n, tad_
 
 int tad_colsum_f32(const float* a, float* out, int64_t M, int N, tad_stream_t stream) {
   TAD_REQUIRE(a && out && M > 0 && N > 0, "colsum_f32: bad args");
+  if (N % 4 == 0) TAD_REQUIRE_ALIGNED("colsum_f32", a, 16);  // (the wide kernel reads float4; the any-N kernel single floats)
   if (N % 4 == 0) hipLaunchKernelGGL(colsum_f32_wide_kernel, dim3((N + 15) / 16), dim3(1024), 0, (hipStream_t)stream, a, out, M, N);
   else hipLaunchKernelGGL(colsum_f32_kernel, dim3((N + 63) / 64), dim3(256), 0, (hipStream_t)stream, a, out, M, N);
   return check_launch("colsum_f32");

@@ -469,8 +469,8 @@ extern "C" int tad_randaug_apply(const uint8_t* x, uint8_t* out, const int32_t* 
     return TAD_OK;
   }
   TAD_REQUIRE(table && workspace, "randaug_apply: null pointer");
-  TAD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 3) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
-              "randaug_apply: table must be 4-byte and workspace 256-byte aligned");
+  TAD_REQUIRE_ALIGNED("randaug_apply", table, 4);
+  TAD_REQUIRE_ALIGNED("randaug_apply", workspace, 256);
   TAD_REQUIRE(workspace_bytes >= tad_randaug_workspace_bytes(n_layers, B, T, H, W), "randaug_apply: workspace of %zu bytes, need %zu",
               workspace_bytes, tad_randaug_workspace_bytes(n_layers, B, T, H, W));
   uint8_t* stats = static_cast<uint8_t*>(workspace);

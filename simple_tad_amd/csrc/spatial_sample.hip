@@ -190,7 +190,7 @@ extern "C" int tad_spatial_sample(const void* x, int x_u8, float* out, const flo
                                   size_t workspace_bytes, int B, int T, int H, int W, int S, tad_stream_t stream) {
   TAD_REQUIRE(x && out && workspace, "spatial_sample: null pointer");
   if (int rc = ss_shape_ok(B, T, H, W, S, "spatial_sample")) return rc;
-  TAD_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "spatial_sample: workspace must be 4-byte aligned");
+  TAD_REQUIRE_ALIGNED("spatial_sample", workspace, 4);
   TAD_REQUIRE(workspace_bytes >= tad_spatial_sample_workspace_bytes(B, T), "spatial_sample: workspace of %zu bytes, need %zu",
               workspace_bytes, tad_spatial_sample_workspace_bytes(B, T));
   TAD_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "spatial_sample: out must be 4-byte aligned");

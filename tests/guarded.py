@@ -120,14 +120,19 @@ class GuardedArena:
             region.view(view).fill_(val)
         elif dtype == torch.uint8 and role == "workspace":  # scratch is read as f32 partial sums
             view, val = poison_bits(torch.float32, self.poison)
-            region.view(view).fill_(val)
+            a, b = lo + (-lo) % 4, hi - hi % 4  # (whole 4-byte words; the bytes an offset= placement leaves around them: 0xFF)
+            self.buf[a:b].view(view).fill_(val)
+            self.buf[lo:a].fill_(0xFF)
+            self.buf[b:hi].fill_(0xFF)
         elif dtype == torch.uint8:
             region.fill_(0xFF)
         else:
             raise ValueError(f"guards around a {dtype} tensor need index_range= or guard_pattern= (no wild indices / addresses)")
 
-    def place(self, tensor_or_shape, dtype=None, role="input", name=None, index_range=None, guard_pattern=None, pitch=None, fill=None):
+    def place(self, tensor_or_shape, dtype=None, role="input", name=None, index_range=None, guard_pattern=None, pitch=None, fill=None, offset=0):
         """A view of the arena: 256-byte aligned start, a guard band immediately before the first and immediately after the last byte.
+        offset=k (bytes, a multiple of the element size, default 0): the view starts k bytes behind the 256-byte boundary instead -- the
+        guard before it grows by k bytes and still ends immediately before the first byte (tests/test_alignment_gpu.py).
         tensor_or_shape: a tensor (its values become the body) or a shape (then ``dtype`` is required).
         role: input | output | inout | workspace.  output / workspace bodies without data are filled with NaN of their dtype
         (``fill`` overrides: torch.zeros); integer ones with 0x7F bytes.
@@ -139,6 +144,8 @@ class GuardedArena:
         dtype = data.dtype if data is not None else dtype
         assert dtype is not None, "place(shape) needs a dtype"
         item = _itemsize(dtype)
+        offset = int(offset)
+        assert offset >= 0 and offset % item == 0, "offset= is in bytes and must keep the elements on their own grid"
         numel = 1
         for s in shape:
             numel *= s
@@ -146,7 +153,7 @@ class GuardedArena:
         p = Placement()
         p.name, p.role, p.dtype, p.shape = name or f"#{len(self.placements)}", role, dtype, shape
         p.lo = self.cursor                      # (on the 256-byte grid)
-        p.start = p.lo + g
+        p.start = p.lo + g + offset
         p.end = p.start + numel * item          # no rounding: the first guard byte is the byte after the last element
         p.hi = p.end + g + (-(p.end + g - self.base)) % ALIGN  # (back on the grid: a whole number of guard elements of any type)
         if p.hi > self.buf.numel():
@@ -163,8 +170,10 @@ class GuardedArena:
             if dtype in _BITS:
                 body.fill_(float("nan"))
             elif dtype == torch.uint8 and role == "workspace":
-                whole = p.start + (p.end - p.start) // 4 * 4
-                self.buf[p.start:whole].view(torch.float32).fill_(float("nan"))
+                first = p.start + (-p.start) % 4  # (whole 4-byte words; an offset= placement leaves up to 3 bytes in front of them)
+                whole = max(first, p.end - p.end % 4)
+                self.buf[first:whole].view(torch.float32).fill_(float("nan"))
+                self.buf[p.start:first].fill_(0xFF)
                 self.buf[whole:p.end].fill_(0xFF)
             else:
                 self.buf[p.start:p.end].fill_(0x7F)

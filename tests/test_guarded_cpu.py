@@ -222,3 +222,38 @@ def test_guard_pattern_keeps_table_rows_valid(arena):
     mem, t0 = raw(arena, ta)
     assert torch.equal(mem[t0 - 8:t0].reshape(2, 4), table[:1].repeat(2, 1)) and not mem[t0 + 8:t0 + 64].any()
     arena.verify()
+
+
+@pytest.mark.parametrize("dtype,offsets", [(torch.float32, (0, 4, 8, 12)), (torch.bfloat16, (0, 2, 6, 14)), (torch.uint8, (0, 1, 7, 15)),
+                                           (torch.int64, (0, 8))])
+def test_place_offset_moves_the_body_and_keeps_the_guards_tight(arena, dtype, offsets):
+    """place(offset=k): the view starts k bytes behind a 256-byte boundary, the guard before it still ends immediately before its first
+    byte, the guard after it still starts at the byte after its last, both at least as wide as without the offset; the next placement
+    is back on the 256-byte grid; a stray write one element in front of the shifted body is reported inside the element in front of its first byte"""
+    item = torch.empty((), dtype=dtype).element_size()
+    kw = dict(index_range=9) if dtype == torch.int64 else {}
+    for k in offsets:
+        arena.reset()
+        data = (torch.arange(ROWS * COLS) % 7).to(dtype).reshape(ROWS, COLS)
+        t = arena.place(data, role="input", name="shifted", offset=k, **kw)
+        nxt = arena.place((3, 5), torch.float32, role="output", name="next")
+        p = arena.placement_of(t)
+        assert t.data_ptr() % 256 == k and p.lo % 256 == arena.base % 256
+        assert p.start - p.lo == GuardedArena.guard_bytes(data.shape, dtype) + k and p.hi - p.end >= GuardedArena.guard_bytes(data.shape, dtype)
+        assert p.end - p.start == data.numel() * item and nxt.data_ptr() % 256 == 0
+        assert same_bits(t, data)
+        mem, t0 = raw(arena, t)
+        if dtype in (torch.float32, torch.bfloat16):
+            view, pat = poison_bits(dtype, arena.poison)
+            assert int(bits(mem[t0 - 1:t0])) == pat and int(bits(mem[t0 + t.numel():t0 + t.numel() + 1])) == pat
+            assert int(bits(mem[t0 - k // item - 1:t0 - k // item])) == pat, "the bytes the offset skipped are guard bytes too"
+        elif dtype == torch.uint8:
+            assert int(mem[t0 - 1]) == 0xFF and int(mem[t0 + t.numel()]) == 0xFF
+        else:
+            assert 0 <= int(mem[t0 - 1]) < 9 and 0 <= int(mem[t0 + t.numel()]) < 9
+        arena.verify()
+        mem[t0 - 1] = 100 if dtype != torch.uint8 else 3  # (differs from every guard value)
+        with pytest.raises(GuardViolation, match=rf"guard before shifted.*offsets -[1-{item}] \.\. -\d relative to its first byte"):
+            arena.verify()
+    with pytest.raises(AssertionError):
+        arena.place(torch.zeros(4), offset=2)  # not on the f32 element grid
