@@ -6,7 +6,11 @@ for bit) and the kernels of csrc/randaug.hip, which state the same arithmetic.  
 
 Frames are uint8 [H, W, 3] (RGB).  ``apply(frame, name, arg, resample, fill)`` carries out one operator on one frame: ``name`` one of
 the reference's op names, ``arg`` the value its level function returned (None for the ops without one), ``resample`` BILINEAR or
-BICUBIC for the geometric ops."""
+BICUBIC for the geometric ops.
+
+Fixture G25 (tests/golden/g25_rand_augment_shapes.npz, tools/make_goldens_randaug_shapes.py) holds PIL's results for the same per-op
+cases at the shapes ``SHAPES`` on the frames of ``frames_at`` (any shape), as SHA-256 per output frame: tests/test_randaug_shapes_cpu.py
+holds the restatement to them, tests/test_randaug_shapes_gpu.py the kernels to the restatement."""
 import hashlib
 import math
 
@@ -72,6 +76,78 @@ def frames():
                 v.flat[rng.integers(0, H * W)] = lo
                 v.flat[(np.argmin(v) + 1 + rng.integers(0, H * W - 1)) % (H * W)] = hi
             out[b, t, :, :, c] = v.astype(np.uint8)
+    return out
+
+
+# fixture G25 (tests/golden/g25_rand_augment_shapes.npz, tools/make_goldens_randaug_shapes.py): the per-op cases at other shapes
+# (B, T, H, W): frames below 3 pixels in a direction, one row, one column, a short pointwise item, a real frame, two non-square mid sizes
+SHAPES = ((2, 3, 1, 1), (2, 3, 1, 7), (2, 3, 7, 1), (2, 3, 2, 2), (2, 3, 3, 3), (2, 3, 2, 9), (2, 3, 3, 40), (1, 2, 224, 224),
+          (2, 2, 45, 80), (2, 2, 67, 63), (1, 4, 9, 11))
+SHAPES_SEED = 26          # (a seed at which the 224 x 224 frames show both ends of the Equalize cut: tests/test_randaug_shapes_cpu.py)
+KINDS = ("gradient", "full", "constant", "two-level")
+
+
+def shape_key(shape):
+    return "x".join(str(int(v)) for v in shape)
+
+
+def case_arg(value, name):
+    """a stored argument (float64, NaN = the op has none) as ``apply`` takes it"""
+    value = float(value)
+    return None if np.isnan(value) else (int(value) if name.startswith(("Posterize", "Solarize")) else value)
+
+
+def golden_args(g, shape):
+    """{case key: argument} of one shape of fixture G25"""
+    cases = op_cases()
+    assert [c[0] for c in cases] == list(g["cases"])
+    return {c[0]: case_arg(a, c[1]) for c, a in zip(cases, g[f"{shape_key(shape)}.args"])}
+
+
+def kind_of(b, t, T):
+    """the kind of frame (b, t) of ``frames_at``: frames run through the four kinds in memory order"""
+    return KINDS[(b * T + t) % 4]
+
+
+def frames_at(B, T, H, W, seed):
+    """seeded input clips uint8 [B, T, H, W, 3] at any shape.  The kind of a frame is fixed by (b, t) (``kind_of``):
+      gradient   a smooth gradient plus noise per channel, cut to a drawn sub-range (as ``frames()``)
+      full       the same on 0..255 in every channel
+      constant   channel 1 holds one value, the others are gradients
+      two-level  channel 2 holds two values, the upper one in more than H * W - 255 pixels (two occupied bins; Equalize's step is 0
+                 once H * W >= 256), the others are gradients
+    Where a frame has two pixels or more, both ends of a gradient channel's range occur."""
+    rng = np.random.default_rng([seed, B, T, H, W])
+    n = H * W
+    yy, xx = np.mgrid[0:H, 0:W]
+    out = np.zeros((B, T, H, W, 3), dtype=np.uint8)
+    for b in range(B):
+        for t in range(T):
+            kind = kind_of(b, t, T)
+            for c in range(3):
+                lo = int(rng.integers(0, 120))
+                hi = int(rng.integers(lo + 40, 256))
+                ax, ay = rng.uniform(-1, 1, 2)
+                noise = rng.normal(0, 12, (H, W))
+                spot = rng.integers(0, n, 2)
+                few = int(rng.integers(1, 255))
+                if kind == "full":
+                    lo, hi = 0, 255
+                if kind == "constant" and c == 1:
+                    out[b, t, :, :, c] = lo
+                    continue
+                if kind == "two-level" and c == 2:
+                    v = np.full(n, hi, dtype=np.uint8)
+                    v[rng.permutation(n)[:min(few, n // 2)]] = lo
+                    out[b, t, :, :, c] = v.reshape(H, W)
+                    continue
+                g = ax * (xx - W / 2) / W + ay * (yy - H / 2) / H
+                g = (g - g.min()) / max(g.max() - g.min(), 1e-9)
+                v = np.clip(np.rint(lo - 20 + g * (hi - lo + 40) + noise), lo, hi)
+                if n >= 2:
+                    v.flat[spot[0]] = lo
+                    v.flat[(spot[0] + 1 + spot[1] % (n - 1)) % n] = hi
+                out[b, t, :, :, c] = v.astype(np.uint8)
     return out
 
 
