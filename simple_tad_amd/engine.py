@@ -113,6 +113,36 @@ def create_optimizer(model, lr, weight_decay=0.05, betas=(0.9, 0.999), eps=1e-8,
     return torch.optim.AdamW(groups, lr=lr, betas=betas, eps=eps, weight_decay=0.0, fused=on_gpu)
 
 
+def freeze_layers(model, spec) -> int:
+    """``--freeze_layers`` of the reference's fine-tuning scripts (run_frame_finetuning.py:143, 465-485), its rule restated with its
+    substring tests: for ``spec`` starting with ``"first N blocks"``, N = int(spec.split(";")[1]) and, per named parameter,
+      * ``"blocks"`` in the name: layer = int(name.split(".")[1]); below N it is frozen unless ``"norm"`` is in the name, from N on
+        it is trainable;
+      * else ``"patch_embed"`` in the name: frozen;
+      * everything else (fc_norm, norm, head, ...): trainable.
+    So the eight Linear tensors, q_bias / v_bias and gamma_1 / gamma_2 of the first N blocks and the patch projection are frozen, and
+    the norms of the frozen blocks keep training.  Any other ``spec`` changes nothing (as in the reference) and warns once.  Returns
+    the number of parameters the rule froze.  Takes a bare model or a DataParallel wrapper; call it before ``create_optimizer`` (and
+    before wrapping, so that the flat gradient layout holds the trainable parameters only): ``get_parameter_groups`` drops frozen
+    parameters, and the 16-bit Functions then launch no weight gradient for them and keep no operand for one (ops.set_skip_frozen)."""
+    inner = model.module if isinstance(model, DataParallel) else model
+    if not (isinstance(spec, str) and spec.startswith("first N blocks")):
+        import warnings
+        warnings.warn(f"freeze_layers: {spec!r} is not of the form 'first N blocks;N'; nothing is frozen")
+        return 0
+    n_blocks = int(spec.split(";")[1])
+    frozen = 0
+    for name, param in inner.named_parameters():
+        if "blocks" in name:
+            param.requires_grad = not (int(name.split(".")[1]) < n_blocks and "norm" not in name)
+        elif "patch_embed" in name:
+            param.requires_grad = False
+        else:
+            param.requires_grad = True
+        frozen += not param.requires_grad
+    return frozen
+
+
 def get_grad_norm_(parameters, norm_type: float = 2.0) -> torch.Tensor:
     """utils.get_grad_norm_ (utils.py:415-427) for norm_type 2: norm(stack(norm(g))) == sqrt(sum ||g||^2).
     On GPU the sum of squares runs through tad_sumsq_f32 (one pass over the gradients)."""
@@ -255,7 +285,7 @@ class NativeScalerWithGradNormCount:
             else:
                 norm = get_grad_norm_(parameters)
         optimizer.step()
-        ops.invalidate_weight_cache()  # fused optimizers do not bump Parameter._version (see ops._cached)
+        ops.invalidate_weight_cache(keep_static=True)  # fused optimizers do not bump Parameter._version (see ops._cached)
         return norm
 
     def state_dict(self):

@@ -29,18 +29,26 @@ from ._lib import EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, TadError
 #     entry for them (``fresh=True``); backward derives the transposed copy at backward time (weights do not change between the
 #     two);
 #   * only forwards without autograd (inference) reuse cached copies, keyed by (version, data_ptr), and ``invalidate_weight_cache``
-#     (called by this package's optimizer wrapper after every step) clears them explicitly.
+#     (called by this package's optimizer wrapper after every step) clears them explicitly;
+#   * a FROZEN weight (``requires_grad == False``, ``set_skip_frozen`` on) is in no optimizer, so nothing changes it behind autograd's
+#     back: its copies are static (``_static``) in training too, made once and kept until its ``_version`` or storage, the precision
+#     mode or a caller's ``invalidate_weight_cache()`` changes.  An optimizer's own step spares them (``keep_static``): it writes only
+#     the parameters it holds.
 _wcache = {}  # id(param) -> {"ref": weakref, "key": (version, data_ptr), kind: tensor}
+_static = {}  # id(param) -> the same layout, for frozen weights in differentiated forwards / backwards
 _MAKERS = {}
 
 
-def invalidate_weight_cache():
+def invalidate_weight_cache(keep_static: bool = False):
     """Drop every cached bf16 weight copy AND every optimizer-written operand mirror (call after modifying parameters by any means
     that may not bump ``_version``: ``p.data.copy_``, a torch fused optimizer step, EMA swaps).  optim.FusedAdamW calls this and then
-    re-registers the mirrors it has just rewritten."""
+    re-registers the mirrors it has just rewritten.  ``keep_static``: for an optimizer's step, which leaves frozen parameters alone --
+    the static copies of frozen weights survive."""
     global _weight_epoch
     _weight_epoch += 1
     _wcache.clear()
+    if not keep_static:
+        _static.clear()
     _mirrors.clear()
     _mirrors_t.clear()
 
@@ -55,7 +63,7 @@ def weight_epoch() -> int:
 
 def cached_weight_tensors():
     """every bf16 weight copy currently cached (a captured graph keeps this list so that the addresses it baked in stay allocated)"""
-    return [v for ent in _wcache.values() for k, v in ent.items() if k not in ("ref", "key")]
+    return [v for tab in (_wcache, _static) for ent in tab.values() for k, v in ent.items() if k not in ("ref", "key")]
 
 
 def _w2d(p):
@@ -113,10 +121,15 @@ def _sink(p):
     return ent
 
 
-def linear_dw(dy, x, w, b=None, loose_bias=False):
+def linear_dw(dy, x, w, b=None, loose_bias=False, need=(True, True)):
     """(dW, db) of a Linear for autograd.  With gradient sinks on the parameters the gradients are accumulated in place and None is
     returned in their stead.  ``loose_bias``: the column sums of dy are wanted as a tensor although there is no bias Parameter to
-    sink them into (qkv: they are split into q_bias / v_bias afterwards)."""
+    sink them into (qkv: they are split into q_bias / v_bias afterwards).  ``need`` = (weight, bias): a frozen weight gets no launch
+    (``x`` may be None then) and a frozen bias no column sums; a trainable bias beside a frozen weight is one column-sum launch."""
+    if not need[1]:
+        b, loose_bias = None, False
+    if not need[0]:
+        return None, (K.colsum_bf16(dy) if (b is not None or loose_bias) else None)
     sw = _sink(w)
     sb = _sink(b) if b is not None else None
     if sw is not None and (b is None or sb is not None):
@@ -149,14 +162,23 @@ def _cached(p: torch.Tensor, kind: str, fresh: bool = False):
         m = _mirror_of(p, kind == "t")
         if m is not None:
             return m
+    tab = _wcache
     if fresh:
         _wcache.pop(pid, None)
-        return _MAKERS[kind](p)
-    ent = _wcache.get(pid)
+        if p.requires_grad or not _skip_frozen or kind not in ("n", "t"):
+            if _static:
+                _static.pop(pid, None)  # (a weight that was frozen once and trains again)
+            return _MAKERS[kind](p)
+        tab = _static  # a frozen weight: nothing updates it between steps
+    elif not p.requires_grad and _skip_frozen and kind in ("n", "t") and getattr(_outer, "grad", None):
+        # a forward under grad mode none of whose inputs is differentiable (a wholly frozen patch embedding, the blocks of a linear
+        # probe) is part of a training step all the same; without grad mode (inference, evaluation) the cache above serves as before
+        tab = _static
+    ent = tab.get(pid)
     key = (p._version, p.data_ptr())
     if ent is None or ent["ref"]() is not p or ent["key"] != key:
-        ent = {"ref": weakref.ref(p, lambda _r, pid=pid: _wcache.pop(pid, None)), "key": key}
-        _wcache[pid] = ent
+        ent = {"ref": weakref.ref(p, lambda _r, pid=pid, tab=tab: tab.pop(pid, None)), "key": key}
+        tab[pid] = ent
     if kind not in ent:
         ent[kind] = _MAKERS[kind](p)
     return ent[kind]
@@ -292,6 +314,35 @@ def _differentiated(ctx) -> bool:
     g = getattr(_outer, "grad", None)
     return (True if g is None else g) and any(ctx.needs_input_grad)
 
+
+
+# --------------------------------------------------------------------------- frozen parameters
+# A parameter with ``requires_grad == False`` (engine.freeze_layers) gets no weight-gradient launch and no bias column sums, its
+# Function returns None for it, and the forward keeps none of the operands only that gradient would read (xn1 / xn2 / a of a Block,
+# the patch matrix).  The input-gradient chain is the same launches on the same bits.  Off: every gradient is computed and every
+# operand kept whatever the flags say, and frozen weights are re-cast every step (the path before the switch existed; tests, A/B runs).
+_skip_frozen = True
+
+
+def set_skip_frozen(enabled: bool):
+    """honour ``requires_grad`` per parameter in the 16-bit Functions (default) or, off, compute and save everything.  Sampled by each
+    forward: an autograd node's backward follows the setting its own forward ran under."""
+    global _skip_frozen
+    _skip_frozen = bool(enabled)
+
+
+def get_skip_frozen() -> bool:
+    return _skip_frozen
+
+
+def _needs(ctx, n: int):
+    """per input 0..n-1 of a Function: may its gradient be wanted?  (ctx.needs_input_grad, or all True with the switch off; an absent
+    -- None -- parameter is the callers' affair either way)"""
+    if not _skip_frozen:
+        return (True,) * n
+    return tuple(bool(f) for f in ctx.needs_input_grad[:n])
+
+
 # --------------------------------------------------------------------------- LayerNorm
 class LayerNormFn(_Fn):
     """nn.LayerNorm(D, eps) on f32 rows -> f32 (modeling_finetune.py:143,149,270)."""
@@ -322,9 +373,17 @@ IMPLICIT_PATCH_EMBED_MIN_TILES = 512
 
 def _patch_embed_backward(ctx, dy, trailing: int):
     """(dweight, dbias) of a 16-bit patch embedding from its saved patch matrix, then ``trailing`` Nones for the inputs after bias"""
-    (cols,) = ctx.saved_tensors
     weight, bias = ctx.params
+    need_w, need_b = ctx.need
+    need_b = need_b and bias is not None
+    if not (need_w or need_b):
+        return (None, None) + (None,) * trailing
     dyb = K.cast_bf16(_f32c(dy).reshape(-1, dy.shape[-1]))
+    if not need_w:  # a frozen projection: no patch matrix was kept
+        return (None, K.colsum_bf16(dyb)) + (None,) * trailing
+    (cols,) = ctx.saved_tensors
+    if not need_b:
+        bias = None
     kw = weight.numel() // weight.shape[0]
     if cols.shape[1] != kw:  # padded K: the gradient of the padding columns is dropped (no in-place sink for a [D, ldk] result)
         dWp, db = K.linear_bwd_weight(dyb, cols, want_bias=bias is not None)
@@ -345,15 +404,19 @@ class PatchEmbedFn(_Fn):
         # columns up to tad_patch_embed_ldk (1216); a pure configuration change for the callers
         ldk = K.patch_embed_ldk(xc.shape[1], tubelet, patch)
         ntok_ = (xc.shape[2] // tubelet) * (xc.shape[3] // patch) * (xc.shape[4] // patch)
-        if not _differentiated(ctx) and -(-xc.shape[0] * ntok_ // 128) * -(-weight.shape[0] // 128) >= IMPLICIT_PATCH_EMBED_MIN_TILES:
-            # nothing is kept for a backward pass (eval / no_grad / inference): the implicit GEMM reads the clip itself and
-            # writes no patch matrix; bit-identical to the explicit form below, which the training step needs for its weight gradient
-            out = K.patch_embed_fwd_implicit(xc, w_bf16(weight, False), _f32c(bias), _f32c(pos), tubelet, patch)
+        ctx.need = _needs(ctx, 3)[1:]
+        keeps_cols = _differentiated(ctx) and ctx.need[0]
+        if not keeps_cols and -(-xc.shape[0] * ntok_ // 128) * -(-weight.shape[0] // 128) >= IMPLICIT_PATCH_EMBED_MIN_TILES:
+            # nothing is kept for a backward pass (eval / no_grad / inference, or a frozen projection): the implicit GEMM
+            # reads the clip itself and writes no patch matrix; bit-identical to the explicit form below, which the training step needs
+            # for its weight gradient
+            out = K.patch_embed_fwd_implicit(xc, w_bf16(weight, _differentiated(ctx)), _f32c(bias), _f32c(pos), tubelet, patch)
             if out is not None:
                 ctx.params = (weight, bias)
                 return out
         out, cols = K.patch_embed_fwd(xc, K.pad_k(w_bf16(weight, _differentiated(ctx)), ldk), _f32c(bias), _f32c(pos), tubelet, patch)
-        ctx.save_for_backward(cols)
+        if ctx.need[0]:
+            ctx.save_for_backward(cols)
         ctx.params = (weight, bias)
         return out
 
@@ -378,7 +441,9 @@ class PatchEmbed16Fn(_Fn):
             cols = K.im2col_tubelets(xc.float(), tubelet, patch, dtype=xc.dtype)
         ntok = (xc.shape[2] // tubelet) * (xc.shape[3] // patch) * (xc.shape[4] // patch)
         out = K.patch_embed_gemm(cols, K.pad_k(w_bf16(weight, _differentiated(ctx)), cols.shape[1]), _f32c(bias), _f32c(pos), ntok)
-        ctx.save_for_backward(cols)
+        ctx.need = _needs(ctx, 3)[1:]
+        if ctx.need[0]:
+            ctx.save_for_backward(cols)
         ctx.params = (weight, bias)
         return out
 
@@ -398,7 +463,9 @@ class PatchEmbedU8Fn(_Fn):
         cols = K.im2col_tubelets_u8(fr, tubelet, patch, mean, std, bgr, t_offset)   # row stride tad_patch_embed_ldk (zero-padded for /14)
         ntok = (T // tubelet) * (H // patch) * (W // patch)
         out = K.patch_embed_gemm(cols, K.pad_k(w_bf16(weight, _differentiated(ctx)), cols.shape[1]), _f32c(bias), _f32c(pos), ntok)
-        ctx.save_for_backward(cols)
+        ctx.need = _needs(ctx, 3)[1:]
+        if ctx.need[0]:
+            ctx.save_for_backward(cols)
         ctx.params = (weight, bias)
         return out
 
@@ -420,7 +487,9 @@ class PatchEmbedWindowsFn(_Fn):
         cols = K.im2col_frame_windows(store, idx, tubelet, patch, mean, std, bgr)   # row stride tad_patch_embed_ldk (zero-padded for /14)
         ntok = (T // tubelet) * (H // patch) * (W // patch)
         out = K.patch_embed_gemm(cols, K.pad_k(w_bf16(weight, _differentiated(ctx)), cols.shape[1]), _f32c(bias), _f32c(pos), ntok)
-        ctx.save_for_backward(cols)
+        ctx.need = _needs(ctx, 4)[2:]
+        if ctx.need[0]:
+            ctx.save_for_backward(cols)
         ctx.params = (weight, bias)
         return out
 
@@ -532,12 +601,14 @@ def _attn_fwd_core(xn, qkv_w, q_bias, v_bias, B, N, H, scale, train, drop=(0.0, 
 
 
 def _attn_bwd_core(d_ao, xn, qkv, ao, lse, qkv_w, has_qkv_bias, B, N, H, scale, dx_dtype, qv_params=None, ao_lo=None, drop=(0.0, 0),
-                   q_prescaled=None, pair=None, rowscale=None):
+                   q_prescaled=None, pair=None, rowscale=None, need=(True, True, True), pair_need=True):
     """returns dxn, dWqkv, dq_bias, dv_bias (None for what went into gradient sinks).  q_prescaled: the q contract of the forward
     that produced `qkv` (ctx.qpre).  pair = (dy, x, w) of ANOTHER bias-less weight gradient over the same rows with the same K that is due
     (the Block's proj: dy = the 16-bit gradient of its output, x = the attention output): a fifth value is returned then, that Linear's dW
     (None if it went into its gradient sink).  With sinks on all parameters the two weight gradients run as ONE launch
-    (K.linear_bwd_weight_pair: a 768 x 768 gradient alone fills the chip with 9 tiles x 28 reduction shares, the pair with 36 x 7)."""
+    (K.linear_bwd_weight_pair: a 768 x 768 gradient alone fills the chip with 9 tiles x 28 reduction shares, the pair with 36 x 7).
+    need = (qkv weight, q_bias, v_bias), pair_need: which of these gradients are wanted at all (frozen parameters: no launch, None;
+    ``xn`` may be None without the weight's).  The pair launch runs when both weights want theirs, the single launch when one does."""
     if q_prescaled is None:
         q_prescaled = _attn_q_prescale
     if qkv.dtype == torch.float32:  # generic head dim (see _attn_fwd_core)
@@ -549,15 +620,22 @@ def _attn_bwd_core(d_ao, xn, qkv, ao, lse, qkv_w, has_qkv_bias, B, N, H, scale, 
     dxn = K.linear_bwd_input(dqkv, wT_bf16(qkv_w, True), out_dtype=dx_dtype)
 
     def done(*r):  # (+ the pair's weight gradient by itself when it did not ride along)
-        return r if pair is None else r + (linear_dw(pair[0], pair[1], pair[2])[0],)
+        return r if pair is None else r + (linear_dw(pair[0], pair[1], pair[2], need=(pair_need, False))[0],)
 
-    if has_qkv_bias and qv_params is not None:
+    need_w, need_q, need_v = need[0], has_qkv_bias and need[1], has_qkv_bias and need[2]
+    if not need_w:
+        if not (need_q or need_v):
+            return done(dxn, None, None, None)
+        cs = K.colsum_bf16(dqkv)  # trainable biases beside a frozen weight: the column sums alone
+        AH = cs.numel() // 3
+        return done(dxn, None, cs[:AH].clone() if need_q else None, cs[2 * AH:].clone() if need_v else None)
+    if need_q and need_v and qv_params is not None:
         ents = [_sink(qkv_w), _sink(qv_params[0]), _sink(qv_params[1])]
         if all(e is not None for e in ents):
             # dW, dq_bias and dv_bias accumulate straight into the flat gradient buffer: no [3D] temporary, no slicing copies, no
             # autograd accumulation kernels
             prms = (qkv_w,) + tuple(qv_params)
-            sp = _sink(pair[2]) if pair is not None else None
+            sp = _sink(pair[2]) if pair is not None and pair_need else None
             paired = sp is not None and pair[0].dtype == dqkv.dtype and pair[1].shape == xn.shape and pair[0].shape[0] == dqkv.shape[0]
             if paired:
                 K.linear_bwd_weight_pair(dqkv, xn, ents[0][1].view(qkv_w.shape[0], -1), ents[1][1], ents[2][1], pair[0], pair[1],
@@ -571,10 +649,10 @@ def _attn_bwd_core(d_ao, xn, qkv, ao, lse, qkv_w, has_qkv_bias, B, N, H, scale, 
             if paired:
                 return dxn, None, None, None, None
             return done(dxn, None, None, None)
-    dWqkv, dbqkv = linear_dw(dqkv, xn, qkv_w, None, loose_bias=has_qkv_bias)
-    if has_qkv_bias:
+    dWqkv, dbqkv = linear_dw(dqkv, xn, qkv_w, None, loose_bias=need_q or need_v)
+    if dbqkv is not None:
         AH = dbqkv.numel() // 3
-        return done(dxn, dWqkv, dbqkv[:AH].clone(), dbqkv[2 * AH:].clone())
+        return done(dxn, dWqkv, dbqkv[:AH].clone() if need_q else None, dbqkv[2 * AH:].clone() if need_v else None)
     return done(dxn, dWqkv, None, None)
 
 
@@ -591,8 +669,9 @@ class AttentionFn(_Fn):
         qkv, ao, (lse, ao_lo) = _attn_fwd_core(xb, qkv_w, q_bias, v_bias, B, N, H, scale, train, ctx.drop)
         ctx.qpre = _attn_q_prescale  # (the contract `qkv` was written under: read back by the backward)
         y, _ = K.linear_fwd(ao, w_bf16(proj_w, train), _f32c(proj_b), out_dtype=torch.float32)
+        ctx.need = _needs(ctx, 6)
         if train:
-            ctx.save_for_backward(xb, qkv, ao, lse, qkv_w, proj_w, ao_lo)
+            ctx.save_for_backward(xb if ctx.need[1] else None, qkv, ao, lse, qkv_w, proj_w, ao_lo)
         ctx.meta = (B, N, H, scale, q_bias is not None, proj_b is not None)
         ctx.proj_b = proj_b
         ctx.qv = (q_bias, v_bias)
@@ -604,9 +683,9 @@ class AttentionFn(_Fn):
         B, N, H, scale, has_qb, has_pb = ctx.meta
         dyb = K.cast_bf16(_f32c(dy).reshape(B * N, -1))
         d_ao = K.linear_bwd_input(dyb, wT_bf16(proj_w, True))
-        dWp, dbp = linear_dw(dyb, ao, proj_w, ctx.proj_b)
+        dWp, dbp = linear_dw(dyb, ao, proj_w, ctx.proj_b, need=ctx.need[4:6])
         dx, dWqkv, dqb, dvb = _attn_bwd_core(d_ao, xb, qkv, ao, lse, qkv_w, has_qb, B, N, H, scale, torch.float32, ctx.qv, ao_lo=ao_lo,
-                                             drop=ctx.drop, q_prescaled=ctx.qpre)
+                                             drop=ctx.drop, q_prescaled=ctx.qpre, need=ctx.need[1:4])
         return dx.reshape(B, N, -1), dWqkv, dqb, dvb, dWp, dbp, None, None, None, None
 
 
@@ -621,8 +700,9 @@ class MlpFn(_Fn):
         xb = K.cast_bf16(_f32c(x).reshape(-1, shp[-1]))
         a, h = K.linear_fwd(xb, w_bf16(fc1_w, train), _f32c(fc1_b), out_dtype=None, epilogue=EPI_BIAS_GELU, want_preact=train)
         y, _ = K.linear_fwd(a, w_bf16(fc2_w, train), _f32c(fc2_b), out_dtype=torch.float32)
+        ctx.need = _needs(ctx, 5)
         if train:
-            ctx.save_for_backward(xb, h, a, fc1_w, fc2_w)
+            ctx.save_for_backward(xb if ctx.need[1] else None, h, a if ctx.need[3] else None, fc1_w, fc2_w)
         ctx.meta = (shp, fc1_b is not None, fc2_b is not None)
         ctx.biases = (fc1_b, fc2_b)
         return y.reshape(*shp[:-1], -1)
@@ -633,9 +713,9 @@ class MlpFn(_Fn):
         shp, has_b1, has_b2 = ctx.meta
         dyb = K.cast_bf16(_f32c(dy).reshape(-1, dy.shape[-1]))
         dh = K.linear_bwd_input(dyb, wT_bf16(fc2_w, True), gelu_preact=h)
-        dW2, db2 = linear_dw(dyb, a, fc2_w, ctx.biases[1])
+        dW2, db2 = linear_dw(dyb, a, fc2_w, ctx.biases[1], need=ctx.need[3:5])
         dx = K.linear_bwd_input(dh, wT_bf16(fc1_w, True), out_dtype=torch.float32)
-        dW1, db1 = linear_dw(dh, xb, fc1_w, ctx.biases[0])
+        dW1, db1 = linear_dw(dh, xb, fc1_w, ctx.biases[0], need=ctx.need[1:3])
         return dx.reshape(shp), dW1, db1, dW2, db2
 
 
@@ -724,7 +804,7 @@ class BlockFn(_Fn):
         if gb is None:
             gb = K.cast_bf16(g) if dp2 is None else K.scale_cast_bf16(g, None, dp2, N)
         dh = K.linear_bwd_input(gb, wT_bf16(fc2_w, True), gelu_preact=h)
-        dW2, db2 = linear_dw(gb, a, fc2_w, ctx.biases[2])
+        dW2, db2 = linear_dw(gb, a, fc2_w, ctx.biases[2], need=ctx.need[12:14])
         return _block_bwd_from_dh(ctx, st, g, dh, dW2, db2)
 
 
@@ -744,8 +824,11 @@ def _block_fwd_to_fc1(ctx, x, n1w, n1b, qkv_w, q_bias, v_bias, proj_w, proj_b, n
                          rowscale=_f32c(dp1), rows_per_scale=N)
     xn2, mean2, rstd2 = K.layernorm_fwd(x1, g2, b2, eps, save_stats=train)
     a, h = K.linear_fwd(xn2, w_bf16(fc1_w, train), _f32c(fc1_b), out_dtype=None, epilogue=EPI_BIAS_GELU, want_preact=train)
+    # inputs 0..13 = x and the thirteen parameters: a frozen Linear weight takes the one operand only ITS gradient reads out of the list
+    need = ctx.need = _needs(ctx, 14)
     if train:
-        ctx.save_for_backward(x0, g1, mean1, rstd1, xn1, qkv, ao, lse, x1, g2, mean2, rstd2, xn2, h, a, qkv_w, proj_w, fc1_w, fc2_w,
+        ctx.save_for_backward(x0, g1, mean1, rstd1, xn1 if need[3] else None, qkv, ao, lse, x1, g2, mean2, rstd2, xn2 if need[10] else None,
+                              h, a if need[12] else None, qkv_w, proj_w, fc1_w, fc2_w,
                               dp1 if dp1 is None else _f32c(dp1), dp2 if dp2 is None else _f32c(dp2), ao_lo)
     ctx.meta = (B, N, D, H, scale, q_bias is not None)
     ctx.biases = (proj_b, fc1_b, fc2_b)
@@ -764,17 +847,18 @@ def _block_bwd_from_dh(ctx, st, g, dh, dW2, db2):
     proj_b, fc1_b, fc2_b = ctx.biases
     B, N, D, H, scale, has_qb = ctx.meta
     dxn2 = K.linear_bwd_input(dh, wT_bf16(fc1_w, True))
-    dW1, db1 = linear_dw(dh, xn2, fc1_w, fc1_b)
+    need = ctx.need
+    dW1, db1 = linear_dw(dh, xn2, fc1_w, fc1_b, need=need[10:12])
     # LN2 backward also emits what the attention branch needs: bf16(drop-path scale * residual-stream grad) and its column
     # sums (= proj bias gradient), so neither a cast pass nor a bias reduction in the dW GEMM is needed
     n1w, n1b, n2w, n2b = ctx.norms
-    gmid, gpb, dg2, dbeta2, dbp = layernorm_bwd_sunk(dxn2, x1, g2, mean2, rstd2, n2w, n2b, colsum_param=proj_b, dres=g, want_bf16=True,
-                                                    rowscale=dp1, rows_per_scale=N)
+    gmid, gpb, dg2, dbeta2, dbp = layernorm_bwd_sunk(dxn2, x1, g2, mean2, rstd2, n2w, n2b, colsum_param=proj_b if need[7] else None, dres=g,
+                                                    want_bf16=True, rowscale=dp1, rows_per_scale=N)
     # ---- attention branch
     d_ao = K.linear_bwd_input(gpb, wT_bf16(proj_w, True))
     # (the proj weight gradient rides with the qkv one: one launch for both, _attn_bwd_core)
     dxn1, dWqkv, dqb, dvb, dWp = _attn_bwd_core(d_ao, xn1, qkv, ao, lse, qkv_w, has_qb, B, N, H, scale, None, ctx.qv, ao_lo=ao_lo, q_prescaled=ctx.qpre,
-                                                 pair=(gpb, ao, proj_w), rowscale=dp1)
+                                                 pair=(gpb, ao, proj_w), rowscale=dp1, need=need[3:6], pair_need=need[6])
     prev = ctx.prev_link
     if prev is not None:
         gin, ginb, dg1, dbeta1, _ = layernorm_bwd_sunk(dxn1, x0, g1, mean1, rstd1, n1w, n1b, dres=gmid, want_bf16=True, rowscale=prev.dp2,
@@ -832,11 +916,22 @@ def _branch_wT(w, gamma):
     return wT_bf16(w, True) if gamma is None else K.rowscale_transpose_cast(_w2d(w), gamma)
 
 
-def _branch_dw(gb, a, w, b, gamma_p, gamma):
+def _branch_dw(gb, a, w, b, gamma_p, gamma, need=(True, True, True)):
     """(dW, db, dgamma) of a branch's Linear and layer-scale from gb (16-bit, scaled and masked, without gamma) and the Linear's input a;
-    None for what went into gradient sinks"""
+    None for what went into gradient sinks.  need = (weight, bias, gamma): with none of the three wanted nothing is launched (``a`` may
+    be None without the weight's and gamma's); a frozen one beside a trainable one is computed with it and dropped, except that a bias
+    alone is gamma times the column sums."""
     if gamma_p is None:
-        return linear_dw(gb, a, w, b) + (None,)
+        return linear_dw(gb, a, w, b, need=need[:2]) + (None,)
+    need_b = need[1] and b is not None
+    if not (need[0] or need[2]):
+        return None, (gamma * K.colsum_bf16(gb) if need_b else None), None
+    if not (need[0] and need[2] and (need_b or b is None)):
+        # mixed flags inside one layer-scaled branch: T = gb^T a serves dW and dgamma alike, so the launches are those of the
+        # all-trainable case (a frozen member has no gradient sink, hence the tensors come back and autograd keeps the wanted ones)
+        T, cs = K.linear_bwd_weight(gb, a, want_bias=b is not None)
+        dW, db, dg = K.layerscale_grads(T, _w2d(w), _f32c(b), cs, gamma)
+        return (dW.reshape(w.shape) if need[0] else None), (db if need_b else None), (dg if need[2] else None)
     T, cs = K.linear_bwd_weight(gb, a, want_bias=b is not None)
     prms = (w, gamma_p) + ((b,) if b is not None else ())
     ents = [_sink(q) for q in prms]
@@ -874,9 +969,12 @@ class BlockVariantFn(_Fn):
         xn2, mean2, rstd2 = K.layernorm_fwd(x1, g2, b2, eps, save_stats=train)
         a, h = K.linear_fwd(xn2, w_bf16(fc1_w, train), _f32c(fc1_b), out_dtype=None, epilogue=EPI_BIAS_GELU, want_preact=train)
         x2 = _branch_fwd(a, fc2_w, fc2_b, x1, gm2, s2, N, train, p, int(seed_mlp))
+        # inputs 0..15 = x, the thirteen parameters of BlockFn, gamma_1, gamma_2; `a` also serves dgamma_2 (see _branch_dw)
+        need = ctx.need = _needs(ctx, 16)
         if train:
-            ctx.save_for_backward(x0, g1, mean1, rstd1, xn1, qkv, ao, lse, x1, g2, mean2, rstd2, xn2, h, a, qkv_w, proj_w, fc1_w, fc2_w,
-                                  s1, s2, ao_lo, gm1, gm2)
+            ctx.save_for_backward(x0, g1, mean1, rstd1, xn1 if need[3] else None, qkv, ao, lse, x1, g2, mean2, rstd2,
+                                  xn2 if need[10] else None, h, a if need[12] or (gamma_2 is not None and need[15]) else None,
+                                  qkv_w, proj_w, fc1_w, fc2_w, s1, s2, ao_lo, gm1, gm2)
         ctx.meta = (B, N, D, H, scale, q_bias is not None, p, int(seed_attn), int(seed_mlp))
         ctx.biases = (proj_b, fc1_b, fc2_b)
         ctx.norms = (n1w, n1b, n2w, n2b)
@@ -893,15 +991,16 @@ class BlockVariantFn(_Fn):
         n1w, n1b, n2w, n2b = ctx.norms
         gamma_1, gamma_2 = ctx.gammas
         g = _f32c(g).reshape(B * N, D)
+        need = ctx.need
         # ---- MLP branch
         if p > 0.0:
             gb = K.branch_dropout_cast(g, dp2, N, p, seed_mlp)
         else:
             gb = K.cast_bf16(g) if dp2 is None else K.scale_cast_bf16(g, None, dp2, N)
         dh = K.linear_bwd_input(gb, _branch_wT(fc2_w, gm2), gelu_preact=h)
-        dW2, db2, dgm2 = _branch_dw(gb, a, fc2_w, fc2_b, gamma_2, gm2)
+        dW2, db2, dgm2 = _branch_dw(gb, a, fc2_w, fc2_b, gamma_2, gm2, need=(need[12], need[13], need[15]))
         dxn2 = K.linear_bwd_input(dh, wT_bf16(fc1_w, True))
-        dW1, db1 = linear_dw(dh, xn2, fc1_w, fc1_b)
+        dW1, db1 = linear_dw(dh, xn2, fc1_w, fc1_b, need=need[10:12])
         # LN2 backward emits op16(dp1 * residual-stream gradient) on the side; under dropout the masked copy needs a pass of its own
         gmid, gpb, dg2, dbeta2, _ = layernorm_bwd_sunk(dxn2, x1, g2, mean2, rstd2, n2w, n2b, dres=g, want_bf16=p == 0.0, rowscale=dp1,
                                                      rows_per_scale=N)
@@ -909,9 +1008,9 @@ class BlockVariantFn(_Fn):
             gpb = K.branch_dropout_cast(gmid, dp1, N, p, seed_attn)
         # ---- attention branch
         d_ao = K.linear_bwd_input(gpb, _branch_wT(proj_w, gm1))
-        dWp, dbp, dgm1 = _branch_dw(gpb, ao, proj_w, proj_b, gamma_1, gm1)
+        dWp, dbp, dgm1 = _branch_dw(gpb, ao, proj_w, proj_b, gamma_1, gm1, need=(need[6], need[7], need[14]))
         dxn1, dWqkv, dqb, dvb = _attn_bwd_core(d_ao, xn1, qkv, ao, lse, qkv_w, has_qb, B, N, H, scale, None, ctx.qv, ao_lo=ao_lo,
-                                               q_prescaled=ctx.qpre, rowscale=dp1)
+                                               q_prescaled=ctx.qpre, rowscale=dp1, need=need[3:6])
         gin, _, dg1, dbeta1, _ = layernorm_bwd_sunk(dxn1, x0, g1, mean1, rstd1, n1w, n1b, dres=gmid)
         return (gin.reshape(B, N, D), dg1, dbeta1, dWqkv, dqb, dvb, dWp, dbp, dg2, dbeta2, dW1, db1, dW2, db2, dgm1, dgm2, None, None,
                 None, None, None, None, None, None)
@@ -972,7 +1071,7 @@ class BlockPoolFn(_Fn):
         B, N, D = x.shape
         S = K.colsum_segments(a, B, N)
         xbar = K.meanpool_fwd(x1.view(B, N, D))
-        ctx.pool_S = S if train else None
+        ctx.pool_S = S if train and ctx.need[12] else None
         # xbar + dp2 ((S / N) W2^T + b2) on the VALUES of the 16-bit operand copy of W2: the pooled operand is never rounded to 16 bits
         return K.pooled_linear(S, w_bf16(fc2_w, train), _f32c(fc2_b), _f32c(dp2), xbar, N)
 
@@ -991,6 +1090,11 @@ class BlockPoolFn(_Fn):
         t = K.linear_bwd_input(gb, wT_bf16(fc2_w, True), out_dtype=torch.float32)
         dh = K.gelu_grad_bcast(t, h, N)
         # dW2 = gb^T S, db2 = N sum_b gb[b]: f32 products of the 16-bit gb values and the f32 sums, into the gradient sinks as linear_dw does
+        need_w, need_b = ctx.need[12], ctx.need[13] and fc2_b is not None
+        if not need_w:  # a frozen fc2: S was not kept; a trainable bias beside it still gets its N sum_b gb[b]
+            return _block_bwd_from_dh(ctx, st, g.view(B * N, D), dh, None, gb.float().sum(0) * float(N) if need_b else None)
+        if not need_b:
+            fc2_b = None
         gbf = gb.float()
         sw = _sink(fc2_w)
         sb = _sink(fc2_b) if fc2_b is not None else None
@@ -1029,8 +1133,9 @@ class LinearFn(_Fn):
             return y.reshape(*shp[:-1], -1)
         xb = K.cast_bf16(_f32c(x).reshape(-1, shp[-1]))
         y, _ = K.linear_fwd(xb, w_bf16(weight, train), _f32c(bias), out_dtype=torch.float32)
+        ctx.need = _needs(ctx, 3)
         if train:
-            ctx.save_for_backward(xb)
+            ctx.save_for_backward(xb if ctx.need[1] else None)
         return y.reshape(*shp[:-1], -1)
 
     @staticmethod
@@ -1044,7 +1149,7 @@ class LinearFn(_Fn):
             return (None if dx is None else dx.reshape(ctx.shp)), dW, db
         dyb = K.cast_bf16(_f32c(dy).reshape(-1, dy.shape[-1]))
         dx = K.linear_bwd_input(dyb, wT_bf16(weight, True), out_dtype=torch.float32) if ctx.needs_input_grad[0] else None
-        dW, db = linear_dw(dyb, xb, weight, bias)
+        dW, db = linear_dw(dyb, xb, weight, bias, need=ctx.need[1:3])
         return (None if dx is None else dx.reshape(ctx.shp)), dW, db
 
 

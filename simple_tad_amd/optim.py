@@ -151,7 +151,7 @@ class FusedAdamW(torch.optim.Optimizer):
         for p in updated:
             self.state[p]["step"] += 1
         self._last_updated = updated
-        ops.invalidate_weight_cache()
+        ops.invalidate_weight_cache(keep_static=True)  # (frozen weights are not in this optimizer: their copies stay)
         if self.mirror is not None:
             if self.mirror_t is not None:
                 K.transpose_bf16_batched(self.mirror, self.mirror_t, self._t_table)
