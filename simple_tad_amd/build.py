@@ -29,7 +29,8 @@ NO_VGPR_FORM = {"gemm_w4.hip"}
 # so are im2col.hip (the output format is a template argument there: it defines tad_im2col_tubelets / _u8 and their _f16 twins itself)
 # and attn_colsum.hip (the operand format is a template argument; one entry point takes it at run time)
 EXTRA_DEPS = {"gemm.hip": ["gemm_kernels.h", "gemm_plan.h"], "gemm_w4.hip": ["gemm_kernels.h", "gemm_plan.h"], "gemm_plan.hip": ["gemm_plan.h", "knob.h"],
-              "attn_fwd.hip": ["attn_plan.h"], "attn_bwd.hip": ["attn_plan.h"], "attn_plan.hip": ["attn_plan.h", "knob.h"]}
+              "attn_fwd.hip": ["attn_plan.h"], "attn_bwd.hip": ["attn_plan.h"], "attn_plan.hip": ["attn_plan.h", "knob.h"],
+              "multiscale_crop.hip": ["frame_io.h"], "frame_resize.hip": ["frame_io.h"], "spatial_sample.hip": ["frame_io.h"], "randaug.hip": ["frame_io.h"]}
 # ema.hip and mixup.hip must round like torch (a product, a product, a sum: three roundings) and are compiled without FMA contraction;
 # randaug.hip must round like PIL's C code (a float blend, a double affine map and cubic: each product and sum on its own).
 # multiscale_crop.hip writes the same normalised f32 values as randaug.hip's frames_to_clip and takes the same flags.

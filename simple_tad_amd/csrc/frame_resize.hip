@@ -20,40 +20,29 @@
 // towards black: rint((float)p * alpha), the product on its own -- cv2.addWeighted(reflect, a, black, 1 - a, 0) in float; the file is
 // compiled without floating-point contraction (build.py).  The fused f32 value is frames_to_clip's: normalize_u8 (common.h).
 //
-// Shape: a workgroup of 256 threads owns FR_TR x FR_TC outputs of one frame.  It stages the tile's taps and coefficients in LDS, runs
-// the horizontal pass over the virtual rows the tile's vertical taps name into int32 LDS planes (one per row and channel), then the
+// Shape: a workgroup of 256 threads owns FRAME_TR x FRAME_TC outputs of one frame (frame_io.h).  It stages the tile's taps and
+// coefficients in LDS, runs the horizontal pass over the virtual rows the tile's vertical taps name into int32 LDS planes (one per row and channel), then the
 // vertical pass out of LDS.  The rows are held densely (slot = row - lowest row) when the taps of the tile span at most 4 rows per
 // output row -- upscales and shrinks up to 4 -- and as four slots per output row otherwise, so only rows under taps are ever read.
 // The four pixels under an output's horizontal taps are 12 contiguous bytes at no particular alignment (W * 3 breaks every one): they come
 // in as aligned words and a funnel shift (fr_load12); where a tap clamps at a border, byte by byte.  A thread's outputs in the vertical
-// pass are four neighbouring columns.
-#include "common.h"
-#include <math.h>
+// pass are four neighbouring columns, written by the clip and frame writers of frame_io.h, which describes the output path.
+#include "frame_io.h"
 #include <string.h>
 #include <type_traits>
 
 TAD_NAMESPACE_BEGIN
 
-constexpr int FR_THREADS = 256;
-constexpr int FR_TR = 32, FR_TC = 32;                    // output rows x columns of a tile: FR_TR * FR_TC / 4 = FR_THREADS
-constexpr int FR_CG = FR_TC / 4;                         // column groups of four per tile row
-constexpr int FR_SLOTS = 4 * FR_TR;                      // virtual rows a tile can need: four taps per output row
-static_assert(FR_TR * FR_CG == FR_THREADS, "tile shape");
-static_assert(FR_SLOTS * 3 * FR_TC * 4 + (FR_TC + FR_TR) * 5 * 4 <= 64 * 1024, "static LDS stays at or below 64 KB");
-
-struct FrNorm {
-  float mean[3], sd[3];
-};
+constexpr int FR_SLOTS = 4 * FRAME_TR;  // virtual rows a tile can need: four taps per output row
+static_assert(FR_SLOTS * 3 * FRAME_TC * 4 + (FRAME_TC + FRAME_TR) * 5 * 4 <= 64 * 1024, "static LDS stays at or below 64 KB");
 
 __host__ __device__ __forceinline__ int64_t fr_set_words(int out) { return TAD_FR_SET_HEAD + (int64_t)out * 5; }
 __host__ __device__ __forceinline__ int64_t fr_table_words(int B, int nv, int Sh, int Sw) {
   return (int64_t)B * TAD_FR_ROW_WORDS + fr_set_words(Sw) + nv * fr_set_words(Sh);
 }
-__device__ __forceinline__ int fr_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ uint32_t fr_clip8(int ss) { return (uint32_t)fr_clamp(ss >> 22, 0, 255); }
 
 // a reflected band byte faded towards black: rint((float)p * alpha), the product on its own, cut to a byte
-__device__ __forceinline__ int fr_fade(int b, float alpha) { return fr_clamp(__float2int_rn(__fmul_rn((float)b, alpha)), 0, 255); }
+__device__ __forceinline__ int fr_fade(int b, float alpha) { return frame_clamp(__float2int_rn(__fmul_rn((float)b, alpha)), 0, 255); }
 
 // the 12 bytes from p (any alignment) as three words: aligned 4-byte loads and a funnel shift.  Only the aligned words that hold one of
 // the 12 bytes are loaded -- three when p is aligned, else four -- so no load leaves the pages of the bytes asked for; the up to three
@@ -71,7 +60,7 @@ __device__ __forceinline__ void fr_load12(const uint8_t* p, uint32_t w[3]) {
 __device__ __forceinline__ void fr_stage(const int32_t* __restrict__ set, int out_size, int o0, int n, int* first, int (*kk)[4], int slots) {
   const int32_t* f = set + TAD_FR_SET_HEAD;
   const int32_t* k = f + out_size;
-  for (int i = threadIdx.x; i < slots * 5; i += FR_THREADS) {
+  for (int i = threadIdx.x; i < slots * 5; i += FRAME_THREADS) {
     const int o = i / 5, j = i - o * 5;
     if (j == 4)
       first[o] = o < n ? f[o0 + o] : 0;
@@ -81,34 +70,34 @@ __device__ __forceinline__ void fr_stage(const int32_t* __restrict__ set, int ou
 }
 
 template <bool F32>
-__global__ __launch_bounds__(FR_THREADS) void frame_resize_kernel(const uint8_t* __restrict__ x, void* __restrict__ out,
-                                                                 const int32_t* __restrict__ tab, FrNorm nm, int B, int T, int H, int W, int Sh,
+__global__ __launch_bounds__(FRAME_THREADS) void frame_resize_kernel(const uint8_t* __restrict__ x, void* __restrict__ out,
+                                                                 const int32_t* __restrict__ tab, ClipNorm nm, int B, int T, int H, int W, int Sh,
                                                                  int Sw, int nv, int tiles_x) {
-  __shared__ __attribute__((aligned(16))) int hp[FR_SLOTS][3][FR_TC];  // (read back four columns at a time)
-  __shared__ int hf[FR_TC], hk[FR_TC][4], vf[FR_TR], vk[FR_TR][4];
+  __shared__ __attribute__((aligned(16))) int hp[FR_SLOTS][3][FRAME_TC];  // (read back four columns at a time)
+  __shared__ int hf[FRAME_TC], hk[FRAME_TC][4], vf[FRAME_TR], vk[FRAME_TR][4];
   const int32_t* r = tab + (int64_t)blockIdx.z * TAD_FR_ROW_WORDS;
   const int sample = r[0];
   if (sample < 0 || sample >= B) return;  // (the same for every thread of the workgroup)
   const int t = blockIdx.y, tid = threadIdx.x;
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
   // mode and pads cut to what the frame allows, the set index to the sets: a malformed table is never an address
-  const int mode = fr_clamp(r[1], TAD_FR_NONE, TAD_FR_REPLICATE);
-  const int pt = mode == TAD_FR_NONE ? 0 : fr_clamp(r[2], 0, H), pb = mode == TAD_FR_NONE ? 0 : fr_clamp(r[3], 0, H);
+  const int mode = frame_clamp(r[1], TAD_FR_NONE, TAD_FR_REPLICATE);
+  const int pt = mode == TAD_FR_NONE ? 0 : frame_clamp(r[2], 0, H), pb = mode == TAD_FR_NONE ? 0 : frame_clamp(r[3], 0, H);
   const float alpha = __int_as_float(r[4]);
   const uint32_t colour = (uint32_t)r[5];
   const int Hv = pt + H + pb;
   const int32_t* hset = tab + (int64_t)B * TAD_FR_ROW_WORDS;
-  const int32_t* vset = hset + fr_set_words(Sw) + fr_clamp(r[6], 0, nv - 1) * fr_set_words(Sh);
-  const int c0 = tx * FR_TC, o0 = ty * FR_TR;
-  const int nc = Sw - c0 < FR_TC ? Sw - c0 : FR_TC, nr = Sh - o0 < FR_TR ? Sh - o0 : FR_TR;
-  fr_stage(hset, Sw, c0, nc, hf, hk, FR_TC);
-  fr_stage(vset, Sh, o0, nr, vf, vk, FR_TR);
+  const int32_t* vset = hset + fr_set_words(Sw) + frame_clamp(r[6], 0, nv - 1) * fr_set_words(Sh);
+  const int c0 = tx * FRAME_TC, o0 = ty * FRAME_TR;
+  const int nc = Sw - c0 < FRAME_TC ? Sw - c0 : FRAME_TC, nr = Sh - o0 < FRAME_TR ? Sh - o0 : FRAME_TR;
+  fr_stage(hset, Sw, c0, nc, hf, hk, FRAME_TC);
+  fr_stage(vset, Sh, o0, nr, vf, vk, FRAME_TR);
   __syncthreads();
 
   // the virtual rows under the tile's vertical taps: [lo, hi], held densely when that is no more rows than four per output row
   int lo = Hv - 1, hi = 0;
   for (int i = 0; i < nr; ++i) {
-    const int a = fr_clamp(vf[i], 0, Hv - 1), b = fr_clamp(vf[i] + 3, 0, Hv - 1);
+    const int a = frame_clamp(vf[i], 0, Hv - 1), b = frame_clamp(vf[i] + 3, 0, Hv - 1);
     lo = a < lo ? a : lo, hi = b > hi ? b : hi;
   }
   const bool dense = hi - lo + 1 <= 4 * nr;
@@ -119,10 +108,10 @@ __global__ __launch_bounds__(FR_THREADS) void frame_resize_kernel(const uint8_t*
   const uint8_t* frame = x + ((int64_t)sample * T + t) * H * W * 3;
   auto hpass = [&](auto reflect) {
     constexpr bool REFLECT = decltype(reflect)::value;
-    const int c = tid & (FR_TC - 1);
+    const int c = tid & (FRAME_TC - 1);
     if (c >= nc) return;
-    for (int slot = tid / FR_TC; slot < nslots; slot += FR_THREADS / FR_TC) {
-      const int v = dense ? lo + slot : fr_clamp(vf[slot >> 2] + (slot & 3), 0, Hv - 1);
+    for (int slot = tid / FRAME_TC; slot < nslots; slot += FRAME_THREADS / FRAME_TC) {
+      const int v = dense ? lo + slot : frame_clamp(vf[slot >> 2] + (slot & 3), 0, Hv - 1);
       // the row map: inside the frame the row itself; in a band its mirror image (faded), the edge row, or the colour
       int fr = v - pt;
       bool band = false;
@@ -133,7 +122,7 @@ __global__ __launch_bounds__(FR_THREADS) void frame_resize_kernel(const uint8_t*
         band = true;
         fr = REFLECT ? H - 1 - (v - pt - H) : H - 1;
       }
-      fr = fr_clamp(fr, 0, H - 1);
+      fr = frame_clamp(fr, 0, H - 1);
       const bool constant = band && mode == TAD_FR_CONST, fade = REFLECT && band;
       const uint8_t* row = frame + (int64_t)fr * W * 3;
       int acc[3] = {0, 0, 0};
@@ -155,7 +144,7 @@ __global__ __launch_bounds__(FR_THREADS) void frame_resize_kernel(const uint8_t*
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int k = hk[c][j];
-          const uint8_t* p = row + (int64_t)fr_clamp(f0 + j, 0, W - 1) * 3;
+          const uint8_t* p = row + (int64_t)frame_clamp(f0 + j, 0, W - 1) * 3;
 #pragma unroll
           for (int ch = 0; ch < 3; ++ch) {
             int b = constant ? (int)((colour >> (8 * ch)) & 255u) : (int)p[ch];
@@ -175,7 +164,7 @@ __global__ __launch_bounds__(FR_THREADS) void frame_resize_kernel(const uint8_t*
   __syncthreads();
 
   // vertical pass: a thread owns four columns of one output row, all three channels
-  const int orow = tid / FR_CG, cg = tid - orow * FR_CG;
+  const int orow = tid / FRAME_CG, cg = tid - orow * FRAME_CG;
   const int col = c0 + cg * 4, valid = Sw - col < 4 ? Sw - col : 4;
   if (orow >= nr || valid <= 0) return;
   int acc[3][4];
@@ -185,8 +174,8 @@ __global__ __launch_bounds__(FR_THREADS) void frame_resize_kernel(const uint8_t*
     for (int q = 0; q < 4; ++q) acc[ch][q] = 1 << 21;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int v = fr_clamp(vf[orow] + j, 0, Hv - 1);
-    const int slot = fr_clamp(dense ? v - lo : orow * 4 + j, 0, FR_SLOTS - 1);
+    const int v = frame_clamp(vf[orow] + j, 0, Hv - 1);
+    const int slot = frame_clamp(dense ? v - lo : orow * 4 + j, 0, FR_SLOTS - 1);
     const int k = vk[orow][j];
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
@@ -198,35 +187,14 @@ __global__ __launch_bounds__(FR_THREADS) void frame_resize_kernel(const uint8_t*
   if (F32) {
     float* o = static_cast<float*>(out) + (((int64_t)sample * 3 * T + t) * Sh + oy) * Sw + col;  // channel ch: + ch * T * Sh * Sw
     const int64_t plane = (int64_t)T * Sh * Sw;
+    float v[3][4];
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      float v[4];
+    for (int ch = 0; ch < 3; ++ch)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) v[q] = normalize_u8((float)fr_clip8(acc[ch][q]), nm.mean[ch], nm.sd[ch]);
-      float* oc = o + ch * plane;
-      if (valid == 4 && (reinterpret_cast<uintptr_t>(oc) & 15) == 0) {
-        *reinterpret_cast<float4*>(oc) = make_float4(v[0], v[1], v[2], v[3]);
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          if (q < valid) oc[q] = v[q];
-      }
-    }
+      for (int q = 0; q < 4; ++q) v[ch][q] = frame_norm8(acc[ch][q], nm.mean[ch], nm.sd[ch]);
+    store_clip_f32x4(o, plane, v, valid);
   } else {
-    uint8_t* o = static_cast<uint8_t*>(out) + ((((int64_t)sample * T + t) * Sh + oy) * Sw + col) * 3;
-    uint32_t pk[3] = {0, 0, 0};
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) pk[(3 * q + ch) >> 2] |= fr_clip8(acc[ch][q]) << (((3 * q + ch) & 3) * 8);
-    if (valid == 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i) reinterpret_cast<uint32_t*>(o)[i] = pk[i];
-    } else {
-#pragma unroll
-      for (int i = 0; i < 12; ++i)
-        if (i < 3 * valid) o[i] = (uint8_t)(pk[i >> 2] >> ((i & 3) * 8));
-    }
+    store_frames_u8x4(static_cast<uint8_t*>(out) + ((((int64_t)sample * T + t) * Sh + oy) * Sw + col) * 3, acc, valid);
   }
 }
 
@@ -237,7 +205,7 @@ using namespace tad;
 static int fr_shape_ok(int B, int nv, int H, int W, int Sh, int Sw, const char* who) {
   TAD_REQUIRE(B > 0 && B <= 65535, "%s: B=%d must be in [1, 65535]", who, B);
   TAD_REQUIRE(nv > 0 && nv <= TAD_FR_MAX_SETS, "%s: n_vsets=%d must be in [1, %d]", who, nv, TAD_FR_MAX_SETS);
-  TAD_REQUIRE(H > 0 && W > 0 && (int64_t)H * W <= ((int64_t)1 << 28), "%s: H=%d W=%d: a frame must have 1 .. 2^28 pixels", who, H, W);
+  if (int rc = frame_extent_ok(who, H, W)) return rc;
   TAD_REQUIRE(Sh > 0 && Sw > 0 && Sh <= 16384 && Sw <= 16384, "%s: S_h=%d S_w=%d must be in [1, 16384]", who, Sh, Sw);
   return TAD_OK;
 }
@@ -280,13 +248,12 @@ extern "C" int tad_frame_resize_plan_check(const int32_t* table_host, int64_t n_
                 "frame_resize_plan_check: vertical set %d: virtual height %d is not the %d rows of the source plus two pads of at most %d", i, set[0], H, H);
     if (int rc = fr_check_set(set, S_h, "vertical", i)) return rc;
   }
-  uint64_t seen[1024] = {0};  // (B <= 65535)
+  SeenSamples seen;  // (B <= 65535)
   for (int k = 0; k < B; ++k) {
     const int32_t* r = table_host + (int64_t)k * TAD_FR_ROW_WORDS;
     const int sample = r[0], mode = r[1], pt = r[2], pb = r[3], vs = r[6];
     TAD_REQUIRE(0 <= sample && sample < B, "frame_resize_plan_check: row %d: sample=%d outside the batch B=%d", k, sample, B);
-    TAD_REQUIRE(!(seen[sample >> 6] >> (sample & 63) & 1), "frame_resize_plan_check: row %d: sample=%d has two rows", k, sample);
-    seen[sample >> 6] |= (uint64_t)1 << (sample & 63);
+    TAD_REQUIRE(!seen.twice(sample), "frame_resize_plan_check: row %d: sample=%d has two rows", k, sample);
     TAD_REQUIRE(mode >= TAD_FR_NONE && mode <= TAD_FR_REPLICATE, "frame_resize_plan_check: row %d: unknown mode %d", k, mode);
     TAD_REQUIRE(pt >= 0 && pb >= 0, "frame_resize_plan_check: row %d: negative pad (%d, %d)", k, pt, pb);
     TAD_REQUIRE(pt <= H && pb <= H, "frame_resize_plan_check: row %d: pad (%d, %d) is greater than H=%d (a second reflection is not built)", k, pt, pb, H);
@@ -309,25 +276,20 @@ extern "C" int tad_frame_resize(const uint8_t* x, void* out, int out_f32, const 
   TAD_REQUIRE(x && out && workspace, "frame_resize: null pointer");
   if (int rc = fr_shape_ok(B, n_vsets, H, W, S_h, S_w, "frame_resize")) return rc;
   TAD_REQUIRE(T > 0 && T <= 65535, "frame_resize: T=%d must be in [1, 65535]", T);
-  TAD_REQUIRE_ALIGNED("frame_resize", workspace, 4);
-  TAD_REQUIRE(workspace_bytes >= tad_frame_resize_workspace_bytes(B, n_vsets, S_h, S_w), "frame_resize: workspace of %zu bytes, need %zu",
-              workspace_bytes, tad_frame_resize_workspace_bytes(B, n_vsets, S_h, S_w));
-  FrNorm nm = {{0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}};
+  if (int rc = table_workspace_ok("frame_resize", workspace, workspace_bytes, tad_frame_resize_workspace_bytes(B, n_vsets, S_h, S_w))) return rc;
+  ClipNorm nm = CLIP_NORM_IDENTITY;
   if (out_f32) {
     TAD_REQUIRE(mean && std_, "frame_resize: the f32 output needs mean and std");
     TAD_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "frame_resize: an f32 out must be 4-byte aligned");
-    for (int c = 0; c < 3; ++c) {
-      TAD_REQUIRE(std::isfinite(mean[c]) && std::isfinite(std_[c]) && std_[c] != 0.0f, "frame_resize: mean / std of channel %d", c);
-      nm.mean[c] = mean[c], nm.sd[c] = std_[c];
-    }
+    if (int rc = clip_norm_from("frame_resize", mean, std_, &nm)) return rc;
   }
-  const int tiles_x = (S_w + FR_TC - 1) / FR_TC, tiles_y = (S_h + FR_TR - 1) / FR_TR;
-  const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)T, (unsigned)B);
+  int tiles_x;
+  const dim3 grid(frame_tile_grid(S_h, S_w, &tiles_x), (unsigned)T, (unsigned)B);
   const int32_t* tab = static_cast<const int32_t*>(workspace);
   hipStream_t s = (hipStream_t)stream;
   if (out_f32)
-    hipLaunchKernelGGL(frame_resize_kernel<true>, grid, dim3(FR_THREADS), 0, s, x, out, tab, nm, B, T, H, W, S_h, S_w, n_vsets, tiles_x);
+    hipLaunchKernelGGL(frame_resize_kernel<true>, grid, dim3(FRAME_THREADS), 0, s, x, out, tab, nm, B, T, H, W, S_h, S_w, n_vsets, tiles_x);
   else
-    hipLaunchKernelGGL(frame_resize_kernel<false>, grid, dim3(FR_THREADS), 0, s, x, out, tab, nm, B, T, H, W, S_h, S_w, n_vsets, tiles_x);
+    hipLaunchKernelGGL(frame_resize_kernel<false>, grid, dim3(FRAME_THREADS), 0, s, x, out, tab, nm, B, T, H, W, S_h, S_w, n_vsets, tiles_x);
   return check_launch("frame_resize");
 }

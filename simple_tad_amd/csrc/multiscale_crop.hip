@@ -13,81 +13,68 @@
 // value is frames_to_clip's: normalize_u8 (common.h) of the byte, IEEE division and subtraction; the file is compiled without
 // floating-point contraction (build.py) as randaug.hip is.
 //
-// Shape: a workgroup owns MC_TR x MC_TC outputs of one frame.  It resamples, horizontally, the input rows its vertical taps span into
-// LDS (one byte plane per channel, four columns to a word), then runs the vertical pass out of LDS; the row halo is recomputed per
-// tile.  Source bytes are loaded one by one (Ws * 3 and the crop offset break every alignment); the outputs of a thread are four
-// neighbouring columns: one 16-byte store per channel on the aligned f32 planes, three 4-byte stores of uint8 pixels.
-#include "common.h"
-#include <math.h>
+// Shape: a workgroup owns FRAME_TR x FRAME_TC outputs of one frame (frame_io.h).  It resamples, horizontally, the input rows its
+// vertical taps span into LDS (one byte plane per channel, four columns to a word), then runs the vertical pass out of LDS; the row
+// halo is recomputed per tile.  Source bytes are loaded one by one (Ws * 3 and the crop offset break every alignment); the outputs of
+// a thread are four neighbouring columns, written by the clip and frame writers of frame_io.h, which describes the output path.
+#include "frame_io.h"
 
 TAD_NAMESPACE_BEGIN
 
-constexpr int MC_THREADS = 256;
-constexpr int MC_TR = 32, MC_TC = 32;                    // output rows x columns of a tile: MC_TR * MC_TC / 4 = MC_THREADS
 constexpr int MC_K = TAD_MSC_MAX_KSIZE;
-constexpr int MC_CG = MC_TC / 4;                         // column groups (words) per LDS row
-// input rows under the vertical taps of a tile: the centres of MC_TR rows lie (MC_TR - 1) * scale apart, the taps reach `support` to
-// either side, scale = support <= 8: (MC_TR - 1) * 8 + 2 * 8 + 1 = 265
+// input rows under the vertical taps of a tile: the centres of FRAME_TR rows lie (FRAME_TR - 1) * scale apart, the taps reach `support`
+// to either side, scale = support <= 8: (FRAME_TR - 1) * 8 + 2 * 8 + 1 = 265.  An LDS row holds FRAME_CG words: four columns each
 constexpr int MC_ROWS = 272;
-static_assert(MC_TR * MC_CG == MC_THREADS && (MC_TR - 1) * 8 + MC_K <= MC_ROWS, "tile shape");
-
-struct McNorm {
-  float mean[3], sd[3];
-};
+static_assert((FRAME_TR - 1) * 8 + MC_K <= MC_ROWS, "tile shape");
 
 __host__ __device__ __forceinline__ int64_t mc_slot_words(int out) { return TAD_MSC_SET_HEAD + (int64_t)out * (2 + MC_K); }
 __host__ __device__ __forceinline__ int64_t mc_table_words(int B, int nh, int nv, int Sh, int Sw) {
   return (int64_t)B * TAD_MSC_ROW_WORDS + nh * mc_slot_words(Sw) + nv * mc_slot_words(Sh);
-}
-__device__ __forceinline__ int mc_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ uint32_t mc_clip8(int ss) {
-  const int v = ss >> 22;
-  return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
 // the coefficients of `n` outputs from output `o0` of a set, staged in LDS with the bounds cut to the crop extent `extent` (a
 // malformed table is never an address: xmin in [0, extent), count in [0, min(ksize, extent - xmin)])
 __device__ __forceinline__ void mc_stage(const int32_t* __restrict__ set, int out_size, int extent, int o0, int n, int (*kk)[MC_K],
                                          int (*bounds)[2], int slots) {
-  const int ksize = mc_clamp(set[2], 1, MC_K);
+  const int ksize = frame_clamp(set[2], 1, MC_K);
   const int32_t* b = set + TAD_MSC_SET_HEAD;
   const int32_t* k = b + 2 * (int64_t)out_size;
-  for (int i = threadIdx.x; i < slots * MC_K; i += MC_THREADS) {
+  for (int i = threadIdx.x; i < slots * MC_K; i += FRAME_THREADS) {
     const int o = i / MC_K, j = i - o * MC_K;
     kk[o][j] = (o < n && j < ksize) ? k[(int64_t)(o0 + o) * ksize + j] : 0;
   }
-  for (int o = threadIdx.x; o < slots; o += MC_THREADS) {
+  for (int o = threadIdx.x; o < slots; o += FRAME_THREADS) {
     int xmin = 0, count = 0;
     if (o < n) {
-      xmin = mc_clamp(b[2 * (o0 + o)], 0, extent - 1);
+      xmin = frame_clamp(b[2 * (o0 + o)], 0, extent - 1);
       const int most = ksize < extent - xmin ? ksize : extent - xmin;
-      count = mc_clamp(b[2 * (o0 + o) + 1], 0, most);
+      count = frame_clamp(b[2 * (o0 + o) + 1], 0, most);
     }
     bounds[o][0] = xmin, bounds[o][1] = count;
   }
 }
 
 template <bool F32>
-__global__ __launch_bounds__(MC_THREADS) void multiscale_crop_kernel(const uint8_t* __restrict__ x, void* __restrict__ out,
-                                                                    const int32_t* __restrict__ tab, McNorm nm, int B, int T, int Hs, int Ws,
+__global__ __launch_bounds__(FRAME_THREADS) void multiscale_crop_kernel(const uint8_t* __restrict__ x, void* __restrict__ out,
+                                                                    const int32_t* __restrict__ tab, ClipNorm nm, int B, int T, int Hs, int Ws,
                                                                     int Sh, int Sw, int nh, int nv, int tiles_x) {
-  __shared__ uint32_t rows[3][MC_ROWS][MC_CG];
-  __shared__ int hk[MC_TC][MC_K], vk[MC_TR][MC_K], hb[MC_TC][2], vb[MC_TR][2];
+  __shared__ uint32_t rows[3][MC_ROWS][FRAME_CG];
+  __shared__ int hk[FRAME_TC][MC_K], vk[FRAME_TR][MC_K], hb[FRAME_TC][2], vb[FRAME_TR][2];
   const int32_t* r = tab + (int64_t)blockIdx.z * TAD_MSC_ROW_WORDS;
   const int sample = r[0];
   if (sample < 0 || sample >= B) return;  // (the same for every thread of the workgroup)
   const int t = blockIdx.y, tid = threadIdx.x;
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
   // the crop cut to the source, the set indices to the sets
-  const int x0 = mc_clamp(r[1], 0, Ws - 1), y0 = mc_clamp(r[2], 0, Hs - 1);
-  const int w = mc_clamp(r[3], 1, Ws - x0), h = mc_clamp(r[4], 1, Hs - y0);
+  const int x0 = frame_clamp(r[1], 0, Ws - 1), y0 = frame_clamp(r[2], 0, Hs - 1);
+  const int w = frame_clamp(r[3], 1, Ws - x0), h = frame_clamp(r[4], 1, Hs - y0);
   const int32_t* sets = tab + (int64_t)B * TAD_MSC_ROW_WORDS;
-  const int32_t* hset = sets + mc_clamp(r[5], 0, nh - 1) * mc_slot_words(Sw);
-  const int32_t* vset = sets + nh * mc_slot_words(Sw) + mc_clamp(r[6], 0, nv - 1) * mc_slot_words(Sh);
-  const int c0 = tx * MC_TC, o0 = ty * MC_TR;
-  const int nc = Sw - c0 < MC_TC ? Sw - c0 : MC_TC, nr = Sh - o0 < MC_TR ? Sh - o0 : MC_TR;
-  mc_stage(hset, Sw, w, c0, nc, hk, hb, MC_TC);
-  mc_stage(vset, Sh, h, o0, nr, vk, vb, MC_TR);
+  const int32_t* hset = sets + frame_clamp(r[5], 0, nh - 1) * mc_slot_words(Sw);
+  const int32_t* vset = sets + nh * mc_slot_words(Sw) + frame_clamp(r[6], 0, nv - 1) * mc_slot_words(Sh);
+  const int c0 = tx * FRAME_TC, o0 = ty * FRAME_TR;
+  const int nc = Sw - c0 < FRAME_TC ? Sw - c0 : FRAME_TC, nr = Sh - o0 < FRAME_TR ? Sh - o0 : FRAME_TR;
+  mc_stage(hset, Sw, w, c0, nc, hk, hb, FRAME_TC);
+  mc_stage(vset, Sh, h, o0, nr, vk, vb, FRAME_TR);
   __syncthreads();
 
   // the input rows under the tile's vertical taps: [lo, lo + n_in) of the crop
@@ -103,7 +90,7 @@ __global__ __launch_bounds__(MC_THREADS) void multiscale_crop_kernel(const uint8
   const uint8_t* src = x + (((int64_t)sample * T + t) * Hs + (y0 + lo)) * Ws * 3 + (int64_t)x0 * 3;
   // (only the column groups the tile has: a ragged last tile does not pay for the columns past the frame)
   const int ncg = (nc + 3) / 4;
-  for (int it = tid; it < n_in * 3 * ncg; it += MC_THREADS) {
+  for (int it = tid; it < n_in * 3 * ncg; it += FRAME_THREADS) {
     const int cg = it % ncg, rc = it / ncg, ch = rc % 3, rr = rc / 3;
     const uint8_t* p = src + (int64_t)rr * Ws * 3 + ch;
     uint32_t pk = 0;
@@ -112,14 +99,14 @@ __global__ __launch_bounds__(MC_THREADS) void multiscale_crop_kernel(const uint8
       const int c = cg * 4 + q, xmin = hb[c][0], count = hb[c][1];
       int ss = 1 << 21;
       for (int j = 0; j < count; ++j) ss += (int)p[(xmin + j) * 3] * hk[c][j];
-      pk |= mc_clip8(ss) << (8 * q);
+      pk |= frame_clip8(ss) << (8 * q);
     }
     rows[ch][rr][cg] = pk;
   }
   __syncthreads();
 
   // vertical pass: a thread owns four columns of one output row, all three channels
-  const int orow = tid / MC_CG, cg = tid - orow * MC_CG;
+  const int orow = tid / FRAME_CG, cg = tid - orow * FRAME_CG;
   const int col = c0 + cg * 4, valid = Sw - col < 4 ? Sw - col : 4;
   if (orow >= nr || valid <= 0) return;
   int acc[3][4];
@@ -143,35 +130,14 @@ __global__ __launch_bounds__(MC_THREADS) void multiscale_crop_kernel(const uint8
   if (F32) {
     float* o = static_cast<float*>(out) + (((int64_t)sample * 3 * T + t) * Sh + oy) * Sw + col;  // channel ch: + ch * T * Sh * Sw
     const int64_t plane = (int64_t)T * Sh * Sw;
+    float v[3][4];
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      float v[4];
+    for (int ch = 0; ch < 3; ++ch)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) v[q] = normalize_u8((float)mc_clip8(acc[ch][q]), nm.mean[ch], nm.sd[ch]);
-      float* oc = o + ch * plane;
-      if (valid == 4 && (reinterpret_cast<uintptr_t>(oc) & 15) == 0) {
-        *reinterpret_cast<float4*>(oc) = make_float4(v[0], v[1], v[2], v[3]);
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          if (q < valid) oc[q] = v[q];
-      }
-    }
+      for (int q = 0; q < 4; ++q) v[ch][q] = frame_norm8(acc[ch][q], nm.mean[ch], nm.sd[ch]);
+    store_clip_f32x4(o, plane, v, valid);
   } else {
-    uint8_t* o = static_cast<uint8_t*>(out) + ((((int64_t)sample * T + t) * Sh + oy) * Sw + col) * 3;
-    uint32_t pk[3] = {0, 0, 0};
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) pk[(3 * q + ch) >> 2] |= mc_clip8(acc[ch][q]) << (((3 * q + ch) & 3) * 8);
-    if (valid == 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i) reinterpret_cast<uint32_t*>(o)[i] = pk[i];
-    } else {
-#pragma unroll
-      for (int i = 0; i < 12; ++i)
-        if (i < 3 * valid) o[i] = (uint8_t)(pk[i >> 2] >> ((i & 3) * 8));
-    }
+    store_frames_u8x4(static_cast<uint8_t*>(out) + ((((int64_t)sample * T + t) * Sh + oy) * Sw + col) * 3, acc, valid);
   }
 }
 
@@ -226,13 +192,12 @@ extern "C" int tad_multiscale_crop_plan_check(const int32_t* table_host, int64_t
   const int32_t* vsets = sets + n_hsets * mc_slot_words(S_w);
   for (int i = 0; i < n_vsets; ++i)
     if (int rc = mc_check_set(vsets + i * mc_slot_words(S_h), S_h, Hs, "vertical", i)) return rc;
-  uint64_t seen[1024] = {0};  // (B <= 65535)
+  SeenSamples seen;  // (B <= 65535)
   for (int k = 0; k < B; ++k) {
     const int32_t* r = table_host + (int64_t)k * TAD_MSC_ROW_WORDS;
     const int sample = r[0], x0 = r[1], y0 = r[2], w = r[3], h = r[4], hs = r[5], vs = r[6];
     TAD_REQUIRE(0 <= sample && sample < B, "multiscale_crop_plan_check: row %d: sample=%d outside the batch B=%d", k, sample, B);
-    TAD_REQUIRE(!(seen[sample >> 6] >> (sample & 63) & 1), "multiscale_crop_plan_check: row %d: sample=%d has two rows", k, sample);
-    seen[sample >> 6] |= (uint64_t)1 << (sample & 63);
+    TAD_REQUIRE(!seen.twice(sample), "multiscale_crop_plan_check: row %d: sample=%d has two rows", k, sample);
     TAD_REQUIRE(x0 >= 0 && y0 >= 0 && w >= 1 && h >= 1 && (int64_t)x0 + w <= Ws && (int64_t)y0 + h <= Hs,
                 "multiscale_crop_plan_check: row %d: crop x0=%d y0=%d w=%d h=%d is not inside the %d x %d source", k, x0, y0, w, h, Ws, Hs);
     TAD_REQUIRE(0 <= hs && hs < n_hsets && 0 <= vs && vs < n_vsets, "multiscale_crop_plan_check: row %d: set indices %d, %d outside [0, %d) / [0, %d)",
@@ -250,28 +215,23 @@ extern "C" int tad_multiscale_crop(const uint8_t* x, void* out, int out_f32, con
   TAD_REQUIRE(x && out && workspace, "multiscale_crop: null pointer");
   if (int rc = mc_shape_ok(B, n_hsets, n_vsets, Hs, Ws, S_h, S_w, "multiscale_crop")) return rc;
   TAD_REQUIRE(T > 0 && T <= 65535, "multiscale_crop: T=%d must be in [1, 65535]", T);
-  TAD_REQUIRE_ALIGNED("multiscale_crop", workspace, 4);
-  TAD_REQUIRE(workspace_bytes >= tad_multiscale_crop_workspace_bytes(B, n_hsets, n_vsets, S_h, S_w),
-              "multiscale_crop: workspace of %zu bytes, need %zu", workspace_bytes,
-              tad_multiscale_crop_workspace_bytes(B, n_hsets, n_vsets, S_h, S_w));
-  McNorm nm = {{0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}};
+  if (int rc = table_workspace_ok("multiscale_crop", workspace, workspace_bytes, tad_multiscale_crop_workspace_bytes(B, n_hsets, n_vsets, S_h, S_w)))
+    return rc;
+  ClipNorm nm = CLIP_NORM_IDENTITY;
   if (out_f32) {
     TAD_REQUIRE(mean && std_, "multiscale_crop: the f32 output needs mean and std");
     TAD_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "multiscale_crop: an f32 out must be 4-byte aligned");
-    for (int c = 0; c < 3; ++c) {
-      TAD_REQUIRE(std::isfinite(mean[c]) && std::isfinite(std_[c]) && std_[c] != 0.0f, "multiscale_crop: mean / std of channel %d", c);
-      nm.mean[c] = mean[c], nm.sd[c] = std_[c];
-    }
+    if (int rc = clip_norm_from("multiscale_crop", mean, std_, &nm)) return rc;
   }
-  const int tiles_x = (S_w + MC_TC - 1) / MC_TC, tiles_y = (S_h + MC_TR - 1) / MC_TR;
-  const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)T, (unsigned)B);
+  int tiles_x;
+  const dim3 grid(frame_tile_grid(S_h, S_w, &tiles_x), (unsigned)T, (unsigned)B);
   const int32_t* tab = static_cast<const int32_t*>(workspace);
   hipStream_t s = (hipStream_t)stream;
   if (out_f32)
-    hipLaunchKernelGGL(multiscale_crop_kernel<true>, grid, dim3(MC_THREADS), 0, s, x, out, tab, nm, B, T, Hs, Ws, S_h, S_w, n_hsets, n_vsets,
+    hipLaunchKernelGGL(multiscale_crop_kernel<true>, grid, dim3(FRAME_THREADS), 0, s, x, out, tab, nm, B, T, Hs, Ws, S_h, S_w, n_hsets, n_vsets,
                        tiles_x);
   else
-    hipLaunchKernelGGL(multiscale_crop_kernel<false>, grid, dim3(MC_THREADS), 0, s, x, out, tab, nm, B, T, Hs, Ws, S_h, S_w, n_hsets, n_vsets,
+    hipLaunchKernelGGL(multiscale_crop_kernel<false>, grid, dim3(FRAME_THREADS), 0, s, x, out, tab, nm, B, T, Hs, Ws, S_h, S_w, n_hsets, n_vsets,
                        tiles_x);
   return check_launch("multiscale_crop");
 }

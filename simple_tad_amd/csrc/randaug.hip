@@ -25,8 +25,7 @@
 //                   truncation, or BICUBIC p1 + d * (p2 + d * (p3 + d * p4)) with p1 = v2, p2 = -v1 + v3, p3 = 2 * (v1 - v2) + v3 - v4,
 //                   p4 = -v1 + v2 - v3 + v4 over four clamped columns and rows, cut to [0, 255] and truncated.
 // The file is compiled without floating-point contraction (build.py): every product and sum rounds as the C code's does.
-#include "common.h"
-#include <math.h>
+#include "frame_io.h"
 
 TAD_NAMESPACE_BEGIN
 
@@ -374,7 +373,8 @@ __global__ __launch_bounds__(RA_THREADS) void randaug_apply_kernel(const uint8_t
 
 // ---------------------------------------------------------------- uint8 frames [B,T,H,W,3] -> normalised f32 clips [B,3,T,H,W]
 // ToTensor, tensor_normalize (normalize_u8, common.h: two IEEE divisions and one subtraction in f32 per element), permute.  An item
-// is four pixels of a frame: twelve bytes in, one 16-byte store per channel plane where the planes are 16-byte aligned
+// is four pixels of a frame: twelve bytes in, one 16-byte store per channel plane where the planes are 16-byte aligned (a whole frame
+// per stride, not the tiles of frame_io.h, which states the normalisation and the host checks this entry point shares)
 __global__ __launch_bounds__(RA_THREADS) void frames_to_clip_kernel(const uint8_t* __restrict__ x, float* __restrict__ out, float m0, float m1,
                                                                    float m2, float s0, float s1, float s2, int T, int HW) {
   const int t = blockIdx.y, b = blockIdx.z;
@@ -415,7 +415,7 @@ static int ra_shape_ok(int n_layers, int B, int T, int H, int W, const char* who
   TAD_REQUIRE(n_layers >= 0 && n_layers <= TAD_RANDAUG_MAX_LAYERS, "%s: n_layers=%d must be in [0, %d]", who, n_layers,
               TAD_RANDAUG_MAX_LAYERS);
   TAD_REQUIRE(B > 0 && B <= 65535 && T > 0 && T <= 64, "%s: B=%d must be in [1, 65535] and T=%d in [1, 64]", who, B, T);
-  TAD_REQUIRE(H > 0 && W > 0 && (int64_t)H * W <= ((int64_t)1 << 28), "%s: H=%d W=%d: a frame must have 1 .. 2^28 pixels", who, H, W);
+  if (int rc = frame_extent_ok(who, H, W)) return rc;
   return TAD_OK;
 }
 
@@ -425,14 +425,12 @@ extern "C" int tad_randaug_plan_check(const int32_t* table_host, int64_t n_words
   TAD_REQUIRE(n_words == (int64_t)n_layers * B * TAD_RANDAUG_ROW_WORDS, "randaug_plan_check: %lld words, expected n_layers * B * %d = %lld",
               (long long)n_words, TAD_RANDAUG_ROW_WORDS, (long long)n_layers * B * TAD_RANDAUG_ROW_WORDS);
   for (int l = 0; l < n_layers; ++l) {
-    uint64_t seen[1024] = {0};  // (B <= 65535)
+    SeenSamples seen;  // (B <= 65535)
     for (int k = 0; k < B; ++k) {
       const RaRow* r = reinterpret_cast<const RaRow*>(table_host + ((int64_t)l * B + k) * TAD_RANDAUG_ROW_WORDS);
       TAD_REQUIRE(0 <= r->sample && r->sample < B, "randaug_plan_check: layer %d row %d: sample=%d outside the batch B=%d", l, k, r->sample,
                   B);
-      TAD_REQUIRE(!(seen[r->sample >> 6] >> (r->sample & 63) & 1), "randaug_plan_check: layer %d row %d: sample=%d has two rows", l, k,
-                  r->sample);
-      seen[r->sample >> 6] |= (uint64_t)1 << (r->sample & 63);
+      TAD_REQUIRE(!seen.twice(r->sample), "randaug_plan_check: layer %d row %d: sample=%d has two rows", l, k, r->sample);
       TAD_REQUIRE(ra_known(r->op), "randaug_plan_check: layer %d row %d: unknown op=%d", l, k, r->op);
       if (r->op == TAD_RA_POSTERIZE) TAD_REQUIRE(r->iarg >= 0 && r->iarg <= 8, "randaug_plan_check: layer %d row %d: bits=%d", l, k, r->iarg);
       if (r->op == TAD_RA_SOLARIZE) TAD_REQUIRE(r->iarg >= 0 && r->iarg <= 256, "randaug_plan_check: layer %d row %d: thresh=%d", l, k, r->iarg);
@@ -500,13 +498,13 @@ extern "C" int tad_frames_to_clip(const uint8_t* x, float* out, const float* mea
   TAD_REQUIRE(x && out && mean && std_, "frames_to_clip: null pointer");
   if (int rc = ra_shape_ok(0, B, T, H, W, "frames_to_clip")) return rc;
   TAD_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "frames_to_clip: out must be 4-byte aligned");
-  for (int c = 0; c < 3; ++c)
-    TAD_REQUIRE(std::isfinite(mean[c]) && std::isfinite(std_[c]) && std_[c] != 0.0f, "frames_to_clip: mean / std of channel %d", c);
+  ClipNorm nm;
+  if (int rc = clip_norm_from("frames_to_clip", mean, std_, &nm)) return rc;
   const int HW = H * W;
   int64_t gx = ((int64_t)(HW + 3) / 4 + RA_THREADS - 1) / RA_THREADS;
   const int64_t cap = (int64_t)B * T >= RA_MAX_BLOCKS ? 1 : RA_MAX_BLOCKS / ((int64_t)B * T);
   if (gx > cap) gx = cap;
   hipLaunchKernelGGL(frames_to_clip_kernel, dim3((unsigned)gx, (unsigned)T, (unsigned)B), dim3(RA_THREADS), 0, (hipStream_t)stream, x, out,
-                     mean[0], mean[1], mean[2], std_[0], std_[1], std_[2], T, HW);
+                     nm.mean[0], nm.mean[1], nm.mean[2], nm.sd[0], nm.sd[1], nm.sd[2], T, HW);
   return check_launch("frames_to_clip");
 }

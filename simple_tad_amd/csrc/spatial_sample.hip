@@ -17,32 +17,20 @@
 //   value = l0y * (l0x * a + l1x * b) + l1y * (l0x * c + l1x * d)
 // A uint8 tap first becomes frames_to_clip's normalize_u8 (common.h) of the byte; a workgroup states those 3 x 256 values once, in LDS.
 //
-// Shape: a gather without reuse beyond the two rows and two columns of a tap, bound by memory traffic.  A workgroup owns SS_TR x
-// SS_TC outputs of one frame for all three channels; a thread owns four neighbouring output columns of one row: it states its row's
-// and its four columns' (i0, i1, l1) in registers (nine multiplications: cheaper than a trip through LDS and a barrier), loads the
+// Shape: a gather without reuse beyond the two rows and two columns of a tap, bound by memory traffic.  A workgroup owns FRAME_TR x
+// FRAME_TC outputs of one frame (frame_io.h) for all three channels; a thread owns four neighbouring output columns of one row: it
+// states its row's and its four columns' (i0, i1, l1) in registers (nine multiplications: cheaper than a trip through LDS and a barrier), loads the
 // 2 x 2 taps of each output (neighbouring lanes read neighbouring or equal addresses: the lines are shared in the vector cache) and
-// issues one 16-byte store per channel where the address allows it.
-#include "common.h"
-#include <math.h>
+// hands them to the clip writer of frame_io.h, which describes the output path.
+#include "frame_io.h"
 #include <string.h>
 
 TAD_NAMESPACE_BEGIN
-
-constexpr int SS_THREADS = 256;
-constexpr int SS_TR = 32, SS_TC = 32;                    // output rows x columns of a tile: SS_TR * SS_TC / 4 = SS_THREADS
-constexpr int SS_CG = SS_TC / 4;
-static_assert(SS_TR * SS_CG == SS_THREADS, "tile shape");
-
-struct SsNorm {
-  float mean[3], sd[3];
-};
 
 struct SsAxis {
   int i0, i1;
   float l0, l1;
 };
-
-__device__ __forceinline__ int ss_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // the taps of index d of the resized grid over n_in source samples.  Whatever `scale` holds (NaN and infinities included), i0 and i1
 // lie in [0, n_in): the comparison is false for a NaN and n_in - 1 is taken.
@@ -63,14 +51,14 @@ __device__ __forceinline__ float ss_blend(const SsAxis& y, const SsAxis& x, floa
 }
 
 template <bool U8>
-__global__ __launch_bounds__(SS_THREADS) void spatial_sample_kernel(const void* __restrict__ xv, float* __restrict__ out,
-                                                                   const int32_t* __restrict__ tab, SsNorm nm, int B, int T, int H, int W, int S,
+__global__ __launch_bounds__(FRAME_THREADS) void spatial_sample_kernel(const void* __restrict__ xv, float* __restrict__ out,
+                                                                   const int32_t* __restrict__ tab, ClipNorm nm, int B, int T, int H, int W, int S,
                                                                    int tiles_x) {
   __shared__ float lut[U8 ? 3 * 256 : 1];
   const int tid = threadIdx.x;
   if (U8) {
     // frames_to_clip's value of every byte, per channel: 768 entries, three per thread
-    for (int e = tid; e < 3 * 256; e += SS_THREADS) {
+    for (int e = tid; e < 3 * 256; e += FRAME_THREADS) {
       const int ch = e >> 8;
       lut[e] = normalize_u8((float)(e & 255), nm.mean[ch], nm.sd[ch]);
     }
@@ -81,14 +69,14 @@ __global__ __launch_bounds__(SS_THREADS) void spatial_sample_kernel(const void* 
   if (sample < 0 || sample >= B * T) return;  // (the same for every thread of the workgroup, and after the only barrier)
   const int clip = sample / T, t = sample - clip * T;
   // the window cut to the source: whatever the row says, every address below lies inside frame (clip, t) of x
-  const int wi = ss_clamp(r[1], 0, H - 1), wj = ss_clamp(r[2], 0, W - 1);
-  const int wh = ss_clamp(r[3], 1, H - wi), ww = ss_clamp(r[4], 1, W - wj);
+  const int wi = frame_clamp(r[1], 0, H - 1), wj = frame_clamp(r[2], 0, W - 1);
+  const int wh = frame_clamp(r[3], 1, H - wi), ww = frame_clamp(r[4], 1, W - wj);
   const int oy = r[7], ox = r[8];
   const bool flip = r[9] != 0;
   const float sy = __int_as_float(r[10]), sx = __int_as_float(r[11]);
 
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  const int orow = ty * SS_TR + tid / SS_CG, col = tx * SS_TC + (tid % SS_CG) * 4;
+  const int orow = ty * FRAME_TR + tid / FRAME_CG, col = tx * FRAME_TC + (tid % FRAME_CG) * 4;
   const int valid = S - col < 4 ? S - col : 4;
   if (orow >= S || valid <= 0) return;
 
@@ -128,18 +116,7 @@ __global__ __launch_bounds__(SS_THREADS) void spatial_sample_kernel(const void* 
   }
 
   const int64_t oplane = (int64_t)T * S * S;
-  float* o = out + (((int64_t)clip * 3 * T + t) * S + orow) * S + col;
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    float* oc = o + ch * oplane;
-    if (valid == 4 && (reinterpret_cast<uintptr_t>(oc) & 15) == 0) {
-      *reinterpret_cast<float4*>(oc) = make_float4(v[ch][0], v[ch][1], v[ch][2], v[ch][3]);
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (q < valid) oc[q] = v[ch][q];
-    }
-  }
+  store_clip_f32x4(out + (((int64_t)clip * 3 * T + t) * S + orow) * S + col, oplane, v, valid);
 }
 
 TAD_NAMESPACE_END
@@ -148,7 +125,7 @@ using namespace tad;
 
 static int ss_shape_ok(int B, int T, int H, int W, int S, const char* who) {
   TAD_REQUIRE(B > 0 && T > 0 && (int64_t)B * T <= 65535, "%s: B=%d T=%d: B * T must be in [1, 65535]", who, B, T);
-  TAD_REQUIRE(H > 0 && W > 0 && (int64_t)H * W <= ((int64_t)1 << 28), "%s: H=%d W=%d: a frame must have 1 .. 2^28 pixels", who, H, W);
+  if (int rc = frame_extent_ok(who, H, W)) return rc;
   TAD_REQUIRE(S > 0 && S <= 16384, "%s: S=%d must be in [1, 16384]", who, S);
   return TAD_OK;
 }
@@ -164,13 +141,12 @@ extern "C" int tad_spatial_sample_plan_check(const int32_t* table_host, int64_t 
   const int n = B * T;
   TAD_REQUIRE(n_words == (int64_t)n * TAD_SS_ROW_WORDS, "spatial_sample_plan_check: %lld words, expected B * T * %d = %lld",
               (long long)n_words, TAD_SS_ROW_WORDS, (long long)n * TAD_SS_ROW_WORDS);
-  uint64_t seen[1024] = {0};  // (B * T <= 65535)
+  SeenSamples seen;  // (B * T <= 65535)
   for (int k = 0; k < n; ++k) {
     const int32_t* r = table_host + (int64_t)k * TAD_SS_ROW_WORDS;
     const int sample = r[0], i = r[1], j = r[2], h = r[3], w = r[4], rh = r[5], rw = r[6], oy = r[7], ox = r[8], flip = r[9];
     TAD_REQUIRE(0 <= sample && sample < n, "spatial_sample_plan_check: row %d: sample=%d outside the B * T = %d frames", k, sample, n);
-    TAD_REQUIRE(!(seen[sample >> 6] >> (sample & 63) & 1), "spatial_sample_plan_check: row %d: sample=%d has two rows", k, sample);
-    seen[sample >> 6] |= (uint64_t)1 << (sample & 63);
+    TAD_REQUIRE(!seen.twice(sample), "spatial_sample_plan_check: row %d: sample=%d has two rows", k, sample);
     TAD_REQUIRE(i >= 0 && j >= 0 && h >= 1 && w >= 1 && (int64_t)i + h <= H && (int64_t)j + w <= W,
                 "spatial_sample_plan_check: row %d: window i=%d j=%d h=%d w=%d is not inside the %d x %d source", k, i, j, h, w, H, W);
     TAD_REQUIRE(rh >= 1 && rw >= 1 && oy >= 0 && ox >= 0 && (int64_t)oy + S <= rh && (int64_t)ox + S <= rw,
@@ -190,27 +166,22 @@ extern "C" int tad_spatial_sample(const void* x, int x_u8, float* out, const flo
                                   size_t workspace_bytes, int B, int T, int H, int W, int S, tad_stream_t stream) {
   TAD_REQUIRE(x && out && workspace, "spatial_sample: null pointer");
   if (int rc = ss_shape_ok(B, T, H, W, S, "spatial_sample")) return rc;
-  TAD_REQUIRE_ALIGNED("spatial_sample", workspace, 4);
-  TAD_REQUIRE(workspace_bytes >= tad_spatial_sample_workspace_bytes(B, T), "spatial_sample: workspace of %zu bytes, need %zu",
-              workspace_bytes, tad_spatial_sample_workspace_bytes(B, T));
+  if (int rc = table_workspace_ok("spatial_sample", workspace, workspace_bytes, tad_spatial_sample_workspace_bytes(B, T))) return rc;
   TAD_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "spatial_sample: out must be 4-byte aligned");
-  SsNorm nm = {{0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}};
+  ClipNorm nm = CLIP_NORM_IDENTITY;
   if (x_u8) {
     TAD_REQUIRE(mean && std_, "spatial_sample: uint8 frames need mean and std");
-    for (int c = 0; c < 3; ++c) {
-      TAD_REQUIRE(std::isfinite(mean[c]) && std::isfinite(std_[c]) && std_[c] != 0.0f, "spatial_sample: mean / std of channel %d", c);
-      nm.mean[c] = mean[c], nm.sd[c] = std_[c];
-    }
+    if (int rc = clip_norm_from("spatial_sample", mean, std_, &nm)) return rc;
   } else {
     TAD_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0, "spatial_sample: f32 clips must be 4-byte aligned");
   }
-  const int tiles_x = (S + SS_TC - 1) / SS_TC, tiles_y = (S + SS_TR - 1) / SS_TR;
-  const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)(B * T));
+  int tiles_x;
+  const dim3 grid(frame_tile_grid(S, S, &tiles_x), (unsigned)(B * T));
   const int32_t* tab = static_cast<const int32_t*>(workspace);
   hipStream_t s = (hipStream_t)stream;
   if (x_u8)
-    hipLaunchKernelGGL(spatial_sample_kernel<true>, grid, dim3(SS_THREADS), 0, s, x, out, tab, nm, B, T, H, W, S, tiles_x);
+    hipLaunchKernelGGL(spatial_sample_kernel<true>, grid, dim3(FRAME_THREADS), 0, s, x, out, tab, nm, B, T, H, W, S, tiles_x);
   else
-    hipLaunchKernelGGL(spatial_sample_kernel<false>, grid, dim3(SS_THREADS), 0, s, x, out, tab, nm, B, T, H, W, S, tiles_x);
+    hipLaunchKernelGGL(spatial_sample_kernel<false>, grid, dim3(FRAME_THREADS), 0, s, x, out, tab, nm, B, T, H, W, S, tiles_x);
   return check_launch("spatial_sample");
 }

@@ -1240,6 +1240,32 @@ def _req_frames(x, name):
         raise _lib.TadError(f"{name}: expected uint8 frames [B,T,H,W,3], got {tuple(x.shape)}")
 
 
+def _clip_out(name, out, shape, dtype, device):
+    """The output of a frame kernel: a new tensor of ``shape``, or the caller's ``out`` (any contiguous view: a ring slot, a slice of
+    a frame store) held to that shape, ``dtype`` and device."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _req(out, dtype, f"{name}.out")
+    if tuple(out.shape) != shape or out.device != device:
+        raise _lib.TadError(f"{name}.out: expected {shape} on {device}, got {tuple(out.shape)} on {out.device}")
+    return out
+
+
+def _norm_pair(name, mean, std):
+    """(mean, std) as the C entry points take them, (None, None) without them; one without the other is an error"""
+    if (mean is None) != (std is None):
+        raise _lib.TadError(f"{name}: mean and std come together")
+    return (None, None) if mean is None else (_f3(mean), _f3(std))
+
+
+def _req_table(name, table, shape, nbytes, what, device):
+    """``table`` is the device copy of ``name``_table()'s tensor: int32 words of ``shape``, the ``nbytes`` bytes of the call's
+    workspace, on the device of its frames"""
+    _req(table, torch.int32, f"{name}.table")
+    if tuple(table.shape) != shape or nbytes == 0 or table.device != device:
+        raise _lib.TadError(f"{name}.table: expected the device copy of {name}_table() for {what}, got {tuple(table.shape)} on {table.device}")
+
+
 def randaug_apply(x, table, stats_layers: int):
     """Carry the device table ``table`` (a copy of randaug_table()'s, [n_layers, B, RANDAUG_ROW_WORDS]) out on the contiguous uint8
     frames x [B,T,H,W,3] (tad_randaug_apply: per layer one apply launch, plus one statistics launch where ``stats_layers`` has the
@@ -1265,12 +1291,7 @@ def frames_to_clip(x, mean, std, out=None):
     ONE launch; IEEE division): torchvision's ToTensor, the reference's tensor_normalize and its permute, bit for bit."""
     _req_frames(x, "frames_to_clip.x")
     B, T, H, W, _ = x.shape
-    if out is None:
-        out = torch.empty((B, 3, T, H, W), dtype=torch.float32, device=x.device)
-    else:
-        _req(out, torch.float32, "frames_to_clip.out")
-        if tuple(out.shape) != (B, 3, T, H, W) or out.device != x.device:
-            raise _lib.TadError(f"frames_to_clip.out: expected {(B, 3, T, H, W)} on {x.device}, got {tuple(out.shape)} on {out.device}")
+    out = _clip_out("frames_to_clip", out, (B, 3, T, H, W), torch.float32, x.device)
     with _timed("frames_to_clip", 0.0, 13.0 * B * T * H * W):
         check(_lib.load().tad_frames_to_clip(x.data_ptr(), out.data_ptr(), _f3(mean), _f3(std), B, T, H, W, _stream()), "tad_frames_to_clip")
     return out
@@ -1312,23 +1333,12 @@ def multiscale_crop(x, table, n_hsets: int, n_vsets: int, S_h: int, S_w: int, me
     with them: the normalised f32 clips [B,3,T,S_h,S_w], the bits frames_to_clip gives on the uint8 result.  x is only read."""
     _req_frames(x, "multiscale_crop.x")
     B, T, Hs, Ws, _ = x.shape
-    _req(table, torch.int32, "multiscale_crop.table")
     lib = _lib.load()
     nbytes = lib.tad_multiscale_crop_workspace_bytes(B, n_hsets, n_vsets, S_h, S_w)
-    if table.dim() != 1 or nbytes == 0 or table.numel() * 4 != nbytes or table.device != x.device:
-        raise _lib.TadError(f"multiscale_crop.table: expected the device copy of multiscale_crop_table() for {B} clips ({nbytes} bytes), "
-                            f"got {tuple(table.shape)} on {table.device}")
-    if (mean is None) != (std is None):
-        raise _lib.TadError("multiscale_crop: mean and std come together")
-    f32 = mean is not None
-    shape = (B, 3, T, S_h, S_w) if f32 else (B, T, S_h, S_w, 3)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32 if f32 else torch.uint8, device=x.device)
-    else:
-        _req(out, torch.float32 if f32 else torch.uint8, "multiscale_crop.out")
-        if tuple(out.shape) != shape or out.device != x.device:
-            raise _lib.TadError(f"multiscale_crop.out: expected {shape} on {x.device}, got {tuple(out.shape)} on {out.device}")
-    m, s = (_f3(mean), _f3(std)) if f32 else (None, None)
+    _req_table("multiscale_crop", table, (nbytes // 4,), nbytes, f"{B} clips ({nbytes} bytes)", x.device)
+    m, s = _norm_pair("multiscale_crop", mean, std)
+    f32 = m is not None
+    out = _clip_out("multiscale_crop", out, (B, 3, T, S_h, S_w) if f32 else (B, T, S_h, S_w, 3), torch.float32 if f32 else torch.uint8, x.device)
     with _timed("multiscale_crop", 0.0, float(x.numel() + out.numel() * out.element_size())):
         check(lib.tad_multiscale_crop(x.data_ptr(), out.data_ptr(), int(f32), m, s, table.data_ptr(), nbytes, B, T, Hs, Ws, S_h, S_w,
                                       n_hsets, n_vsets, _stream()), "tad_multiscale_crop")
@@ -1378,23 +1388,12 @@ def frame_resize(x, table, n_vsets: int, S_h: int, S_w: int, mean=None, std=None
     the uint8 result.  ``out`` may be any contiguous view of that shape (a ring slot, a slice of a frame store).  x is only read."""
     _req_frames(x, "frame_resize.x")
     B, T, H, W, _ = x.shape
-    _req(table, torch.int32, "frame_resize.table")
     lib = _lib.load()
     nbytes = lib.tad_frame_resize_workspace_bytes(B, n_vsets, S_h, S_w)
-    if table.dim() != 1 or nbytes == 0 or table.numel() * 4 != nbytes or table.device != x.device:
-        raise _lib.TadError(f"frame_resize.table: expected the device copy of frame_resize_table() for {B} clips ({nbytes} bytes), "
-                            f"got {tuple(table.shape)} on {table.device}")
-    if (mean is None) != (std is None):
-        raise _lib.TadError("frame_resize: mean and std come together")
-    f32 = mean is not None
-    shape = (B, 3, T, S_h, S_w) if f32 else (B, T, S_h, S_w, 3)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32 if f32 else torch.uint8, device=x.device)
-    else:
-        _req(out, torch.float32 if f32 else torch.uint8, "frame_resize.out")
-        if tuple(out.shape) != shape or out.device != x.device:
-            raise _lib.TadError(f"frame_resize.out: expected {shape} on {x.device}, got {tuple(out.shape)} on {out.device}")
-    m, s = (_f3(mean), _f3(std)) if f32 else (None, None)
+    _req_table("frame_resize", table, (nbytes // 4,), nbytes, f"{B} clips ({nbytes} bytes)", x.device)
+    m, s = _norm_pair("frame_resize", mean, std)
+    f32 = m is not None
+    out = _clip_out("frame_resize", out, (B, 3, T, S_h, S_w) if f32 else (B, T, S_h, S_w, 3), torch.float32 if f32 else torch.uint8, x.device)
     with _timed("frame_resize", 0.0, float(x.numel() + out.numel() * out.element_size())):
         check(lib.tad_frame_resize(x.data_ptr(), out.data_ptr(), int(f32), m, s, table.data_ptr(), nbytes, B, T, H, W, S_h, S_w, n_vsets,
                                    _stream()), "tad_frame_resize")
@@ -1428,8 +1427,7 @@ def spatial_sample(x, table, S: int, mean=None, std=None, out=None):
     """Carry the device table ``table`` (a copy of spatial_sample_table()'s: the call's workspace, only read) out on the contiguous f32
     clips x [B,3,T,H,W] or, with ``mean`` / ``std``, on the contiguous uint8 frames x [B,T,H,W,3] (tad_spatial_sample, ONE launch).
     Returns the f32 clips [B,3,T,S,S]; from uint8 frames they have the bits of the f32 route on frames_to_clip(x).  x is only read."""
-    if (mean is None) != (std is None):
-        raise _lib.TadError("spatial_sample: mean and std come together")
+    m, s = _norm_pair("spatial_sample", mean, std)
     u8 = isinstance(x, torch.Tensor) and x.dtype == torch.uint8
     if u8:
         _req_frames(x, "spatial_sample.x")
@@ -1443,20 +1441,10 @@ def spatial_sample(x, table, S: int, mean=None, std=None, out=None):
         if mean is not None:
             raise _lib.TadError("spatial_sample: f32 clips are normalised already; mean and std go with uint8 frames")
         B, _, T, H, W = x.shape
-    _req(table, torch.int32, "spatial_sample.table")
     lib = _lib.load()
     nbytes = lib.tad_spatial_sample_workspace_bytes(B, T)
-    if tuple(table.shape) != (B * T, _lib.SS_ROW_WORDS) or nbytes == 0 or table.device != x.device:
-        raise _lib.TadError(f"spatial_sample.table: expected the device copy of spatial_sample_table() for {B} clips of {T} frames, "
-                            f"got {tuple(table.shape)} on {table.device}")
-    shape = (B, 3, T, S, S)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    else:
-        _req(out, torch.float32, "spatial_sample.out")
-        if tuple(out.shape) != shape or out.device != x.device:
-            raise _lib.TadError(f"spatial_sample.out: expected {shape} on {x.device}, got {tuple(out.shape)} on {out.device}")
-    m, s = (_f3(mean), _f3(std)) if u8 else (None, None)
+    _req_table("spatial_sample", table, (B * T, _lib.SS_ROW_WORDS), nbytes, f"{B} clips of {T} frames", x.device)
+    out = _clip_out("spatial_sample", out, (B, 3, T, S, S), torch.float32, x.device)
     with _timed("spatial_sample", 0.0, float(x.numel() * x.element_size() + out.numel() * 4)):
         check(lib.tad_spatial_sample(x.data_ptr(), int(u8), out.data_ptr(), m, s, table.data_ptr(), nbytes, B, T, H, W, S, _stream()),
               "tad_spatial_sample")

@@ -84,6 +84,67 @@ def test_host_validation_without_gpu(lib_path):
     assert lib.tad_adamw_step(p, p, p, p, None, p, 4096, lr, wd, 200, st, 0.9, 0.999, 1e-8, None, None, None) == -1  # > MAX_GROUPS
 
 
+def test_frame_kernels_keep_their_own_names_in_the_shared_host_checks(lib_path):
+    """the frame kernels share their host-side checks (csrc/frame_io.h); every message still reads as the entry point states it, its own
+    name in front.  Each call fails on the host, before any launch."""
+    from simple_tad_amd import _lib, kernels as K
+    lib = _lib.load()
+
+    def refused(rc):
+        assert rc == -1
+        return lib.tad_last_error_string().decode()
+
+    buf = ctypes.create_string_buffer(2048)
+    p = (ctypes.addressof(buf) + 255) & ~255  # a stand-in for every device pointer: 256-byte aligned, so p + 2 ends in 0x02
+    mean, std = (ctypes.c_float * 3)(0.5, 0.5, 0.5), (ctypes.c_float * 3)(0.25, 0.0, 0.25)
+    B, T, H, W, S = 2, 2, 4, 4, 2
+    need_mc = lib.tad_multiscale_crop_workspace_bytes(B, 1, 1, S, S)
+    need_fr = lib.tad_frame_resize_workspace_bytes(B, 1, S, S)
+    need_ss = lib.tad_spatial_sample_workspace_bytes(B, T)
+    assert (need_mc, need_fr, need_ss) == (400, 176, 192)
+
+    # a std of zero
+    assert refused(lib.tad_multiscale_crop(p, p, 1, mean, std, p, need_mc, B, T, H, W, S, S, 1, 1, None)) == "multiscale_crop: mean / std of channel 1"
+    assert refused(lib.tad_frame_resize(p, p, 1, mean, std, p, need_fr, B, T, H, W, S, S, 1, None)) == "frame_resize: mean / std of channel 1"
+    assert refused(lib.tad_spatial_sample(p, 1, p, mean, std, p, need_ss, B, T, H, W, S, None)) == "spatial_sample: mean / std of channel 1"
+    assert refused(lib.tad_frames_to_clip(p, p, mean, std, B, T, H, W, None)) == "frames_to_clip: mean / std of channel 1"
+    # a workspace one byte short, and one that is no table of int32 words
+    assert refused(lib.tad_multiscale_crop(p, p, 0, None, None, p, need_mc - 1, B, T, H, W, S, S, 1, 1, None)) == \
+        "multiscale_crop: workspace of 399 bytes, need 400"
+    assert refused(lib.tad_frame_resize(p, p, 0, None, None, p, need_fr - 1, B, T, H, W, S, S, 1, None)) == \
+        "frame_resize: workspace of 175 bytes, need 176"
+    assert refused(lib.tad_spatial_sample(p, 0, p, None, None, p, need_ss - 1, B, T, H, W, S, None)) == \
+        "spatial_sample: workspace of 191 bytes, need 192"
+    misaligned = "%s: workspace is misaligned: it must be 4-byte aligned (the address ends in 0x02)"
+    assert refused(lib.tad_multiscale_crop(p, p, 0, None, None, p + 2, need_mc, B, T, H, W, S, S, 1, 1, None)) == misaligned % "multiscale_crop"
+    assert refused(lib.tad_frame_resize(p, p, 0, None, None, p + 2, need_fr, B, T, H, W, S, S, 1, None)) == misaligned % "frame_resize"
+    assert refused(lib.tad_spatial_sample(p, 0, p, None, None, p + 2, need_ss, B, T, H, W, S, None)) == misaligned % "spatial_sample"
+
+    # a sample with two rows, in each plan check: a table its builder accepts, then row 1 renamed to sample 0
+    def twice(table, row_words, check, *shape):
+        tab = table.numpy().reshape(-1).copy()
+        assert check(tab.ctypes.data, tab.size, *shape) == 0
+        tab[row_words] = 0
+        return refused(check(tab.ctypes.data, tab.size, *shape))
+
+    half = [[1 << 21, 1 << 21]] * S  # two taps of a half each per output, 22-bit
+    msc_set = (4, 2, [[0, 2], [2, 2]], half)
+    tab = K.multiscale_crop_table([(0, 0, 0, W, H, 0, 0), (1, 0, 0, W, H, 0, 0)], [msc_set], [msc_set], B, H, W, S, S)
+    assert twice(tab, _lib.MSC_ROW_WORDS, lib.tad_multiscale_crop_plan_check, B, 1, 1, H, W, S, S) == \
+        "multiscale_crop_plan_check: row 1: sample=0 has two rows"
+    fr_set = (4, [0, 1], [[0, 2048, 0, 0]] * S)
+    tab = K.frame_resize_table([(k, _lib.FR_NONE, 0, 0, 0.0, (0, 0, 0), 0) for k in range(B)], fr_set, [fr_set], B, H, W, S, S)
+    assert twice(tab, _lib.FR_ROW_WORDS, lib.tad_frame_resize_plan_check, B, 1, H, W, S, S) == \
+        "frame_resize_plan_check: row 1: sample=0 has two rows"
+    tab = K.spatial_sample_table([(k, 0, 0, H, W, S, S, 0, 0, 0) for k in range(B * T)], B, T, H, W, S)
+    assert twice(tab, _lib.SS_ROW_WORDS, lib.tad_spatial_sample_plan_check, B, T, H, W, S) == \
+        "spatial_sample_plan_check: row 1: sample=0 has two rows"
+    tab, _ = K.randaug_table([[(k, _lib.RA_COPY, 0, 0.0, None, (0, 0, 0), 0) for k in range(B)]] * 2, B, T)
+    tab = tab.numpy().copy()
+    tab[1, 1, 0] = 0  # the second layer's second row
+    assert refused(lib.tad_randaug_plan_check(tab.ctypes.data, tab.size, 2, B, T)) == "randaug_plan_check: layer 1 row 1: sample=0 has two rows"
+
+
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
     from simple_tad_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)

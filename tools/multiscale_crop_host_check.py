@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Run the TEXT of the multi-scale crop kernel (simple_tad_amd/csrc/multiscale_crop.hip, from its constants to the end of the kernel)
-on the CPU, in a stand-alone program built with the address and undefined-behaviour sanitizers, and hold it to the goldens.
+"""Run the TEXT of the multi-scale crop kernel (simple_tad_amd/csrc/multiscale_crop.hip, from its constants to the end of the kernel,
+behind the device half of csrc/frame_io.h: the tile, the clamps and the writers of the output) on the CPU, in a stand-alone program built with the address and undefined-behaviour sanitizers, and hold it to the goldens.
 
 The program defines the few HIP words the kernel uses (``__global__``, ``threadIdx``, ``__shared__`` as static storage,
 ``__fdiv_rn`` ...) and runs the 256 threads of a workgroup in turn, barrier by barrier: ``__syncthreads()`` ends a thread's run at the
@@ -70,10 +70,10 @@ int main(int argc, char** argv) {  // x.bin tab.bin out.bin f32 B T Hs Ws Sh Sw 
   if (nx != (size_t)B * T * Hs * Ws * 3 || nt != (size_t)mc_table_words(B, nh, nv, Sh, Sw)) return 3;
   const size_t on = (size_t)B * T * Sh * Sw * 3 * (f32 ? 4 : 1);
   void* out = malloc(on); memset(out, 0x7F, on);
-  McNorm nm = {{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}};
-  const int tiles_x = (Sw + MC_TC - 1) / MC_TC, tiles_y = (Sh + MC_TR - 1) / MC_TR;
+  ClipNorm nm = {{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}};
+  const int tiles_x = (Sw + FRAME_TC - 1) / FRAME_TC, tiles_y = (Sh + FRAME_TR - 1) / FRAME_TR;
   for (unsigned z = 0; z < (unsigned)B; ++z) for (unsigned y = 0; y < (unsigned)T; ++y) for (unsigned t = 0; t < (unsigned)(tiles_x * tiles_y); ++t)
-    for (g_phase = 0; g_phase < 3; ++g_phase) for (unsigned tid = 0; tid < MC_THREADS; ++tid) {
+    for (g_phase = 0; g_phase < 3; ++g_phase) for (unsigned tid = 0; tid < FRAME_THREADS; ++tid) {
       blockIdx = {t, y, z}; threadIdx = {tid, 0, 0}; g_seen = 0;
       if (f32) multiscale_crop_kernel<true>(x, out, tab, nm, B, T, Hs, Ws, Sh, Sw, nh, nv, tiles_x);
       else multiscale_crop_kernel<false>(x, out, tab, nm, B, T, Hs, Ws, Sh, Sw, nh, nv, tiles_x);
@@ -96,7 +96,10 @@ def build(workdir):
     """the stand-alone program: the kernel's own text between two shims; returns its path"""
     with open(KERNEL) as f:
         src = f.read()
-    body = src[src.index("constexpr int MC_THREADS"):src.index("TAD_NAMESPACE_END")]
+    body = src[src.index("constexpr int MC_K"):src.index("TAD_NAMESPACE_END")]
+    with open(os.path.join(os.path.dirname(KERNEL), "frame_io.h")) as f:  # what the kernel shares with the other frame kernels: device side
+        src = f.read()
+    body = src[src.index("struct ClipNorm"):src.index("// ----", src.index("struct ClipNorm"))] + body
     with open(os.path.join(os.path.dirname(KERNEL), "common.h")) as f:  # the one helper of common.h the kernel calls, in its own text too
         normalize = next(line for line in f if "float normalize_u8(" in line)
     cpp, exe = os.path.join(workdir, "msc_host.cpp"), os.path.join(workdir, "msc_host")
