@@ -4,6 +4,7 @@ shared library is loaded on first use and every op fails loudly if it is missing
 from . import registry
 from .registry import create_model, register_model, list_models
 from . import modeling_finetune
+from . import internvideo2
 from .ops import set_precision, get_precision
 from .tuning import TuningScope
 from . import mixup, loss, random_erasing, rand_augment, transforms, spatial_sampling, frame_targets, grad_norms

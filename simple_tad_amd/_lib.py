@@ -146,6 +146,19 @@ for _bf, _h in (*F16_TWINS.items(), *VARIANT_F16_TWINS.items()):
     SIGNATURES[_h] = SIGNATURES[_bf]
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL = 0, 1, 2
 ABI_VERSION = 5
+
+# The extension ABI (include/tad_mi355x_ext.h): entry points added beside the frozen core ABI, in the same library, with a version of
+# their own.  name -> (restype, argtypes); the 16-bit format is an argument (TAD_BF16 / TAD_F16), so there are no twins.
+EXT_SIGNATURES = {
+    "tadx_abi_version": (_i, []),
+    "tadx_rmsnorm_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _i64, _i, _f, _vp]),
+    "tadx_rmsnorm_bwd_workspace_bytes": (_sz, [_i64, _i]),
+    "tadx_rmsnorm_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _sz, _i64, _i, _vp]),
+    "tadx_qk_rmsnorm_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _f, _i64, _i, _f, _vp]),
+    "tadx_qk_rmsnorm_bwd_workspace_bytes": (_sz, [_i64, _i]),
+    "tadx_qk_rmsnorm_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _vp, _sz, _i64, _i, _vp]),
+}
+EXT_ABI_VERSION = 1
 LINEAR_PLAN_FIELDS = ("r0", "rows", "kernel", "persistent", "direct", "grid", "block", "group_m", "sk_splits", "sk_mode", "epilogue")
 ATTN_PLAN_FIELDS = ("kernel", "hd", "out16", "qs", "drop", "dma_mode", "skip", "has_lo", "grid", "block")
 ATTN_FWD, ATTN_FWD_Q64, ATTN_BWD_DQ, ATTN_BWD_DKV = range(4)  # the "kernel" field
@@ -189,7 +202,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} not found: the HIP extension has not been built. Run `python -m simple_tad_amd.build` "
             "(or __graft_entry__.build()). There is no CPU fallback for the MI355X path.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover
@@ -199,6 +212,9 @@ def load() -> C.CDLL:
     v = lib.tad_abi_version()
     if v != ABI_VERSION:
         raise TadError(f"ABI mismatch: library reports {v}, binding expects {ABI_VERSION}")
+    v = lib.tadx_abi_version()
+    if v != EXT_ABI_VERSION:
+        raise TadError(f"extension ABI mismatch: library reports {v}, binding expects {EXT_ABI_VERSION}")
     _lib = lib
     return lib
 

@@ -554,6 +554,106 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres=None, want_bf16=False, want_col
     return dx, dxb, dg, db, cs
 
 
+# ----------------------------------------------------------------------------- RMSNorm, q / k RMS normalisation (extension ABI)
+def _ext(name: str):
+    return getattr(_lib.load(), name)
+
+
+def rmsnorm_fwd(x, gamma, eps: float, out_dtype=None, save_stats=True):
+    """y = x * rsqrt(mean(x^2) + eps) * gamma.  out_dtype: torch.float32, or a 16-bit operand format (None = the process-wide one).
+    Returns y, rrms [rows] | None."""
+    _req(x, torch.float32, "rmsnorm.x")
+    _req(gamma, torch.float32, "rmsnorm.gamma")
+    D = x.shape[-1]
+    rows = x.numel() // D
+    assert gamma.numel() == D
+    y = torch.empty(x.shape, dtype=out_dtype or _op16, device=x.device)
+    rrms = torch.empty(rows, dtype=torch.float32, device=x.device) if save_stats else None
+    with _timed("rmsnorm_fwd", 0.0, rows * D * (4.0 + y.element_size())):
+        check(_ext("tadx_rmsnorm_fwd")(x.data_ptr(), gamma.data_ptr(), y.data_ptr(), _dt(y), _p(rrms), rows, D, float(eps), _stream()),
+              "tadx_rmsnorm_fwd")
+    return y, rrms
+
+
+def rmsnorm_bwd(dy, x, gamma, rrms, dres=None, want_op16=False, into=None):
+    """returns dx f32, dx16 | None, dgamma.  dy: f32 or a 16-bit operand format (dx16 takes that format, else the process-wide one).
+    into: an existing f32 [D] tensor the gamma gradient is ADDED to (a gradient sink) instead of a fresh one."""
+    _req(x, torch.float32, "rmsnorm_bwd.x")
+    _req(gamma, torch.float32, "rmsnorm_bwd.gamma")
+    _req(rrms, torch.float32, "rmsnorm_bwd.rrms")
+    if not dy.is_cuda or dy.dtype not in (torch.float32,) + OP16_DTYPES or not dy.is_contiguous():
+        raise _lib.TadError("rmsnorm_bwd.dy: must be a contiguous GPU tensor, f32, bf16 or f16")
+    op = dy.dtype if dy.dtype in OP16_DTYPES else _op16
+    D = x.shape[-1]
+    rows = x.numel() // D
+    assert dy.numel() == x.numel() and rrms.numel() == rows and gamma.numel() == D
+    if dres is not None:
+        _req(dres, torch.float32, "rmsnorm_bwd.dres")
+        assert dres.numel() == x.numel()
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    dx16 = torch.empty(x.shape, dtype=op, device=x.device) if want_op16 else None
+    if into is not None:
+        _req(into, torch.float32, "rmsnorm_bwd.into")
+        assert into.numel() == D
+        dg = into
+    else:
+        dg = torch.empty(D, dtype=torch.float32, device=x.device)
+    nbytes = _ext("tadx_rmsnorm_bwd_workspace_bytes")(rows, D)
+    ws = workspace(nbytes, x.device)
+    with _timed("rmsnorm_bwd", 0.0, rows * D * (dy.element_size() + 4.0 + 4.0 + (4.0 if dres is not None else 0.0) + (2.0 if want_op16 else 0.0))):
+        check(_ext("tadx_rmsnorm_bwd")(dy.data_ptr(), _dt(dy), x.data_ptr(), gamma.data_ptr(), rrms.data_ptr(), _p(dres), dx.data_ptr(), _p(dx16),
+                                       TAD_F16 if op == torch.float16 else TAD_BF16, dg.data_ptr(), int(into is not None), ws.data_ptr(),
+                                       ws.numel(), rows, D, _stream()), "tadx_rmsnorm_bwd")
+    return dx, dx16, dg
+
+
+def qk_rmsnorm_fwd(qkv32, gq, gk, eps: float, q_out_scale: float = 1.0, dtype=None, save_stats=True):
+    """qkv32 [M,3A] f32 -> qkv16 [M,3A]: q * rq * gq * q_out_scale | k * rk * gk | v, each rounded once; rr [M,2] = (rq, rk) | None.
+    q_out_scale: the q contract of attn_fwd (q_prescale_of(scale) for pre-scaled q, else 1)."""
+    _req(qkv32, torch.float32, "qk_rmsnorm.qkv32")
+    _req(gq, torch.float32, "qk_rmsnorm.gq")
+    _req(gk, torch.float32, "qk_rmsnorm.gk")
+    M, A3 = qkv32.shape
+    A = A3 // 3
+    assert A * 3 == A3 and gq.numel() == A and gk.numel() == A
+    out = torch.empty((M, A3), dtype=dtype or _op16, device=qkv32.device)
+    op = _req16(out, "qk_rmsnorm.out")
+    rr = torch.empty((M, 2), dtype=torch.float32, device=qkv32.device) if save_stats else None
+    with _timed("qk_rmsnorm_fwd", 0.0, M * A3 * 6.0):
+        check(_ext("tadx_qk_rmsnorm_fwd")(qkv32.data_ptr(), gq.data_ptr(), gk.data_ptr(), out.data_ptr(), _dt(out), _p(rr), float(q_out_scale),
+                                          M, A, float(eps), _stream()), "tadx_qk_rmsnorm_fwd")
+    return out, rr
+
+
+def qk_rmsnorm_bwd(dqkv16, qkv32, gq, gk, rr, q_out_scale: float = 1.0, into=None):
+    """attn_bwd's dqkv [M,3A] back through the two norms: returns the 16-bit gradient of the qkv Linear's output, dgq, dgk.
+    into = (dgq, dgk): existing f32 [A] tensors the gamma gradients are ADDED to."""
+    op = _req16(dqkv16, "qk_rmsnorm_bwd.dqkv16")
+    _req(qkv32, torch.float32, "qk_rmsnorm_bwd.qkv32")
+    _req(gq, torch.float32, "qk_rmsnorm_bwd.gq")
+    _req(gk, torch.float32, "qk_rmsnorm_bwd.gk")
+    _req(rr, torch.float32, "qk_rmsnorm_bwd.rr")
+    M, A3 = qkv32.shape
+    A = A3 // 3
+    assert A * 3 == A3 and dqkv16.numel() == qkv32.numel() and rr.numel() == 2 * M and gq.numel() == A and gk.numel() == A
+    out = torch.empty((M, A3), dtype=op, device=qkv32.device)
+    if into is not None:
+        dgq, dgk = into
+        for t in into:
+            _req(t, torch.float32, "qk_rmsnorm_bwd.into")
+            assert t.numel() == A
+    else:
+        dgq = torch.empty(A, dtype=torch.float32, device=qkv32.device)
+        dgk = torch.empty(A, dtype=torch.float32, device=qkv32.device)
+    nbytes = _ext("tadx_qk_rmsnorm_bwd_workspace_bytes")(M, A)
+    ws = workspace(nbytes, qkv32.device)
+    with _timed("qk_rmsnorm_bwd", 0.0, M * A3 * 8.0 - M * A * 4.0):
+        check(_ext("tadx_qk_rmsnorm_bwd")(dqkv16.data_ptr(), _dt(dqkv16), qkv32.data_ptr(), gq.data_ptr(), gk.data_ptr(), rr.data_ptr(),
+                                          float(q_out_scale), out.data_ptr(), dgq.data_ptr(), dgk.data_ptr(), int(into is not None),
+                                          ws.data_ptr(), ws.numel(), M, A, _stream()), "tadx_qk_rmsnorm_bwd")
+    return out, dgq, dgk
+
+
 # ----------------------------------------------------------------------------- linear
 def linear_fwd(x, w, bias=None, out_dtype=None, epilogue=EPI_BIAS, want_preact=False, residual=None, gamma=None,
                rowscale=None, rows_per_scale=1):

@@ -697,7 +697,9 @@ class MlpFn(_Fn):
         _need_gpu(x, "Mlp")
         shp = x.shape
         train = _differentiated(ctx)
-        xb = K.cast_bf16(_f32c(x).reshape(-1, shp[-1]))
+        # (an input that already is the 16-bit operand -- RMSNormFn's out16 -- is read as it is, and gets its gradient in that format)
+        ctx.x16 = x.dtype == K.operand_dtype()
+        xb = _op16_rows(x)
         a, h = K.linear_fwd(xb, w_bf16(fc1_w, train), _f32c(fc1_b), out_dtype=None, epilogue=EPI_BIAS_GELU, want_preact=train)
         y, _ = K.linear_fwd(a, w_bf16(fc2_w, train), _f32c(fc2_b), out_dtype=torch.float32)
         ctx.need = _needs(ctx, 5)
@@ -714,9 +716,186 @@ class MlpFn(_Fn):
         dyb = K.cast_bf16(_f32c(dy).reshape(-1, dy.shape[-1]))
         dh = K.linear_bwd_input(dyb, wT_bf16(fc2_w, True), gelu_preact=h)
         dW2, db2 = linear_dw(dyb, a, fc2_w, ctx.biases[1], need=ctx.need[3:5])
-        dx = K.linear_bwd_input(dh, wT_bf16(fc1_w, True), out_dtype=torch.float32)
+        dx = K.linear_bwd_input(dh, wT_bf16(fc1_w, True), out_dtype=None if ctx.x16 else torch.float32)
         dW1, db1 = linear_dw(dh, xb, fc1_w, ctx.biases[0], need=ctx.need[1:3])
         return dx.reshape(shp), dW1, db1, dW2, db2
+
+
+# --------------------------------------------------------------------------- InternVideo2: RMSNorm, attention with q / k normalisation
+# (other_models/InternVideo2_single_modality/models/internvideo2.py; kernels: csrc/rmsnorm.hip through the extension ABI)
+_iv2_kernels = True
+
+
+def set_iv2_kernels(enabled: bool):
+    """A/B switch: the two norms of the InternVideo2 family (RMSNormFn, the q / k normalisation inside IV2AttentionFn) through their HIP
+    kernels (default) or, off, through the torch expressions of the same arithmetic.  Everything else -- Linears, attention, what is
+    saved -- is unchanged.  Sampled by each forward; a node's backward follows its own forward."""
+    global _iv2_kernels
+    _iv2_kernels = bool(enabled)
+
+
+def get_iv2_kernels() -> bool:
+    return _iv2_kernels
+
+
+def require_attn_head_dim(hd: int):
+    """the refusal of _attn_fwd_core, for callers that must give it before any other work (an InternVideo2 block: before its first norm)"""
+    if hd not in (64, 80):
+        raise TadError(f"attention: head_dim {hd} has no kernel (64 and 80 do)")
+
+
+_q_cols = {}  # (A, factor, device) -> f32 [3A]: the factor on the q third, ones elsewhere (the cast of an un-normalised qkv, IV2AttentionFn)
+
+
+def _q_scale_column(A: int, s: float, device):
+    key = (A, float(s), str(device))
+    col = _q_cols.get(key)
+    if col is None:
+        col = torch.ones(3 * A, dtype=torch.float32, device=device)
+        col[:A] = s
+        _q_cols[key] = col
+    return col
+
+
+def _iv2_no_precise(what: str):
+    if _PRECISION == "precise":
+        raise TadError(f'{what}: precision "precise" has no route for the InternVideo2 family (use "fast" or "half")')
+
+
+def _op16_rows(x):
+    """x [..., C] as 16-bit operand rows [M, C]: as it is when it already has the operand format, else cast from f32"""
+    if x.dtype == K.operand_dtype():
+        x = x.detach().reshape(-1, x.shape[-1])
+        return x if x.is_contiguous() else x.contiguous()
+    return K.cast_bf16(_f32c(x).reshape(-1, x.shape[-1]))
+
+
+def _rms_torch_fwd(x, g, eps):
+    rr = torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps)
+    return x * rr * g, rr
+
+
+def _rms_torch_bwd(dy, x, g, rr):
+    xh, t = x * rr, dy * g
+    return rr * (t - xh * (t * xh).mean(-1, keepdim=True)), (dy * xh).sum(0)
+
+
+class RMSNormFn(_Fn):
+    """RMSNorm.forward (internvideo2.py:119-130) on f32 rows: weight * x * rsqrt(mean(x^2) + eps).  out16: the result is the 16-bit
+    operand of the Linear behind it (and the gradient arrives in that format), else f32."""
+
+    @staticmethod
+    def forward(ctx, x, weight, eps, out16=False):
+        _need_gpu(x, "RMSNorm")
+        _iv2_no_precise("RMSNorm")
+        xc, w = _f32c(x), _f32c(weight)
+        D = xc.shape[-1]
+        x2 = xc.reshape(-1, D)
+        train = _differentiated(ctx)
+        ctx.kernels = _iv2_kernels
+        out_dtype = K.operand_dtype() if out16 else torch.float32
+        if ctx.kernels:
+            y, rr = K.rmsnorm_fwd(x2, w, eps, out_dtype=out_dtype, save_stats=train)
+        else:
+            y, rr = _rms_torch_fwd(x2, w, eps)
+            y = y.to(out_dtype)
+        ctx.need = _needs(ctx, 2)
+        ctx.weight = weight
+        if train:
+            ctx.save_for_backward(x2, w, rr)
+        return y.reshape(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, w, rr = ctx.saved_tensors
+        D = x2.shape[-1]
+        dy2 = dy.detach().reshape(-1, D)
+        dy2 = dy2 if dy2.is_contiguous() else dy2.contiguous()
+        if not ctx.kernels:
+            dx, dg = _rms_torch_bwd(dy2.float(), x2, w, rr)
+            return dx.reshape(dy.shape), (dg if ctx.need[1] else None), None, None
+        ent = _sink(ctx.weight) if ctx.need[1] else None
+        dx, _, dg = K.rmsnorm_bwd(dy2, x2, w, rr, into=None if ent is None else ent[1])
+        if ent is not None:
+            if ent[2] is not None:
+                ent[2](ctx.weight)
+            dg = None
+        return dx.reshape(dy.shape), (dg if ctx.need[1] else None), None, None
+
+
+class IV2AttentionFn(_Fn):
+    """Attention.forward of InternVideo2 (internvideo2.py:151-219): the qkv Linear (one bias [3A] or none) to f32, RMS normalisation of q
+    and k over the full H*d width (gq / gk; None: qk_normalization off), space-time attention, proj.  The softmax scale's q contract
+    (get_attn_q_prescale) rides in the normalisation kernel: the norm comes after the Linear, so the Linear's epilogue cannot carry it.
+    x: f32, or the 16-bit operand itself (then dx has that format too)."""
+
+    @staticmethod
+    def forward(ctx, x, qkv_w, qkv_b, gq, gk, proj_w, proj_b, H, scale, eps):
+        _need_gpu(x, "Attention")
+        _iv2_no_precise("Attention")
+        B, N, C = x.shape
+        hd = head_dim_of(qkv_w, H)
+        require_attn_head_dim(hd)
+        if (gq is None) != (gk is None):
+            raise TadError("Attention: q_norm and k_norm come together")
+        train = _differentiated(ctx)
+        ctx.x16 = x.dtype == K.operand_dtype()
+        ctx.kernels = _iv2_kernels
+        ctx.qpre = _attn_q_prescale
+        s = K.q_prescale_of(scale) if ctx.qpre else 1.0
+        A = H * hd
+        xb = _op16_rows(x)
+        qkv32, _ = K.linear_fwd(xb, w_bf16(qkv_w, train), _f32c(qkv_b), out_dtype=torch.float32)
+        rr = g0 = g1 = None
+        if gq is None:
+            # no normalisation: the cast to the operand format carries the q contract
+            qkv = K.scale_cast_op16(qkv32, gamma=None if s == 1.0 else _q_scale_column(A, s, x.device))
+            qkv32 = None
+        else:
+            g0, g1 = _f32c(gq), _f32c(gk)
+            if ctx.kernels:
+                qkv, rr = K.qk_rmsnorm_fwd(qkv32, g0, g1, eps, q_out_scale=s, save_stats=train)
+            else:
+                q, k, v = qkv32.split(A, dim=1)
+                (qn, rq), (kn, rk) = _rms_torch_fwd(q, g0, eps), _rms_torch_fwd(k, g1, eps)
+                qkv = torch.cat((qn * s, kn, v), dim=1).to(K.operand_dtype())
+                rr = torch.cat((rq, rk), dim=1).contiguous()
+        r = K.attn_fwd(qkv, B, N, H, scale, out_dtype=None, want_lse=train, want_lo=train and _attn_exact_delta, q_prescaled=ctx.qpre, d=hd)
+        ao, lse, ao_lo = r[0], r[1], (r[2] if len(r) > 2 else None)
+        y, _ = K.linear_fwd(ao, w_bf16(proj_w, train), _f32c(proj_b), out_dtype=torch.float32)
+        ctx.need = _needs(ctx, 7)
+        if train:
+            ctx.save_for_backward(xb if ctx.need[1] else None, qkv32, qkv, ao, lse, ao_lo, rr, g0, g1, qkv_w, proj_w)
+        ctx.meta = (B, N, H, hd, scale, s)
+        ctx.params = (qkv_b, gq, gk, proj_b)
+        return y.reshape(B, N, -1)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xb, qkv32, qkv, ao, lse, ao_lo, rr, g0, g1, qkv_w, proj_w = ctx.saved_tensors
+        B, N, H, hd, scale, s = ctx.meta
+        qkv_b, gq, gk, proj_b = ctx.params
+        A = H * hd
+        dyb = K.cast_bf16(_f32c(dy).reshape(B * N, -1))
+        d_ao = K.linear_bwd_input(dyb, wT_bf16(proj_w, True))
+        dWp, dbp = linear_dw(dyb, ao, proj_w, proj_b, need=ctx.need[5:7])
+        # (the q slot is the gradient of the plain q under either contract: of the normalised q here, s not applied -- tad_mi355x_ext.h)
+        dqkv = K.attn_bwd(qkv, ao, d_ao, lse, B, N, H, scale, out_lo=ao_lo, q_prescaled=ctx.qpre, d=hd)
+        dgq = dgk = None
+        if gq is not None:
+            if ctx.kernels:
+                dqkv, dgq, dgk = K.qk_rmsnorm_bwd(dqkv, qkv32, g0, g1, rr, q_out_scale=s)
+            else:
+                dq, dk, dv = dqkv.float().split(A, dim=1)
+                q, k, _ = qkv32.split(A, dim=1)
+                (dq, dgq), (dk, dgk) = _rms_torch_bwd(dq, q, g0, rr[:, 0:1]), _rms_torch_bwd(dk, k, g1, rr[:, 1:2])
+                dqkv = torch.cat((dq, dk, dv), dim=1).to(dqkv.dtype)
+            dgq, dgk = (dgq if ctx.need[3] else None), (dgk if ctx.need[4] else None)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = K.linear_bwd_input(dqkv, wT_bf16(qkv_w, True), out_dtype=None if ctx.x16 else torch.float32).reshape(B, N, -1)
+        dWqkv, dbqkv = linear_dw(dqkv, xb, qkv_w, qkv_b, need=(ctx.need[1], ctx.need[2] and qkv_b is not None))
+        return dx, dWqkv, dbqkv, dgq, dgk, dWp, dbp, None, None, None
 
 
 # --------------------------------------------------------------------------- fused Block
@@ -1151,6 +1330,36 @@ class LinearFn(_Fn):
         dx = K.linear_bwd_input(dyb, wT_bf16(weight, True), out_dtype=torch.float32) if ctx.needs_input_grad[0] else None
         dW, db = linear_dw(dyb, xb, weight, bias, need=ctx.need[1:3])
         return (None if dx is None else dx.reshape(ctx.shp)), dW, db
+
+
+class LinearSplitFn(_Fn):
+    """nn.Linear on f32 rows through the split-operand GEMMs (hi + lo, three MFMA products: f32-level accuracy) in EVERY precision mode:
+    LinearFn's precise branch as a function of its own.  For the few Linears whose rounding reaches the logits directly -- the
+    attention-pooling head of the InternVideo2 family, where 16-bit operands cost more accuracy than the whole encoder in front of them
+     and the split costs two D x D GEMMs per step."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        _need_gpu(x, "Linear")
+        ctx.params = (weight, bias)
+        ctx.shp = x.shape
+        train = _differentiated(ctx)
+        x2 = _f32c(x).reshape(-1, x.shape[-1])
+        y = precise_linear(x2, weight, bias, fresh=train)
+        ctx.need = _needs(ctx, 3)
+        if train:
+            ctx.save_for_backward(x2 if ctx.need[1] else None)
+        return y.reshape(*x.shape[:-1], -1)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x2,) = ctx.saved_tensors
+        weight, bias = ctx.params
+        dy2 = _f32c(dy).reshape(-1, dy.shape[-1])
+        dx = precise_dx(dy2, weight).reshape(ctx.shp) if ctx.needs_input_grad[0] else None
+        dW = precise_dw(dy2, x2, want_bias=False)[0] if ctx.need[1] else None
+        db = K.colsum_f32(dy2) if (bias is not None and ctx.need[2]) else None
+        return dx, dW, db
 
 
 # --------------------------------------------------------------------------- MAE pre-training path (SURVEY 8f-2)
