@@ -32,7 +32,7 @@ NO_VGPR_FORM = {"gemm_w4.hip"}
 EXTRA_DEPS = {"gemm.hip": ["gemm_kernels.h", "gemm_plan.h"], "gemm_w4.hip": ["gemm_kernels.h", "gemm_plan.h"], "gemm_plan.hip": ["gemm_plan.h", "knob.h"],
               "attn_fwd.hip": ["attn_plan.h"], "attn_bwd.hip": ["attn_plan.h"], "attn_plan.hip": ["attn_plan.h", "knob.h"],
               "multiscale_crop.hip": ["frame_io.h"], "frame_resize.hip": ["frame_io.h"], "spatial_sample.hip": ["frame_io.h"], "randaug.hip": ["frame_io.h"],
-              "rmsnorm.hip": ["../../include/tad_mi355x_ext.h"]}
+              "layernorm.hip": ["rownorm.h"], "rmsnorm.hip": ["rownorm.h", "../../include/tad_mi355x_ext.h"]}
 # ema.hip and mixup.hip must round like torch (a product, a product, a sum: three roundings) and are compiled without FMA contraction;
 # randaug.hip must round like PIL's C code (a float blend, a double affine map and cubic: each product and sum on its own).
 # multiscale_crop.hip writes the same normalised f32 values as randaug.hip's frames_to_clip and takes the same flags.

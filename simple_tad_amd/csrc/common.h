@@ -53,6 +53,17 @@ __device__ __forceinline__ uint32_t pack16x2(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, v);
   }
 }
+// ... and back: the low / high element of a packed pair -> f32.  bf16: the upper half of the f32 pattern; f16: v_cvt_f32_f16.
+template <int FMT>
+__device__ __forceinline__ float lo16_f32(uint32_t w) {
+  if constexpr (FMT == TAD_F16) return (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xffffu));
+  else return __uint_as_float(w << 16);
+}
+template <int FMT>
+__device__ __forceinline__ float hi16_f32(uint32_t w) {
+  if constexpr (FMT == TAD_F16) return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16));
+  else return __uint_as_float(w & 0xffff0000u);
+}
 
 // A uint8 pixel value as the network sees it: ToTensor (u / 255), then tensor_normalize ((v - mean) / std).  Two IEEE divisions and one
 // subtraction, each rounded on its own whatever -ffp-contract says: every kernel that reads uint8 frames writes these bits.
@@ -117,20 +128,8 @@ __device__ __forceinline__ float op16_to_f32(uint16_t v) {
 #endif
 }
 // low / high element of a packed pair
-__device__ __forceinline__ float op16_lo_f32(uint32_t w) {
-#ifdef TAD_OPND_F16
-  return (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xffffu));
-#else
-  return __uint_as_float(w << 16);
-#endif
-}
-__device__ __forceinline__ float op16_hi_f32(uint32_t w) {
-#ifdef TAD_OPND_F16
-  return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16));
-#else
-  return __uint_as_float(w & 0xffff0000u);
-#endif
-}
+__device__ __forceinline__ float op16_lo_f32(uint32_t w) { return lo16_f32<TAD_OP16>(w); }
+__device__ __forceinline__ float op16_hi_f32(uint32_t w) { return hi16_f32<TAD_OP16>(w); }
 __device__ __forceinline__ uint16_t f32_to_op16(float f) { return f32_to_16<TAD_OP16>(f); }
 __device__ __forceinline__ uint32_t pack_op16x2(float lo, float hi) { return pack16x2<TAD_OP16>(lo, hi); }
 

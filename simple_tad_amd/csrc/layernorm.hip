@@ -1,16 +1,11 @@
 // LayerNorm forward / backward for rows of D f32 elements (D % 4 == 0, D <= 2048).
 // HBM-bound: one wave per row, the row lives in registers (float4 per lane per 256 columns),
 // two-pass mean / variance in registers (same numerics as torch: biased variance around the mean),
-// wave reductions by cross-lane shuffles -- no LDS on the forward path.
-#include "common.h"
+// wave reductions by cross-lane shuffles -- no LDS on the forward path.  What this shape shares with rmsnorm.hip (the instance per row
+// width, the dealing of rows to backward blocks, the cross-wave combine, the float4 / 16-bit helpers) is rownorm.h.
+#include "rownorm.h"
 
 TAD_NAMESPACE_BEGIN
-
-constexpr int LN_MAX_V = 8;  // float4 per lane -> D <= 64*4*8 = 2048
-
-int launch_reduce_partials(const float* partial, float* out, int splits, int64_t n, int accumulate, hipStream_t st);
-int launch_reduce_cols(const float* partial, float* out0, float* out1, float* out2, int nq, int splits, int n, int accumulate,
-                       hipStream_t st);
 
 template <int NV, bool OUT_BF16>
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
@@ -27,7 +22,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = lane + 64 * i;
-    v[i] = (c < D4) ? ldg_f4<false>(xr + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    v[i] = (c < D4) ? ldg_f4<false>(xr + c) : zero4();
     s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
   }
   const float mu = wave_sum(s) / (float)D;
@@ -57,9 +52,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
       o.z = (v[i].z - mu) * rs * g.z + b.z;
       o.w = (v[i].w - mu) * rs * g.w + b.w;
       if (OUT_BF16) {
-        uint2 p;
-        p.x = pack_op16x2(o.x, o.y);
-        p.y = pack_op16x2(o.z, o.w);
+        const uint2 p = pack16x4<TAD_OP16>(o);
         stg_u2<false>(reinterpret_cast<uint2*>((uint16_t*)y + row * D) + c, p);
       } else {
         stg_f4<false>(reinterpret_cast<float4*>((float*)y + row * D) + c, o);
@@ -70,7 +63,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
 
 // Backward.  Each block owns a contiguous chunk of rows; each wave walks rows of the chunk with stride 4 and keeps
 // per-lane column partials of dgamma, dbeta and (optionally) colsum(dx) in registers; they are combined across the
-// block's 4 waves in LDS and written as one partial row per block -> reduced by reduce_partials_kernel.
+// block's 4 waves in LDS and written as one partial row per block and quantity (rownorm_combine) -> reduced by launch_reduce_cols.
 // FULL: D == 256 * NV (768, 1024, 1280, 512 ...): no per-lane column guard, so the row loop is one basic block up to the optional bf16
 // store (the guards split every chunk into its own exec-masked region with its own waits).
 __device__ const float ln_one = 1.0f;
@@ -82,7 +75,6 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restri
                                                             float* __restrict__ partial /*[grid][3][D]*/, int64_t rows, int D,
                                                             int rows_per_block, int want_colsum,
                                                             const float* __restrict__ rowscale, int rows_per_scale) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];  // [4][3][D]
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int D4 = D >> 2;
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
@@ -91,8 +83,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restri
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = lane + 64 * i;
-    g[i] = (c < D4) ? reinterpret_cast<const float4*>(gamma)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-    dg[i] = db[i] = cs[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    g[i] = (c < D4) ? reinterpret_cast<const float4*>(gamma)[c] : zero4();
+    dg[i] = db[i] = cs[i] = zero4();
   }
   // One row per wave and iteration.  Everything the row needs (x, dy, the residual gradient, its statistics and its drop-path scale) is
   // requested in ONE batch at the top -- the first version waited for each 256-column chunk on its own and fetched `dres` only behind
@@ -137,16 +129,15 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restri
     for (int i = 0; i < NV; ++i) {
       const int c = lane + 64 * i;
       if (FULL || c < D4) {
-        if (DY_BF16)
-          dyv[i] = make_float4(op16_lo_f32(dyp[i].x), op16_hi_f32(dyp[i].x), op16_lo_f32(dyp[i].y), op16_hi_f32(dyp[i].y));
+        if (DY_BF16) dyv[i] = unpack16x4<TAD_OP16>(dyp[i]);
         xh[i] = make_float4((xv[i].x - mu) * rs, (xv[i].y - mu) * rs, (xv[i].z - mu) * rs, (xv[i].w - mu) * rs);
-        const float4 t = make_float4(dyv[i].x * g[i].x, dyv[i].y * g[i].y, dyv[i].z * g[i].z, dyv[i].w * g[i].w);
+        const float4 t = mul4(dyv[i], g[i]);
         s1 += (t.x + t.y) + (t.z + t.w);
-        s2 += (t.x * xh[i].x + t.y * xh[i].y) + (t.z * xh[i].z + t.w * xh[i].w);
-        dg[i].x += dyv[i].x * xh[i].x; dg[i].y += dyv[i].y * xh[i].y; dg[i].z += dyv[i].z * xh[i].z; dg[i].w += dyv[i].w * xh[i].w;
-        db[i].x += dyv[i].x; db[i].y += dyv[i].y; db[i].z += dyv[i].z; db[i].w += dyv[i].w;
+        s2 += dot4(t, xh[i]);
+        acc4(dg[i], mul4(dyv[i], xh[i]));
+        acc4(db[i], dyv[i]);
       } else {
-        xh[i] = dyv[i] = rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        xh[i] = dyv[i] = rv[i] = zero4();
       }
     }
     const float c1 = wave_sum_dpp(s1) / (float)D;
@@ -164,53 +155,21 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restri
       const int c = lane + 64 * i;
       if (FULL || c < D4) stg_f4<false>(reinterpret_cast<float4*>(dx + row * D) + c, o[i]);
       // the bf16 copy and the column sums feed the branch Linear, whose output was scaled per sample (drop-path)
-      o[i].x *= sc; o[i].y *= sc; o[i].z *= sc; o[i].w *= sc;
-      if (FULL || c < D4) { cs[i].x += o[i].x; cs[i].y += o[i].y; cs[i].z += o[i].z; cs[i].w += o[i].w; }
+      o[i] = scale4(o[i], sc);
+      if (FULL || c < D4) acc4(cs[i], o[i]);
     }
     if (dxb) {
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
         const int c = lane + 64 * i;
         if (FULL || c < D4) {
-          uint2 p;
-          p.x = pack_op16x2(o[i].x, o[i].y);
-          p.y = pack_op16x2(o[i].z, o[i].w);
+          const uint2 p = pack16x4<TAD_OP16>(o[i]);
           stg_u2<false>(reinterpret_cast<uint2*>(dxb + row * D) + c, p);
         }
       }
     }
   }
-  // cross-wave combine
-  float4* sm = reinterpret_cast<float4*>(smem);  // [wave][3][D4]
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int c = lane + 64 * i;
-    if (c < D4) {
-      sm[(wave * 3 + 0) * D4 + c] = dg[i];
-      sm[(wave * 3 + 1) * D4 + c] = db[i];
-      sm[(wave * 3 + 2) * D4 + c] = cs[i];
-    }
-  }
-  __syncthreads();
-  const int nq = want_colsum ? 3 : 2;
-  for (int idx = threadIdx.x; idx < nq * D4; idx += 256) {
-    const int q = idx / D4, c = idx - q * D4;
-    float4 a = sm[(0 * 3 + q) * D4 + c];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      const float4 b = sm[(w * 3 + q) * D4 + c];
-      a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-    }
-    // partial layout: [q][grid][D] so each quantity can be reduced with reduce_partials_kernel
-    reinterpret_cast<float4*>(partial + ((int64_t)q * gridDim.x + blockIdx.x) * D)[c] = a;
-  }
-}
-
-static inline int ln_bwd_blocks(int64_t rows) {
-  int64_t b = (rows + 31) / 32;  // >= 32 rows per block
-  if (b > 1024) b = 1024;
-  if (b < 1) b = 1;
-  return (int)b;
+  rownorm_combine<NV>(partial, D, want_colsum ? 3 : 2, wave, dg, db, cs);
 }
 
 TAD_NAMESPACE_END
@@ -222,15 +181,13 @@ extern "C" {
 int tad_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* y, int y_dtype, float* mean, float* rstd,
                       int64_t rows, int D, float eps, tad_stream_t stream) {
   TAD_REQUIRE(x && gamma && beta && y, "layernorm_fwd: null pointer");
-  TAD_REQUIRE(rows > 0 && D > 0 && D % 4 == 0 && D <= 64 * 4 * LN_MAX_V, "layernorm_fwd: D=%d must be a multiple of 4 and <= %d", D,
-              64 * 4 * LN_MAX_V);
+  TAD_REQUIRE(rows > 0 && rownorm_width_ok(D), "layernorm_fwd: D=%d must be a multiple of 4 and <= %d", D, ROWNORM_MAX_D);
   TAD_REQUIRE(y_dtype == TAD_F32 || y_dtype == TAD_OP16, "layernorm_fwd: bad y_dtype %d", y_dtype);
   // float4 loads of x, gamma and beta; y: float4 stores (f32) or 8-byte packed stores (16-bit); mean and rstd are written float by float
   TAD_REQUIRE_ALIGNED("layernorm_fwd", x, 16);
   TAD_REQUIRE_ALIGNED("layernorm_fwd", gamma, 16);
   TAD_REQUIRE_ALIGNED("layernorm_fwd", beta, 16);
   TAD_REQUIRE_ALIGNED("layernorm_fwd", y, y_dtype == TAD_F32 ? 16 : 8);
-  const int nv = (D / 4 + 63) / 64;
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   hipStream_t st = (hipStream_t)stream;
 #define LN_FWD(NV)                                                                                                          \
@@ -238,21 +195,13 @@ int tad_layernorm_fwd(const float* x, const float* gamma, const float* beta, voi
     hipLaunchKernelGGL((layernorm_fwd_kernel<NV, true>), grid, block, 0, st, x, gamma, beta, y, mean, rstd, rows, D, eps); \
   else                                                                                                                      \
     hipLaunchKernelGGL((layernorm_fwd_kernel<NV, false>), grid, block, 0, st, x, gamma, beta, y, mean, rstd, rows, D, eps);
-  switch (nv) {
-    case 1: LN_FWD(1); break;
-    case 2: LN_FWD(2); break;
-    case 3: LN_FWD(3); break;
-    case 4: LN_FWD(4); break;
-    case 5: LN_FWD(5); break;
-    case 6: LN_FWD(6); break;
-    default: LN_FWD(8); break;
-  }
+  ROWNORM_SWITCH_NV(rownorm_nv(D), LN_FWD)
 #undef LN_FWD
   return check_launch("layernorm_fwd");
 }
 
 #ifndef TAD_OPND_F16  // format-independent: one copy for the library (bf16 pass)
-size_t tad_layernorm_bwd_workspace_bytes(int64_t rows, int D) { return (size_t)3 * ln_bwd_blocks(rows) * (size_t)D * sizeof(float); }
+size_t tad_layernorm_bwd_workspace_bytes(int64_t rows, int D) { return rownorm_bwd_plan(rows, D, 3).partial_floats * sizeof(float); }
 #endif
 
 int tad_layernorm_bwd(const void* dy, int dy_dtype, const float* x, const float* gamma, const float* mean, const float* rstd,
@@ -260,7 +209,7 @@ int tad_layernorm_bwd(const void* dy, int dy_dtype, const float* x, const float*
                       const float* rowscale, int rows_per_scale, int accumulate, void* ws, size_t ws_bytes, int64_t rows, int D,
                       tad_stream_t stream) {
   TAD_REQUIRE(dy && x && gamma && mean && rstd && dx && dgamma && dbeta && ws, "layernorm_bwd: null pointer");
-  TAD_REQUIRE(rows > 0 && D > 0 && D % 4 == 0 && D <= 64 * 4 * LN_MAX_V, "layernorm_bwd: unsupported D=%d", D);
+  TAD_REQUIRE(rows > 0 && rownorm_width_ok(D), "layernorm_bwd: unsupported D=%d", D);
   TAD_REQUIRE(dy_dtype == TAD_F32 || dy_dtype == TAD_OP16, "layernorm_bwd: bad dy_dtype %d", dy_dtype);
   TAD_REQUIRE(!rowscale || rows_per_scale > 0, "layernorm_bwd: rows_per_scale must be positive");
   // float4 accesses to every row operand, the partials in ws and (in the reduction) dgamma / dbeta / colsum_dx; 8-byte pieces of the 16-bit
@@ -275,36 +224,25 @@ int tad_layernorm_bwd(const void* dy, int dy_dtype, const float* x, const float*
   TAD_REQUIRE_ALIGNED("layernorm_bwd", dbeta, 16);
   TAD_REQUIRE_ALIGNED("layernorm_bwd", colsum_dx, 16);
   TAD_REQUIRE_ALIGNED("layernorm_bwd", ws, 16);
-  const int blocks = ln_bwd_blocks(rows);
-  if (ws_bytes < (size_t)3 * blocks * D * sizeof(float)) { set_error("layernorm_bwd: workspace too small"); return TAD_ENOSPACE; }
-  const int rows_per_block = (int)((rows + blocks - 1) / blocks);
-  const int nv = (D / 4 + 63) / 64;
-  const size_t smem = (size_t)4 * 3 * D * sizeof(float);
+  const RowNormBwd p = rownorm_bwd_plan(rows, D, 3);
+  if (ws_bytes < p.partial_floats * sizeof(float)) { set_error("layernorm_bwd: workspace too small"); return TAD_ENOSPACE; }
   hipStream_t st = (hipStream_t)stream;
   float* partial = (float*)ws;
   const int want_cs = colsum_dx != nullptr;
-  const bool full = (D == 256 * nv);
-#define LN_BWD_(NV, BF, FULL_)                                                                                                  \
-  hipLaunchKernelGGL((layernorm_bwd_kernel<NV, BF, FULL_>), dim3(blocks), dim3(256), smem, st, dy, x, gamma, mean, rstd, dres, dx, \
-                     dx_bf16, partial, rows, D, rows_per_block, want_cs, rowscale, rows_per_scale)
-#define LN_BWD(NV)                                                                                                             \
-  if (dy_dtype == TAD_OP16) { if (full) LN_BWD_(NV, true, true); else LN_BWD_(NV, true, false); }                               \
-  else { if (full) LN_BWD_(NV, false, true); else LN_BWD_(NV, false, false); }
-  switch (nv) {
-    case 1: LN_BWD(1); break;
-    case 2: LN_BWD(2); break;
-    case 3: LN_BWD(3); break;
-    case 4: LN_BWD(4); break;
-    case 5: LN_BWD(5); break;
-    case 6: LN_BWD(6); break;
-    default: LN_BWD(8); break;
-  }
+#define LN_BWD_(NV, BF, FULL_)                                                                                                        \
+  hipLaunchKernelGGL((layernorm_bwd_kernel<NV, BF, FULL_>), dim3(p.blocks), dim3(256), p.smem_bytes, st, dy, x, gamma, mean, rstd, dres, \
+                     dx, dx_bf16, partial, rows, D, p.rows_per_block, want_cs, rowscale, rows_per_scale)
+#define LN_BWD_F(NV, BF) \
+  if (D == 256 * NV) LN_BWD_(NV, BF, true); else LN_BWD_(NV, BF, false)
+#define LN_BWD(NV) \
+  if (dy_dtype == TAD_OP16) { LN_BWD_F(NV, true); } else { LN_BWD_F(NV, false); }
+  ROWNORM_SWITCH_NV(rownorm_nv(D), LN_BWD)
 #undef LN_BWD
+#undef LN_BWD_F
 #undef LN_BWD_
   int rc = check_launch("layernorm_bwd");
   if (rc) return rc;
-  rc = launch_reduce_cols(partial, dgamma, dbeta, colsum_dx, colsum_dx ? 3 : 2, blocks, D, accumulate ? 1 : 0, st);
-  return rc;
+  return launch_reduce_cols(partial, dgamma, dbeta, colsum_dx, colsum_dx ? 3 : 2, p.blocks, D, accumulate ? 1 : 0, st);
 }
 
 }  // extern "C"

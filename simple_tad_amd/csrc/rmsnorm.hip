@@ -1,48 +1,13 @@
 // RMSNorm forward / backward for rows of D f32 elements (D % 4 == 0, D <= 2048), and the RMS normalisation of the q and k thirds of a
 // qkv row over their full H*d width (InternVideo2's qk_normalization): the extension ABI of include/tad_mi355x_ext.h (tadx_*).
-// Same shape as layernorm.hip: HBM-bound, one wave per row, the row lives in registers (float4 per lane per 256 columns) and is read
-// once, wave reductions by cross-lane steps, per-block column partials of the gamma gradients reduced in a fixed order (no atomics).
+// Same shape as layernorm.hip, and what the two share is one copy in rownorm.h: the instance per row width (ROWNORM_SWITCH_NV), the
+// dealing of rows to backward blocks, the cross-wave combine into per-block column partials and the float4 / 16-bit helpers.
 // Compiled ONCE: the 16-bit format of an operand is a run-time argument (TAD_BF16 / TAD_F16) that selects a template instance, so there
 // are no _f16 twins.
-#include "common.h"
+#include "rownorm.h"
 #include "../../include/tad_mi355x_ext.h"
 
 TAD_NAMESPACE_BEGIN
-
-constexpr int RMS_MAX_V = 8;  // float4 per lane -> D <= 64*4*8 = 2048
-
-int launch_reduce_cols(const float* partial, float* out0, float* out1, float* out2, int nq, int splits, int n, int accumulate,
-                       hipStream_t st);
-
-// a packed pair of 16-bit values of format FMT -> f32 (the run-time-format counterparts of op16_lo_f32 / op16_hi_f32)
-template <int FMT>
-__device__ __forceinline__ float lo16_f32(uint32_t w) {
-  if constexpr (FMT == TAD_F16) return (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xffffu));
-  else return __uint_as_float(w << 16);
-}
-template <int FMT>
-__device__ __forceinline__ float hi16_f32(uint32_t w) {
-  if constexpr (FMT == TAD_F16) return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16));
-  else return __uint_as_float(w & 0xffff0000u);
-}
-template <int FMT>
-__device__ __forceinline__ float4 unpack16x4(const uint2& p) {
-  return make_float4(lo16_f32<FMT>(p.x), hi16_f32<FMT>(p.x), lo16_f32<FMT>(p.y), hi16_f32<FMT>(p.y));
-}
-// round-to-nearest-even, a NaN stays a NaN (pack16x2, common.h)
-template <int FMT>
-__device__ __forceinline__ uint2 pack16x4(const float4& o) {
-  uint2 p;
-  p.x = pack16x2<FMT>(o.x, o.y);
-  p.y = pack16x2<FMT>(o.z, o.w);
-  return p;
-}
-__device__ __forceinline__ float sumsq4(const float4& v) { return (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w); }
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
-__device__ __forceinline__ float4 mul4(const float4& a, const float4& b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-__device__ __forceinline__ float4 scale4(const float4& a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
-__device__ __forceinline__ void acc4(float4& a, const float4& b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
 // y = x * rsqrt(mean(x^2) + eps) * gamma.  YFMT: TAD_F32 / TAD_BF16 / TAD_F16.  Four rows per block, one per wave.
 template <int NV, int YFMT>
@@ -80,13 +45,34 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const float* __restric
 // unchanged); without a residual gradient the row of x is read a second time and multiplied by 0 so that the loads stay one block.
 //   xh = x * rrms, t = dy * gamma:  dx = rrms * (t - xh * mean(t * xh)) (+ dres),  dgamma = sum_rows dy * xh
 // An all-zero row: xh = 0, so dx = rrms * dy * gamma, finite.
+// One float4 chunk of that gradient, on either side of the wave sum of s; both backward kernels are made of these two.  The first half
+// takes one norm (rmsnorm_bwd_kernel) or two (q and k) and walks them stage by stage, the order in which the q / k kernel has always
+// interleaved its two chains: the compiler's choice of which product of a sum it fuses follows the statement order, and with it the bits.
+struct RmsChunk {
+  float4& xh;       // out: x * r (may be x itself)
+  float4& t;        // out: dy * g
+  const float4& x;
+  const float4& dy;
+  const float4& g;
+  float r;          // the row's rrms
+  float& s;         // += t . xh
+  float4& dg;       // += dy * xh
+};
+template <typename... C>
+__device__ __forceinline__ void rms_grad_chunk(const C&... n) {
+  ((n.xh = scale4(n.x, n.r)), ...);
+  ((n.t = mul4(n.dy, n.g)), ...);
+  ((n.s += dot4(n.t, n.xh)), ...);
+  (acc4(n.dg, mul4(n.dy, n.xh)), ...);
+}
+__device__ __forceinline__ float rms_grad_dx(float t, float xh, float r, float c /* mean(t * xh) */) { return r * (t - xh * c); }
+
 template <int NV, int DYFMT, bool FULL>
 __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const void* __restrict__ dy, const float* __restrict__ x,
                                                           const float* __restrict__ gamma, const float* __restrict__ rrms,
                                                           const float* __restrict__ dres, float* __restrict__ dx,
                                                           uint16_t* __restrict__ dx16, int dx16_fmt, float* __restrict__ partial /*[grid][D]*/,
                                                           int64_t rows, int D, int rows_per_block) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];  // [4][D]
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int D4 = D >> 2;
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
@@ -122,10 +108,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const void* __restrict
       const int c = lane + 64 * i;
       if (FULL || c < D4) {
         if constexpr (DYFMT != TAD_F32) dyv[i] = unpack16x4<DYFMT>(dyp[i]);
-        xh[i] = scale4(xv[i], rr);
-        t[i] = mul4(dyv[i], g[i]);
-        s2 += dot4(t[i], xh[i]);
-        acc4(dg[i], mul4(dyv[i], xh[i]));
+        rms_grad_chunk(RmsChunk{xh[i], t[i], xv[i], dyv[i], g[i], rr, s2, dg[i]});
       } else {
         xh[i] = t[i] = rv[i] = zero4();
       }
@@ -134,10 +117,10 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const void* __restrict
     float4 o[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      o[i].x = fmaf(rv[i].x, rmul, rr * (t[i].x - xh[i].x * c2));
-      o[i].y = fmaf(rv[i].y, rmul, rr * (t[i].y - xh[i].y * c2));
-      o[i].z = fmaf(rv[i].z, rmul, rr * (t[i].z - xh[i].z * c2));
-      o[i].w = fmaf(rv[i].w, rmul, rr * (t[i].w - xh[i].w * c2));
+      o[i].x = fmaf(rv[i].x, rmul, rms_grad_dx(t[i].x, xh[i].x, rr, c2));
+      o[i].y = fmaf(rv[i].y, rmul, rms_grad_dx(t[i].y, xh[i].y, rr, c2));
+      o[i].z = fmaf(rv[i].z, rmul, rms_grad_dx(t[i].z, xh[i].z, rr, c2));
+      o[i].w = fmaf(rv[i].w, rmul, rms_grad_dx(t[i].w, xh[i].w, rr, c2));
     }
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -153,20 +136,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const void* __restrict
       }
     }
   }
-  // cross-wave combine, one partial row per block
-  float4* sm = reinterpret_cast<float4*>(smem);  // [wave][D4]
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int c = lane + 64 * i;
-    if (c < D4) sm[wave * D4 + c] = dg[i];
-  }
-  __syncthreads();
-  for (int c = threadIdx.x; c < D4; c += 256) {
-    float4 a = sm[c];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) acc4(a, sm[w * D4 + c]);
-    reinterpret_cast<float4*>(partial + (int64_t)blockIdx.x * D)[c] = a;
-  }
+  rownorm_combine<NV>(partial, D, 1, wave, dg);
 }
 
 // One pass over a qkv row [3A] f32: q third -> q * rq * gq * q_out_scale, k third -> k * rk * gk, v third cast; all rounded once to FMT.
@@ -222,7 +192,6 @@ __global__ __launch_bounds__(256) void qk_rmsnorm_bwd_kernel(const uint16_t* __r
                                                              const float* __restrict__ gq, const float* __restrict__ gk,
                                                              const float* __restrict__ rr, uint16_t* __restrict__ dpre16,
                                                              float* __restrict__ partial, int64_t M, int A, int rows_per_block) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];  // [4][2][A]
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int A4 = A >> 2;
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
@@ -261,14 +230,7 @@ __global__ __launch_bounds__(256) void qk_rmsnorm_bwd_kernel(const uint16_t* __r
       const int c = lane + 64 * i;
       if (c < A4) {
         const float4 dq = unpack16x4<FMT>(pq[i]), dk = unpack16x4<FMT>(pk[i]);
-        q[i] = scale4(q[i], rq);  // xh
-        k[i] = scale4(k[i], rk);
-        tq[i] = mul4(dq, g0[i]);
-        tk[i] = mul4(dk, g1[i]);
-        sq += dot4(tq[i], q[i]);
-        sk += dot4(tk[i], k[i]);
-        acc4(d0[i], mul4(dq, q[i]));
-        acc4(d1[i], mul4(dk, k[i]));
+        rms_grad_chunk(RmsChunk{q[i], tq[i], q[i], dq, g0[i], rq, sq, d0[i]}, RmsChunk{k[i], tk[i], k[i], dk, g1[i], rk, sk, d1[i]});  // q, k become xh
       } else {
         q[i] = k[i] = tq[i] = tk[i] = zero4();
       }
@@ -279,61 +241,24 @@ __global__ __launch_bounds__(256) void qk_rmsnorm_bwd_kernel(const uint16_t* __r
     for (int i = 0; i < NV; ++i) {
       const int c = lane + 64 * i;
       if (c < A4) {
-        const float4 oq = make_float4(rq * (tq[i].x - q[i].x * cq), rq * (tq[i].y - q[i].y * cq), rq * (tq[i].z - q[i].z * cq),
-                                      rq * (tq[i].w - q[i].w * cq));
-        const float4 ok = make_float4(rk * (tk[i].x - k[i].x * ck), rk * (tk[i].y - k[i].y * ck), rk * (tk[i].z - k[i].z * ck),
-                                      rk * (tk[i].w - k[i].w * ck));
+        const float4 oq = make_float4(rms_grad_dx(tq[i].x, q[i].x, rq, cq), rms_grad_dx(tq[i].y, q[i].y, rq, cq),
+                                      rms_grad_dx(tq[i].z, q[i].z, rq, cq), rms_grad_dx(tq[i].w, q[i].w, rq, cq));
+        const float4 ok = make_float4(rms_grad_dx(tk[i].x, k[i].x, rk, ck), rms_grad_dx(tk[i].y, k[i].y, rk, ck),
+                                      rms_grad_dx(tk[i].z, k[i].z, rk, ck), rms_grad_dx(tk[i].w, k[i].w, rk, ck));
         stg_u2<false>(dst + c, pack16x4<FMT>(oq));
         stg_u2<false>(dst + A4 + c, pack16x4<FMT>(ok));
         stg_u2<false>(dst + 2 * A4 + c, pv[i]);
       }
     }
   }
-  float4* sm = reinterpret_cast<float4*>(smem);  // [wave][2][A4]
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int c = lane + 64 * i;
-    if (c < A4) {
-      sm[(wave * 2 + 0) * A4 + c] = d0[i];
-      sm[(wave * 2 + 1) * A4 + c] = d1[i];
-    }
-  }
-  __syncthreads();
-  for (int idx = threadIdx.x; idx < 2 * A4; idx += 256) {
-    const int qn = idx / A4, c = idx - qn * A4;
-    float4 a = sm[qn * A4 + c];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) acc4(a, sm[(w * 2 + qn) * A4 + c]);
-    // partial layout: [q][grid][A], one quantity per reduce_cols row block
-    reinterpret_cast<float4*>(partial + ((int64_t)qn * gridDim.x + blockIdx.x) * A)[c] = a;
-  }
+  rownorm_combine<NV>(partial, A, 2, wave, d0, d1);
 }
 
-static inline int rms_bwd_blocks(int64_t rows) {
-  int64_t b = (rows + 31) / 32;  // >= 32 rows per block
-  if (b > 1024) b = 1024;
-  if (b < 1) b = 1;
-  return (int)b;
-}
 static inline bool is_op16(int fmt) { return fmt == TAD_BF16 || fmt == TAD_F16; }
 
 TAD_NAMESPACE_END
 
 using namespace tad;
-
-// One instance per float4 count: the kernels' NV must be the row's own (D / 256 rounded up), because the backward's FULL variant drops the
-// column guard on the strength of D == 256 * NV.  (nv = 7, D = 1792: an NV = 8 instance would run its eighth chunk into the next row.)
-#define RMS_SWITCH_NV(nv, M_) \
-  switch (nv) {               \
-    case 1: M_(1); break;     \
-    case 2: M_(2); break;     \
-    case 3: M_(3); break;     \
-    case 4: M_(4); break;     \
-    case 5: M_(5); break;     \
-    case 6: M_(6); break;     \
-    case 7: M_(7); break;     \
-    default: M_(8); break;    \
-  }
 
 extern "C" {
 
@@ -342,14 +267,12 @@ int tadx_abi_version(void) { return TADX_ABI_VERSION; }
 int tadx_rmsnorm_fwd(const float* x, const float* gamma, void* y, int y_dtype, float* rrms, int64_t rows, int D, float eps,
                      tad_stream_t stream) {
   TAD_REQUIRE(x && gamma && y, "rmsnorm_fwd: null pointer");
-  TAD_REQUIRE(rows > 0 && D > 0 && D % 4 == 0 && D <= 64 * 4 * RMS_MAX_V, "rmsnorm_fwd: D=%d must be a multiple of 4 and <= %d", D,
-              64 * 4 * RMS_MAX_V);
+  TAD_REQUIRE(rows > 0 && rownorm_width_ok(D), "rmsnorm_fwd: D=%d must be a multiple of 4 and <= %d", D, ROWNORM_MAX_D);
   TAD_REQUIRE(y_dtype == TAD_F32 || is_op16(y_dtype), "rmsnorm_fwd: bad y_dtype %d", y_dtype);
   // float4 loads of x and gamma; y: float4 stores (f32) or 8-byte packed stores (16-bit); rrms is written float by float
   TAD_REQUIRE_ALIGNED("rmsnorm_fwd", x, 16);
   TAD_REQUIRE_ALIGNED("rmsnorm_fwd", gamma, 16);
   TAD_REQUIRE_ALIGNED("rmsnorm_fwd", y, y_dtype == TAD_F32 ? 16 : 8);
-  const int nv = (D / 4 + 63) / 64;
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   hipStream_t st = (hipStream_t)stream;
 #define RMS_FWD_(NV, F) hipLaunchKernelGGL((rmsnorm_fwd_kernel<NV, F>), grid, block, 0, st, x, gamma, y, rrms, rows, D, eps)
@@ -357,20 +280,19 @@ int tadx_rmsnorm_fwd(const float* x, const float* gamma, void* y, int y_dtype, f
   if (y_dtype == TAD_F32) RMS_FWD_(NV, TAD_F32);    \
   else if (y_dtype == TAD_F16) RMS_FWD_(NV, TAD_F16); \
   else RMS_FWD_(NV, TAD_BF16);
-  RMS_SWITCH_NV(nv, RMS_FWD)
+  ROWNORM_SWITCH_NV(rownorm_nv(D), RMS_FWD)
 #undef RMS_FWD
 #undef RMS_FWD_
   return check_launch("rmsnorm_fwd");
 }
 
-size_t tadx_rmsnorm_bwd_workspace_bytes(int64_t rows, int D) { return (size_t)rms_bwd_blocks(rows) * (size_t)D * sizeof(float); }
+size_t tadx_rmsnorm_bwd_workspace_bytes(int64_t rows, int D) { return rownorm_bwd_plan(rows, D, 1).partial_floats * sizeof(float); }
 
 int tadx_rmsnorm_bwd(const void* dy, int dy_dtype, const float* x, const float* gamma, const float* rrms, const float* dres, float* dx,
                      uint16_t* dx16, int dx16_fmt, float* dgamma, int accumulate, void* ws, size_t ws_bytes, int64_t rows, int D,
                      tad_stream_t stream) {
   TAD_REQUIRE(dy && x && gamma && rrms && dx && dgamma && ws, "rmsnorm_bwd: null pointer");
-  TAD_REQUIRE(rows > 0 && D > 0 && D % 4 == 0 && D <= 64 * 4 * RMS_MAX_V, "rmsnorm_bwd: D=%d must be a multiple of 4 and <= %d", D,
-              64 * 4 * RMS_MAX_V);
+  TAD_REQUIRE(rows > 0 && rownorm_width_ok(D), "rmsnorm_bwd: D=%d must be a multiple of 4 and <= %d", D, ROWNORM_MAX_D);
   TAD_REQUIRE(dy_dtype == TAD_F32 || is_op16(dy_dtype), "rmsnorm_bwd: bad dy_dtype %d", dy_dtype);
   TAD_REQUIRE(!dx16 || is_op16(dx16_fmt), "rmsnorm_bwd: bad dx16_fmt %d", dx16_fmt);
   // float4 accesses to every f32 row operand, the partials in ws and (in the reduction) dgamma; 8-byte pieces of the 16-bit tensors;
@@ -383,37 +305,32 @@ int tadx_rmsnorm_bwd(const void* dy, int dy_dtype, const float* x, const float* 
   TAD_REQUIRE_ALIGNED("rmsnorm_bwd", dx16, 8);
   TAD_REQUIRE_ALIGNED("rmsnorm_bwd", dgamma, 16);
   TAD_REQUIRE_ALIGNED("rmsnorm_bwd", ws, 16);
-  const int blocks = rms_bwd_blocks(rows);
-  if (ws_bytes < (size_t)blocks * D * sizeof(float)) { set_error("rmsnorm_bwd: workspace too small"); return TAD_ENOSPACE; }
-  const int rows_per_block = (int)((rows + blocks - 1) / blocks);
-  const int nv = (D / 4 + 63) / 64;
-  const size_t smem = (size_t)4 * D * sizeof(float);
+  const RowNormBwd p = rownorm_bwd_plan(rows, D, 1);
+  if (ws_bytes < p.partial_floats * sizeof(float)) { set_error("rmsnorm_bwd: workspace too small"); return TAD_ENOSPACE; }
   hipStream_t st = (hipStream_t)stream;
   float* partial = (float*)ws;
-  const bool full = (D == 256 * nv);
-#define RMS_BWD_(NV, F, FULL_)                                                                                                    \
-  hipLaunchKernelGGL((rmsnorm_bwd_kernel<NV, F, FULL_>), dim3(blocks), dim3(256), smem, st, dy, x, gamma, rrms, dres, dx, dx16, dx16_fmt, \
-                     partial, rows, D, rows_per_block)
+#define RMS_BWD_(NV, F, FULL_)                                                                                                      \
+  hipLaunchKernelGGL((rmsnorm_bwd_kernel<NV, F, FULL_>), dim3(p.blocks), dim3(256), p.smem_bytes, st, dy, x, gamma, rrms, dres, dx, dx16, \
+                     dx16_fmt, partial, rows, D, p.rows_per_block)
 #define RMS_BWD_F(NV, F) \
-  if (full) RMS_BWD_(NV, F, true); else RMS_BWD_(NV, F, false)
+  if (D == 256 * NV) RMS_BWD_(NV, F, true); else RMS_BWD_(NV, F, false)
 #define RMS_BWD(NV)                                     \
   if (dy_dtype == TAD_F32) { RMS_BWD_F(NV, TAD_F32); }  \
   else if (dy_dtype == TAD_F16) { RMS_BWD_F(NV, TAD_F16); } \
   else { RMS_BWD_F(NV, TAD_BF16); }
-  RMS_SWITCH_NV(nv, RMS_BWD)
+  ROWNORM_SWITCH_NV(rownorm_nv(D), RMS_BWD)
 #undef RMS_BWD
 #undef RMS_BWD_F
 #undef RMS_BWD_
   int rc = check_launch("rmsnorm_bwd");
   if (rc) return rc;
-  return launch_reduce_cols(partial, dgamma, nullptr, nullptr, 1, blocks, D, accumulate ? 1 : 0, st);
+  return launch_reduce_cols(partial, dgamma, nullptr, nullptr, 1, p.blocks, D, accumulate ? 1 : 0, st);
 }
 
 int tadx_qk_rmsnorm_fwd(const float* qkv32, const float* gq, const float* gk, uint16_t* qkv16, int fmt, float* rr, float q_out_scale,
                         int64_t M, int A, float eps, tad_stream_t stream) {
   TAD_REQUIRE(qkv32 && gq && gk && qkv16, "qk_rmsnorm_fwd: null pointer");
-  TAD_REQUIRE(M > 0 && A > 0 && A % 4 == 0 && A <= 64 * 4 * RMS_MAX_V, "qk_rmsnorm_fwd: A=%d must be a multiple of 4 and <= %d", A,
-              64 * 4 * RMS_MAX_V);
+  TAD_REQUIRE(M > 0 && rownorm_width_ok(A), "qk_rmsnorm_fwd: A=%d must be a multiple of 4 and <= %d", A, ROWNORM_MAX_D);
   TAD_REQUIRE(is_op16(fmt), "qk_rmsnorm_fwd: bad fmt %d", fmt);
   TAD_REQUIRE(q_out_scale > 0.f, "qk_rmsnorm_fwd: q_out_scale must be positive");
   // float4 loads of qkv32 (row stride 3A floats), gq and gk; 8-byte packed stores to qkv16; rr is written float by float
@@ -421,26 +338,24 @@ int tadx_qk_rmsnorm_fwd(const float* qkv32, const float* gq, const float* gk, ui
   TAD_REQUIRE_ALIGNED("qk_rmsnorm_fwd", gq, 16);
   TAD_REQUIRE_ALIGNED("qk_rmsnorm_fwd", gk, 16);
   TAD_REQUIRE_ALIGNED("qk_rmsnorm_fwd", qkv16, 8);
-  const int nv = (A / 4 + 63) / 64;
   const dim3 grid((unsigned)((M + 3) / 4)), block(256);
   hipStream_t st = (hipStream_t)stream;
 #define QK_FWD_(NV, F) hipLaunchKernelGGL((qk_rmsnorm_fwd_kernel<NV, F>), grid, block, 0, st, qkv32, gq, gk, qkv16, rr, q_out_scale, M, A, eps)
 #define QK_FWD(NV) \
   if (fmt == TAD_F16) QK_FWD_(NV, TAD_F16); else QK_FWD_(NV, TAD_BF16);
-  RMS_SWITCH_NV(nv, QK_FWD)
+  ROWNORM_SWITCH_NV(rownorm_nv(A), QK_FWD)
 #undef QK_FWD
 #undef QK_FWD_
   return check_launch("qk_rmsnorm_fwd");
 }
 
-size_t tadx_qk_rmsnorm_bwd_workspace_bytes(int64_t M, int A) { return (size_t)2 * rms_bwd_blocks(M) * (size_t)A * sizeof(float); }
+size_t tadx_qk_rmsnorm_bwd_workspace_bytes(int64_t M, int A) { return rownorm_bwd_plan(M, A, 2).partial_floats * sizeof(float); }
 
 int tadx_qk_rmsnorm_bwd(const uint16_t* dqkv16, int fmt, const float* qkv32, const float* gq, const float* gk, const float* rr,
                         float q_out_scale, uint16_t* dqkv_pre16, float* dgq, float* dgk, int accumulate, void* ws, size_t ws_bytes,
                         int64_t M, int A, tad_stream_t stream) {
   TAD_REQUIRE(dqkv16 && qkv32 && gq && gk && rr && dqkv_pre16 && dgq && dgk && ws, "qk_rmsnorm_bwd: null pointer");
-  TAD_REQUIRE(M > 0 && A > 0 && A % 4 == 0 && A <= 64 * 4 * RMS_MAX_V, "qk_rmsnorm_bwd: A=%d must be a multiple of 4 and <= %d", A,
-              64 * 4 * RMS_MAX_V);
+  TAD_REQUIRE(M > 0 && rownorm_width_ok(A), "qk_rmsnorm_bwd: A=%d must be a multiple of 4 and <= %d", A, ROWNORM_MAX_D);
   TAD_REQUIRE(is_op16(fmt), "qk_rmsnorm_bwd: bad fmt %d", fmt);
   // the factor itself does not enter the gradient (the header says why); it is checked so that a forward / backward pair agrees on it
   TAD_REQUIRE(q_out_scale > 0.f, "qk_rmsnorm_bwd: q_out_scale must be positive");
@@ -452,24 +367,21 @@ int tadx_qk_rmsnorm_bwd(const uint16_t* dqkv16, int fmt, const float* qkv32, con
   TAD_REQUIRE_ALIGNED("qk_rmsnorm_bwd", dgq, 16);
   TAD_REQUIRE_ALIGNED("qk_rmsnorm_bwd", dgk, 16);
   TAD_REQUIRE_ALIGNED("qk_rmsnorm_bwd", ws, 16);
-  const int blocks = rms_bwd_blocks(M);
-  if (ws_bytes < (size_t)2 * blocks * A * sizeof(float)) { set_error("qk_rmsnorm_bwd: workspace too small"); return TAD_ENOSPACE; }
-  const int rows_per_block = (int)((M + blocks - 1) / blocks);
-  const int nv = (A / 4 + 63) / 64;
-  const size_t smem = (size_t)4 * 2 * A * sizeof(float);
+  const RowNormBwd p = rownorm_bwd_plan(M, A, 2);
+  if (ws_bytes < p.partial_floats * sizeof(float)) { set_error("qk_rmsnorm_bwd: workspace too small"); return TAD_ENOSPACE; }
   hipStream_t st = (hipStream_t)stream;
   float* partial = (float*)ws;
-#define QK_BWD_(NV, F)                                                                                                          \
-  hipLaunchKernelGGL((qk_rmsnorm_bwd_kernel<NV, F>), dim3(blocks), dim3(256), smem, st, dqkv16, qkv32, gq, gk, rr, dqkv_pre16, partial, M, \
-                     A, rows_per_block)
+#define QK_BWD_(NV, F)                                                                                                               \
+  hipLaunchKernelGGL((qk_rmsnorm_bwd_kernel<NV, F>), dim3(p.blocks), dim3(256), p.smem_bytes, st, dqkv16, qkv32, gq, gk, rr, dqkv_pre16, \
+                     partial, M, A, p.rows_per_block)
 #define QK_BWD(NV) \
   if (fmt == TAD_F16) QK_BWD_(NV, TAD_F16); else QK_BWD_(NV, TAD_BF16);
-  RMS_SWITCH_NV(nv, QK_BWD)
+  ROWNORM_SWITCH_NV(rownorm_nv(A), QK_BWD)
 #undef QK_BWD
 #undef QK_BWD_
   int rc = check_launch("qk_rmsnorm_bwd");
   if (rc) return rc;
-  return launch_reduce_cols(partial, dgq, dgk, nullptr, 2, blocks, A, accumulate ? 1 : 0, st);
+  return launch_reduce_cols(partial, dgq, dgk, nullptr, 2, p.blocks, A, accumulate ? 1 : 0, st);
 }
 
 }  // extern "C"

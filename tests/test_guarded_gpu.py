@@ -365,7 +365,7 @@ def test_attention_dropout(K, arena, B, N, H, d, prescaled, fmt, poison):
 # =============================================================================================== LayerNorm, pooling
 @poison
 @fmt
-@pytest.mark.parametrize("rows,D", [(5, 4), (33, 252), (201, 1000), (31, 1280), (1569, 2048)])
+@pytest.mark.parametrize("rows,D", [(5, 4), (33, 252), (201, 1000), (31, 1280), (5, 1792), (1569, 2048)])
 def test_layernorm(K, arena, rows, D, fmt, poison):
     op = FMTS[fmt]
     g = torch.Generator().manual_seed(rows + D)

@@ -70,6 +70,8 @@ def _cases(lib):
     assert ws_r == 1 * D * 4 and ws_q == 2 * 1 * A_ * 4
     assert lib.tadx_rmsnorm_bwd_workspace_bytes(70, 768) == 3 * 768 * 4  # 32 rows per block
     assert lib.tadx_rmsnorm_bwd_workspace_bytes(5, 1792) == 1792 * 4 and lib.tadx_qk_rmsnorm_bwd_workspace_bytes(5, 1792) == 2 * 1792 * 4
+    # LayerNorm's backward deals its rows the same way (csrc/rownorm.h): three quantities, 50 blocks of 32 rows for 1569 rows
+    assert lib.tad_layernorm_bwd_workspace_bytes(5, 1792) == 3 * 1792 * 4 and lib.tad_layernorm_bwd_workspace_bytes(1569, 1000) == 3 * 50 * 1000 * 4
     out = []
     for ydt, yitem, need in ((F32, 4, {}), (BF16, 2, {"y": 8}), (F16, 2, {"y": 8})):
         out.append(("tadx_rmsnorm_fwd", dict(x=P(4), gamma=P(4), y=P(yitem), y_dtype=ydt, rrms=P(4), rows=ROWS, D=D, eps=1e-6, stream=None), need))

@@ -195,7 +195,7 @@ def test_no_grad_forward_takes_the_implicit_patch_embedding():
 
 
 # ------------------------------------------------------------------ layernorm
-@pytest.mark.parametrize("rows,D", [(150, 128), (37, 384), (1030, 768), (5, 1024), (9, 1280)])
+@pytest.mark.parametrize("rows,D", [(150, 128), (37, 384), (1030, 768), (5, 1024), (9, 1280), (9, 1792), (3, 1540)])
 def test_layernorm_fwd_bwd(K, rows, D):
     x = R.tensor_for(f"ln.x{D}", (rows, D), scale=2.0, shift=0.5)
     w = R.tensor_for(f"ln.w{D}", (D,), scale=0.1, shift=1.0)
