@@ -5,6 +5,7 @@ from . import registry
 from .registry import create_model, register_model, list_models
 from . import modeling_finetune
 from . import internvideo2
+from . import internvideo2_pretrain
 from .ops import set_precision, get_precision
 from .tuning import TuningScope
 from . import mixup, loss, random_erasing, rand_augment, transforms, spatial_sampling, frame_targets, grad_norms

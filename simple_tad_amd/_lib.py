@@ -159,6 +159,15 @@ EXT_SIGNATURES = {
     "tadx_qk_rmsnorm_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _vp, _sz, _i64, _i, _vp]),
 }
 EXT_ABI_VERSION = 1
+
+# The pre-training ABI (include/tad_mi355x_pretrain.h): the third surface of the library, tadp_*, with a version of its own.  The
+# extension ABI above is held at its seven entry points, so what MAE pre-training of the InternVideo2 family adds lives here.  f32 only.
+PRETRAIN_SIGNATURES = {
+    "tadp_abi_version": (_i, []),
+    "tadp_visible_tokens_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "tadp_visible_tokens_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+}
+PRETRAIN_ABI_VERSION = 1
 LINEAR_PLAN_FIELDS = ("r0", "rows", "kernel", "persistent", "direct", "grid", "block", "group_m", "sk_splits", "sk_mode", "epilogue")
 ATTN_PLAN_FIELDS = ("kernel", "hd", "out16", "qs", "drop", "dma_mode", "skip", "has_lo", "grid", "block")
 ATTN_FWD, ATTN_FWD_Q64, ATTN_BWD_DQ, ATTN_BWD_DKV = range(4)  # the "kernel" field
@@ -202,7 +211,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} not found: the HIP extension has not been built. Run `python -m simple_tad_amd.build` "
             "(or __graft_entry__.build()). There is no CPU fallback for the MI355X path.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *PRETRAIN_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover
@@ -215,6 +224,9 @@ def load() -> C.CDLL:
     v = lib.tadx_abi_version()
     if v != EXT_ABI_VERSION:
         raise TadError(f"extension ABI mismatch: library reports {v}, binding expects {EXT_ABI_VERSION}")
+    v = lib.tadp_abi_version()
+    if v != PRETRAIN_ABI_VERSION:
+        raise TadError(f"pre-training ABI mismatch: library reports {v}, binding expects {PRETRAIN_ABI_VERSION}")
     _lib = lib
     return lib
 

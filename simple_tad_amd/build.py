@@ -18,7 +18,7 @@ _LIB_NAME = os.environ.get("TAD_BUILD_LIB", "libtad_ablation.so" if _ABLATION el
 EXP_DIR = os.path.join(os.path.dirname(HERE), "build_exp")
 _PRODUCTION = _LIB_NAME == "libtad_mi355x.so"
 LIB = os.path.join(HERE if _PRODUCTION else EXP_DIR, os.path.basename(_LIB_NAME))
-SOURCES = ["capi.hip", "elementwise.hip", "patch_embed.hip", "layernorm.hip", "gemm.hip", "gemm_plan.hip", "gemm_w4.hip", "attn_fwd.hip", "attn_bwd.hip", "attn_plan.hip", "attn_f32.hip", "precise.hip", "optim.hip", "ema.hip", "mixup.hip", "frame_loss.hip", "erasing.hip", "randaug.hip", "multiscale_crop.hip", "frame_resize.hip", "spatial_sample.hip", "mae.hip", "metrics.hip", "group_metrics.hip", "grad_segnorm.hip", "collective.hip", "im2col.hip", "pooled_tail.hip", "layerscale.hip", "attn_colsum.hip", "rmsnorm.hip"]
+SOURCES = ["capi.hip", "elementwise.hip", "patch_embed.hip", "layernorm.hip", "gemm.hip", "gemm_plan.hip", "gemm_w4.hip", "attn_fwd.hip", "attn_bwd.hip", "attn_plan.hip", "attn_f32.hip", "precise.hip", "optim.hip", "ema.hip", "mixup.hip", "frame_loss.hip", "erasing.hip", "randaug.hip", "multiscale_crop.hip", "frame_resize.hip", "spatial_sample.hip", "mae.hip", "metrics.hip", "group_metrics.hip", "grad_segnorm.hip", "collective.hip", "im2col.hip", "pooled_tail.hip", "layerscale.hip", "attn_colsum.hip", "rmsnorm.hip", "visible_tokens.hip"]
 # Sources that touch 16-bit GEMM / attention operands are compiled a second time with -DTAD_OPND_F16: the same kernels for IEEE half
 # operands, exported as tad_*_f16 (csrc/common.h, csrc/opnd_f16_names.h; include/tad_mi355x.h "IEEE half operand twins").
 F16_SOURCES = ["elementwise.hip", "patch_embed.hip", "layernorm.hip", "gemm.hip", "gemm_w4.hip", "attn_fwd.hip", "attn_bwd.hip", "optim.hip", "pooled_tail.hip", "layerscale.hip"]
@@ -28,11 +28,13 @@ NO_VGPR_FORM = {"gemm_w4.hip"}
 # gemm_plan.hip and attn_plan.hip (the launch planners: host code, nothing in them depends on the operand format) are compiled once, not per format;
 # so are im2col.hip (the output format is a template argument there: it defines tad_im2col_tubelets / _u8 and their _f16 twins itself)
 # and attn_colsum.hip (the operand format is a template argument; one entry point takes it at run time); rmsnorm.hip (the extension ABI,
-# include/tad_mi355x_ext.h) takes every 16-bit format at run time
+# include/tad_mi355x_ext.h) takes every 16-bit format at run time; visible_tokens.hip (the pre-training ABI, include/tad_mi355x_pretrain.h)
+# is f32 only
 EXTRA_DEPS = {"gemm.hip": ["gemm_kernels.h", "gemm_plan.h"], "gemm_w4.hip": ["gemm_kernels.h", "gemm_plan.h"], "gemm_plan.hip": ["gemm_plan.h", "knob.h"],
               "attn_fwd.hip": ["attn_plan.h"], "attn_bwd.hip": ["attn_plan.h"], "attn_plan.hip": ["attn_plan.h", "knob.h"],
               "multiscale_crop.hip": ["frame_io.h"], "frame_resize.hip": ["frame_io.h"], "spatial_sample.hip": ["frame_io.h"], "randaug.hip": ["frame_io.h"],
-              "layernorm.hip": ["rownorm.h"], "rmsnorm.hip": ["rownorm.h", "../../include/tad_mi355x_ext.h"]}
+              "layernorm.hip": ["rownorm.h"], "rmsnorm.hip": ["rownorm.h", "../../include/tad_mi355x_ext.h"],
+              "visible_tokens.hip": ["../../include/tad_mi355x_pretrain.h"]}
 # ema.hip and mixup.hip must round like torch (a product, a product, a sum: three roundings) and are compiled without FMA contraction;
 # randaug.hip must round like PIL's C code (a float blend, a double affine map and cubic: each product and sum on its own).
 # multiscale_crop.hip writes the same normalised f32 values as randaug.hip's frames_to_clip and takes the same flags.

@@ -2,7 +2,8 @@
 (SURVEY 8f-2): per step -- lr / weight-decay assignment (:39-45), reconstruction target from the clip (:51-66, one HIP kernel on
 the masked tokens only), model forward, ``nn.MSELoss`` (:68-70, fused loss + gradient kernel), ``loss.item()``, scaler step with
 ``clip_grad=max_norm`` (:79-81), the per-head gradient-norm diagnostics over the encoder (:30-33, 84-91, 134-147; one device-side
-collect per step, ``train_one_epoch_with_grad_norms``), synchronise.  Left out: the ``gc.collect()/empty_cache()`` per step (:36-37), tensorboard
+collect per step, ``train_one_epoch_with_grad_norms``), synchronise.  ``train_one_epoch_double`` (:155-307) is the same step over two
+loaders at once, their batches joined.  Left out: the ``gc.collect()/empty_cache()`` per step (:36-37), tensorboard
 logging."""
 from __future__ import annotations
 
@@ -52,8 +53,53 @@ def train_one_epoch_with_grad_norms(model: torch.nn.Module, data_loader: Iterabl
                             lr_schedule_values, wd_schedule_values, tubelet_size, log, augment_fn, grad_norms)
 
 
+def train_one_epoch_double(model: torch.nn.Module, data_loader1: Iterable, data_loader2: Iterable, optimizer, device: torch.device,
+                           epoch: int, loss_scaler, max_norm: float = 0, patch_size: int = 16, normlize_target: bool = True, start_steps=0,
+                           lr_schedule_values=None, wd_schedule_values=None, tubelet_size: int = 2, log=None, augment_fn=None):
+    """Counterpart of ``engine_for_pretraining.train_one_epoch_double`` (engine_for_pretraining.py:155-307), the step of domain-adaptive
+    pre-training on two datasets at once: it walks ``zip(data_loader1, data_loader2)`` (so it stops with the shorter loader), joins the
+    clips and the masks of the two batches along the batch dimension, loader 1's first (:196-199), and runs the step of
+    ``train_one_epoch`` on the joined batch.  Host batches are joined on the host and move to the device as one tensor; batches a
+    ``prefetch.ClipPrefetcher`` already delivered to the device are joined there.  Every clip of the JOINED batch must mask the same
+    number of tokens: another count in loader 2's batch is refused before any kernel runs.
+
+    Returns the ``stats`` dict of ``train_one_epoch``.  The reference returns a pair whose second item, the gradient-norm diagnostics,
+    is always ``None``: its collect call is commented out (:234-235, with ``with_grad_norms`` left False by its caller).  There is no
+    ``grad_norms`` argument here for that reason."""
+    return _train_one_epoch(model, _joined_batches(data_loader1, data_loader2, device), optimizer, device, epoch, loss_scaler, max_norm,
+                            patch_size, normlize_target, start_steps, lr_schedule_values, wd_schedule_values, tubelet_size, log, augment_fn,
+                            None, who="train_one_epoch_double")
+
+
+def _join(a, b, device):
+    """two batches' tensors as one, a's rows first: where both already are where the other is they are joined there (host with host,
+    device with device); a host half beside a device half follows it to the device first"""
+    a, b = torch.as_tensor(a), torch.as_tensor(b)
+    if a.device != b.device:
+        a, b = a.to(device, non_blocking=True), b.to(device, non_blocking=True)
+    return torch.cat([a, b], dim=0)
+
+
+def _joined_batches(data_loader1, data_loader2, device):
+    """the step iterator of ``train_one_epoch_double``: (clips, masks) of loader 1's batch followed by loader 2's.  Masks are flattened
+    per clip before they are joined, so that the two loaders may deliver them as [B, T, H, W] or [B, N] alike; a pair of batches
+    without masks (an ``augment_fn`` draws them) yields the clips alone.  Masks from one loader only are refused: dropping them would
+    hide the mismatch behind a later message, or behind masks an ``augment_fn`` draws anew."""
+    for step, (batch1, batch2) in enumerate(zip(data_loader1, data_loader2)):
+        has1, has2 = len(batch1) > 1, len(batch2) > 1
+        if has1 != has2:
+            raise ValueError(f"train_one_epoch_double: step {step}: data_loader{1 if has1 else 2} delivers masks and "
+                             f"data_loader{2 if has1 else 1} does not; both loaders must deliver (clips, masks), or both the clips alone")
+        videos = _join(batch1[0], batch2[0], device)
+        if has1:
+            yield videos, _join(torch.as_tensor(batch1[1]).flatten(1), torch.as_tensor(batch2[1]).flatten(1), device)
+        else:
+            yield (videos,)
+
+
 def _train_one_epoch(model, data_loader, optimizer, device, epoch, loss_scaler, max_norm, patch_size, normlize_target, start_steps,
-                     lr_schedule_values, wd_schedule_values, tubelet_size, log, augment_fn, grad_norms):
+                     lr_schedule_values, wd_schedule_values, tubelet_size, log, augment_fn, grad_norms, who="train_one_epoch"):
+    """``data_loader``: the step iterator -- anything that yields (clips, masks) or (clips,) batches, one per step"""
     model.train()
     dp = model if isinstance(model, DataParallel) else None
     inner = dp.module if dp is not None else model
@@ -75,7 +121,7 @@ def _train_one_epoch(model, data_loader, optimizer, device, epoch, loss_scaler, 
             augmented = augment_fn(videos)
             videos, bool_masked_pos = augmented if isinstance(augmented, (tuple, list)) else (augmented, bool_masked_pos)
         if bool_masked_pos is None:
-            raise ValueError("train_one_epoch: no masks for this step: the batch holds one item and augment_fn "
+            raise ValueError(f"{who}: no masks for this step: the batch holds one item and augment_fn "
                              + ("returned the clips alone" if augment_fn is not None else "is None")
                              + " (pass (clips, masks) batches, or an augment_fn that returns (clips, masks))")
         # host-side counts (the mask comes from the loader's generator): one read of all clips' counts where clip 0's was read before
@@ -84,7 +130,7 @@ def _train_one_epoch(model, data_loader, optimizer, device, epoch, loss_scaler, 
         if any(c != num_masked for c in counts):
             # token_indices splits every clip at clip 0's count: masked tokens of another clip would land among the visible ones
             # (the reference's x[~mask].reshape(B, -1, C) usually raises here)
-            raise ValueError(f"train_one_epoch: the clips of this batch mask different numbers of tokens {counts}; "
+            raise ValueError(f"{who}: the clips of this batch mask different numbers of tokens {counts}; "
                              "every clip of a batch must mask the same number")
         bool_masked_pos = torch.as_tensor(bool_masked_pos).to(device, non_blocking=True).flatten(1).to(torch.bool)
         with torch.no_grad():

@@ -810,6 +810,23 @@ def linear_bwd_weight(dy, x, want_bias=True, dW=None, db=None, accumulate=False)
     M, N = dy.shape
     M2, K = x.shape
     assert M == M2
+    if N % 8:
+        # the GEMM moves dy's rows in 16-byte pieces (N % 8 == 0, refused otherwise).  Another width -- the MAE decoder head of a 14 x 14
+        # patch: 588 pixels -- gets zero columns up to the next multiple of 8, as linear_bwd_input's reduction gets them from
+        # _pad_reduction: the rows of dW and the entries of db they produce are dropped, the others are the same sums on the same bits.
+        # Given outputs (gradient sinks) receive the slices by one copy or, with accumulate, one add.
+        tW, tb = linear_bwd_weight(torch.nn.functional.pad(dy, (0, (-N) % 8)).contiguous(), x, want_bias=want_bias)
+        tW, tb = tW[:N], (tb[:N] if want_bias else None)
+        if dW is None:
+            dW, accumulate = tW, False
+        else:
+            dW.add_(tW) if accumulate else dW.copy_(tW)
+        if want_bias:
+            if db is None:
+                db = tb
+            else:
+                db.add_(tb) if accumulate else db.copy_(tb)
+        return dW, (db if want_bias else None)
     if dW is None:
         dW = torch.empty((N, K), dtype=torch.float32, device=dy.device)
         accumulate = False
@@ -890,6 +907,9 @@ def linear_bwd_weight_pair(dy1, x1, dW1, db1, db1b, dy2, x2, dW2, accumulate):
 def colsum_bf16(a, out=None):
     op = _req16(a, "colsum.a")
     M, N = a.shape
+    if N % 8:  # (16-byte row chunks: zero columns up to the next multiple of 8, dropped again -- as linear_bwd_weight)
+        s = colsum_bf16(torch.nn.functional.pad(a, (0, (-N) % 8)).contiguous())[:N]
+        return s if out is None else out.copy_(s)
     if out is None:
         out = torch.empty(N, dtype=torch.float32, device=a.device)
     lib = _lib.load()
@@ -1644,6 +1664,47 @@ def mae_assemble(x_vis, mask_token, pos, vis_idx, mask_idx, B):
         check(_lib.load().tad_mae_assemble(x_vis.data_ptr(), mask_token.data_ptr(), pos.data_ptr(), vis_idx.data_ptr(), mask_idx.data_ptr(),
                                            out.data_ptr(), B, Nv, Nm, D, _stream()), "tad_mae_assemble")
     return out
+
+
+def visible_tokens_fwd(x, pos, tok):
+    """out [B,Nv,D] = x[b, tok[b,i]] + pos[tok[b,i]]: x [B,N,D] f32, pos [N,D] f32, tok [B,Nv] int32 with values in [0, N), distinct per
+    clip (device data: not checked).  The pre-training ABI, include/tad_mi355x_pretrain.h."""
+    _req(x, torch.float32, "visible_tokens.x")
+    _req(pos, torch.float32, "visible_tokens.pos")
+    _idx(tok, "visible_tokens.tok")
+    if x.dim() != 3 or pos.dim() != 2 or tok.dim() != 2 or tok.shape[0] != x.shape[0] or pos.shape != x.shape[1:]:
+        raise _lib.TadError(f"visible_tokens: inconsistent shapes x {tuple(x.shape)}, pos {tuple(pos.shape)}, tok {tuple(tok.shape)}")
+    B, N, D = x.shape
+    Nv = tok.shape[1]
+    out = torch.empty((B, Nv, D), dtype=torch.float32, device=x.device)
+    with _timed("visible_tokens_fwd", 0.0, 12.0 * out.numel()):
+        check(_ext("tadp_visible_tokens_fwd")(x.data_ptr(), pos.data_ptr(), tok.data_ptr(), out.data_ptr(), B, N, Nv, D, _stream()),
+              "tadp_visible_tokens_fwd")
+    return out
+
+
+def visible_tokens_bwd(g, slot, want_dx=True, want_dpos=True, into=None):
+    """(dx [B,N,D] | None, dpos [N,D] | None) from g [B,Nv,D] f32 and slot [B,N] int32 (the inverse of tok, -1 = not visible), one launch.
+    dx has every row written (+0 where a token is masked); dpos sums the clips in the order b = 0, 1, ....
+    into: an existing f32 tensor of N*D elements the table gradient is ADDED to (a gradient sink) instead of a fresh one."""
+    _req(g, torch.float32, "visible_tokens_bwd.g")
+    _idx(slot, "visible_tokens_bwd.slot")
+    if g.dim() != 3 or slot.dim() != 2 or slot.shape[0] != g.shape[0]:
+        raise _lib.TadError(f"visible_tokens_bwd: inconsistent shapes g {tuple(g.shape)}, slot {tuple(slot.shape)}")
+    B, Nv, D = g.shape
+    N = slot.shape[1]
+    dx = torch.empty((B, N, D), dtype=torch.float32, device=g.device) if want_dx else None
+    dpos = None
+    if into is not None:
+        _req(into, torch.float32, "visible_tokens_bwd.into")
+        assert want_dpos and into.numel() == N * D
+        dpos = into
+    elif want_dpos:
+        dpos = torch.empty((N, D), dtype=torch.float32, device=g.device)
+    with _timed("visible_tokens_bwd", 0.0, 4.0 * D * (B * Nv + (B * N if want_dx else 0) + (N if dpos is not None else 0))):
+        check(_ext("tadp_visible_tokens_bwd")(g.data_ptr(), slot.data_ptr(), _p(dx), _p(dpos), int(into is not None), B, N, Nv, D, _stream()),
+              "tadp_visible_tokens_bwd")
+    return dx, dpos
 
 
 def mae_target(videos, mask_idx, tubelet, patch, mean, std, normalize_target=True):

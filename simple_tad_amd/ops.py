@@ -1400,6 +1400,78 @@ class MaeAssembleFn(_Fn):
         return d_xv, d_tok, None, None, None
 
 
+# The entry of the InternVideo2 MAE encoder (internvideo2_pretrain_videomae.py:184-205): a TRAINABLE position table is added, then the
+# visible tokens are kept.  Kernels: csrc/visible_tokens.hip through the pre-training ABI (include/tad_mi355x_pretrain.h).
+_visible_token_kernels = True
+
+
+def set_visible_token_kernels(enabled: bool):
+    """A/B switch: VisibleTokensFn through its HIP kernels (default) or, off, through the torch expressions of the same arithmetic
+    (``x + pos`` over every token, then the index; backward: the index_put into zeros and the dense sum over the batch that autograd
+    would run).  Forward and dx are the same bits either way; the table gradient is summed in torch's order when off.  Sampled by each
+    forward; a node's backward follows its own forward."""
+    global _visible_token_kernels
+    _visible_token_kernels = bool(enabled)
+
+
+def get_visible_token_kernels() -> bool:
+    return _visible_token_kernels
+
+
+class VisibleTokensFn(_Fn):
+    """``(x + pos)[~mask].reshape(B, -1, C)`` with the visible tokens given as indices: x [B,N,D] f32, pos [1,N,D] or [N,D] (a Parameter
+    or any tensor that may want a gradient), vis_tok [B,Nv] int32 (modeling_pretrain.token_indices) -> [B,Nv,D].  Only the visible rows of
+    x are read.  Backward, one launch: dx [B,N,D] with every row written (requested only if x wants a gradient) and the table's
+    gradient summed over the clips in the order b = 0, 1, ... (requested only if pos wants one; written straight into pos' gradient
+    sink where it has one)."""
+
+    @staticmethod
+    def forward(ctx, x, pos, vis_tok):
+        _need_gpu(x, "visible tokens")
+        xc, pc = _f32c(x), _f32c(pos)
+        B, N, D = xc.shape
+        if pc.numel() != N * D or vis_tok.dim() != 2 or vis_tok.shape[0] != B:
+            raise TadError(f"visible tokens: x {tuple(x.shape)}, pos {tuple(pos.shape)} and vis_tok {tuple(vis_tok.shape)} do not belong together")
+        pc = pc.reshape(N, D)
+        tok = vis_tok.detach()
+        tok = tok if tok.dtype == torch.int32 else tok.to(torch.int32)
+        tok = tok if tok.is_contiguous() else tok.contiguous()
+        ctx.kernels = _visible_token_kernels
+        ctx.need = _needs(ctx, 2)
+        ctx.pos = pos
+        ctx.meta = (B, N, D)
+        if ctx.kernels:
+            out = K.visible_tokens_fwd(xc, pc, tok)
+            if _differentiated(ctx):
+                # slot[b, n]: where token n stands among clip b's visible tokens, -1 if it is masked; built on the device, no sync
+                slot = torch.full((B, N), -1, dtype=torch.int32, device=xc.device)
+                slot.scatter_(1, tok.long(), torch.arange(tok.shape[1], dtype=torch.int32, device=xc.device).expand(B, -1))
+                ctx.save_for_backward(slot)
+        else:
+            out = (xc + pc)[torch.arange(B, device=xc.device).unsqueeze(1), tok.long()]
+            if _differentiated(ctx):
+                ctx.save_for_backward(tok)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (idx,) = ctx.saved_tensors
+        B, N, D = ctx.meta
+        gc = _f32c(g)
+        need_x, need_pos = ctx.need
+        if not ctx.kernels:
+            full = torch.zeros((B, N, D), dtype=torch.float32, device=gc.device)
+            full[torch.arange(B, device=gc.device).unsqueeze(1), idx.long()] = gc
+            return (full if need_x else None), (full.sum(0).reshape(ctx.pos.shape) if need_pos else None), None
+        ent = _sink(ctx.pos) if need_pos else None
+        dx, dpos = K.visible_tokens_bwd(gc, idx, want_dx=need_x, want_dpos=need_pos, into=None if ent is None else ent[1])
+        if ent is not None:
+            if ent[2] is not None:
+                ent[2](ctx.pos)
+            dpos = None
+        return dx, (None if dpos is None else dpos.reshape(ctx.pos.shape)), None
+
+
 class MseLossFn(_Fn):
     """nn.MSELoss()(outputs, labels) (engine_for_pretraining.py:27,70): loss and d(loss)/d(outputs) in one pass"""
 
