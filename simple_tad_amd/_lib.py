@@ -168,6 +168,18 @@ PRETRAIN_SIGNATURES = {
     "tadp_visible_tokens_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
 PRETRAIN_ABI_VERSION = 1
+
+# The serving ABI (include/tad_mi355x_serve.h): the fourth surface, tads_*, in a library of its own -- libtad_mi355x_serve.so, loaded beside
+# the first one (the three surfaces above are held where they are).  It keeps its own error text (tads_last_error_string; check_serve).
+SERVE_LIB_PATH = os.path.join(_HERE, "libtad_mi355x_serve.so")
+SERVE_SIGNATURES = {
+    "tads_abi_version": (_i, []),
+    "tads_last_error_string": (C.c_char_p, []),
+    "tads_class_token_entry_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "tads_class_token_entry_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "tads_residual_rmsnorm_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _f, _vp]),
+}
+SERVE_ABI_VERSION = 1
 LINEAR_PLAN_FIELDS = ("r0", "rows", "kernel", "persistent", "direct", "grid", "block", "group_m", "sk_splits", "sk_mode", "epilogue")
 ATTN_PLAN_FIELDS = ("kernel", "hd", "out16", "qs", "drop", "dma_mode", "skip", "has_lo", "grid", "block")
 ATTN_FWD, ATTN_FWD_Q64, ATTN_BWD_DQ, ATTN_BWD_DKV = range(4)  # the "kernel" field
@@ -227,8 +239,47 @@ def load() -> C.CDLL:
     v = lib.tadp_abi_version()
     if v != PRETRAIN_ABI_VERSION:
         raise TadError(f"pre-training ABI mismatch: library reports {v}, binding expects {PRETRAIN_ABI_VERSION}")
+    _load_serve()
     _lib = lib
     return lib
+
+
+_serve = None
+
+
+def _load_serve() -> C.CDLL:
+    global _serve
+    if _serve is not None:
+        return _serve
+    if not os.path.exists(SERVE_LIB_PATH):
+        raise TadError(
+            f"{SERVE_LIB_PATH} not found: the serving library has not been built. Run `python -m simple_tad_amd.build` "
+            "(or __graft_entry__.build()). There is no CPU fallback for the MI355X path.")
+    lib = C.CDLL(SERVE_LIB_PATH)
+    for name, (res, args) in SERVE_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:  # pragma: no cover
+            raise TadError(f"{SERVE_LIB_PATH} does not export {name}") from e
+        fn.restype = res
+        fn.argtypes = args
+    v = lib.tads_abi_version()
+    if v != SERVE_ABI_VERSION:
+        raise TadError(f"serving ABI mismatch: library reports {v}, binding expects {SERVE_ABI_VERSION}")
+    _serve = lib
+    return lib
+
+
+def load_serve() -> C.CDLL:
+    """the serving library (tads_*); loaded, and checked, together with the first one"""
+    load()
+    return _serve
+
+
+def check_serve(rc: int, what: str = "") -> None:
+    if rc != 0:
+        msg = load_serve().tads_last_error_string()
+        raise TadError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
 
 
 def check(rc: int, what: str = "") -> None:

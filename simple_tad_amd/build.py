@@ -1,4 +1,4 @@
-"""Build libtad_mi355x.so (gfx950) in-tree with hipcc.  `python -m simple_tad_amd.build [--force]`."""
+"""Build libtad_mi355x.so and libtad_mi355x_serve.so (gfx950) in-tree with hipcc.  `python -m simple_tad_amd.build [--force]`."""
 import os
 import subprocess
 import sys
@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 # library: without TAD_BUILD_LIB it builds build_exp/libtad_ablation.so in its own object directory.
 _ABLATION = os.environ.get("TAD_BUILD_ABLATION") == "1"
 _LIB_NAME = os.environ.get("TAD_BUILD_LIB", "libtad_ablation.so" if _ABLATION else "libtad_mi355x.so")
-# The production library is the ONLY built file in the package directory; every experiment / ablation build (and its objects) goes to
+# The production library and the serving library beside it (SERVE_LIB below) are the ONLY built files in the package directory; every experiment / ablation build (and its objects) goes to
 # <repo>/build_exp/ -- git-ignored like every built artefact, but not gpurun-ignored, so it travels to the GPU box with the snapshot.
 EXP_DIR = os.path.join(os.path.dirname(HERE), "build_exp")
 _PRODUCTION = _LIB_NAME == "libtad_mi355x.so"
@@ -42,6 +42,12 @@ EXTRA_DEPS = {"gemm.hip": ["gemm_kernels.h", "gemm_plan.h"], "gemm_w4.hip": ["ge
 # frame_resize.hip fades a reflected pad band with one f32 product rounded on its own (cv2.addWeighted) and writes frames_to_clip's f32 values.
 # A `#pragma clang fp contract(off)` is not enough: -ffp-contract=fast also lets the code generator fuse fmul + fadd by itself.
 NO_FP_CONTRACT = {"ema.hip", "mixup.hip", "randaug.hip", "multiscale_crop.hip", "spatial_sample.hip", "frame_resize.hip"}
+# The serving library (include/tad_mi355x_serve.h, tads_*): libtad_mi355x.so is held at its three surfaces, so the fourth is linked apart, from
+# its own source list, with the same FLAGS plus hidden visibility (its entry points alone are exported: nothing in it can bind to or shadow
+# the first library's C++ symbols).  Built after the first library by build(); experiment and ablation builds do not build it.
+SERVE_LIB = os.path.join(HERE, "libtad_mi355x_serve.so")
+SERVE_SOURCES = ["iv2_serve.hip"]
+EXTRA_DEPS["iv2_serve.hip"] = ["rownorm.h", "../../include/tad_mi355x_serve.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wno-unused-result",
          # keep MFMA accumulators in the (unified) VGPR file: without it the compiler parks them in AGPRs and pays a
          # v_accvgpr_read/write per element around every softmax / epilogue
@@ -64,6 +70,39 @@ def _deps_mtime():
 
 
 def build(force: bool = False, verbose: bool = True) -> str:
+    """build what is stale: the library (returned) and, in a production build, the serving library beside it"""
+    lib = _build_core(force, verbose)
+    if _PRODUCTION:
+        _build_serve(force, verbose)
+    return lib
+
+
+def _build_serve(force: bool, verbose: bool) -> str:
+    if not force and os.path.exists(SERVE_LIB) and os.path.getmtime(SERVE_LIB) >= _deps_mtime():
+        return SERVE_LIB
+    objdir = os.path.join(HERE, "build")
+    os.makedirs(objdir, exist_ok=True)
+    hipcc = _hipcc()
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(os.path.dirname(HERE), "include", "tad_mi355x.h")]
+    objs = []
+    for src in SERVE_SOURCES:
+        obj, srcp = os.path.join(objdir, src.replace(".hip", ".o")), os.path.join(CSRC, src)
+        deps = [srcp, *headers, *[os.path.join(CSRC, d) for d in EXTRA_DEPS.get(src, [])]]
+        objs.append(obj)
+        if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(p) for p in deps):
+            continue
+        cmd = [hipcc, *FLAGS, "-fvisibility=hidden", "-c", srcp, "-o", obj]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-fvisibility=hidden", "-o", SERVE_LIB, *objs]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    return SERVE_LIB
+
+
+def _build_core(force: bool = False, verbose: bool = True) -> str:
     if not force and os.path.exists(LIB) and os.path.getmtime(LIB) >= _deps_mtime():
         return LIB
     objdir = os.path.join(HERE, "build") if _PRODUCTION else os.path.join(EXP_DIR, "obj_" + os.path.splitext(os.path.basename(LIB))[0])

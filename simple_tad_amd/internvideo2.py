@@ -10,8 +10,13 @@ One route instead of the reference's two: ``use_flash_attn``, ``use_fused_rmsnor
             applies the attention kernels' q contract), the head_dim-64 attention kernels, proj
     mlp     ops.MlpFn
 
-and layer scale, drop path and the residual as torch element-wise ops on the f32 stream.  The class token's concatenation and the
-``+ pos_embed`` are torch ops too: the table is trainable here and receives its gradient.  ``clip_projector`` (attention pooling with one
+and, with gradients enabled, layer scale, drop path and the residual as torch element-wise ops on the f32 stream.  Without gradients the
+blocks run as one loop in which each half block's layer scale, residual and the norm behind it are ONE launch (``_blocks_eval``;
+csrc/iv2_serve.hip, ops.set_iv2_serve_kernels).  The class token's concatenation and the ``+ pos_embed`` are one kernel pass in every mode
+(ops.ClassTokenEntryFn): the table is trainable here and receives its gradient, summed over the clips in a fixed order.  The entry takes
+what modeling_finetune.PatchEmbed takes: float clips, clips in the 16-bit operand format, uint8 frames [B,T,H,W,3] (with a ring offset)
+and frame_store.FrameWindows -- so inference.score_video / SlidingWindow, FrameStore and the engines serve this family as they serve
+the ViT.  ``clip_projector`` (attention pooling with one
 query per clip, head_dim 24 at the shipped sizes) is composed of MeanPoolFn, LayerNormFn, LinearSplitFn (split-operand GEMMs) and a torch softmax over [B, heads, N].
 
 There is no CPU path, and no "precise" mode for this family.
@@ -28,6 +33,7 @@ import torch.utils.checkpoint as checkpoint
 
 from . import ops
 from ._lib import TadError
+from .frame_store import FrameWindows
 from .modeling_finetune import DropPath, to_2tuple, trunc_normal_
 from .registry import register_model
 
@@ -299,17 +305,52 @@ class PatchEmbed(nn.Module):
         if norm_layer:
             raise TadError("PatchEmbed: a norm behind the projection is never used by this family and has no route")
 
-    def forward(self, x):
-        _no_precise("PatchEmbed")
-        if x.dim() != 5 or not x.is_floating_point():
-            raise TadError("PatchEmbed: this family takes normalised float clips [B,C,T,H,W]")
-        B, C, T, H, W = x.shape
-        assert H == self.img_size[0] and W == self.img_size[1], \
+    # ---- input stage, as modeling_finetune.PatchEmbed has it: uint8 frames, frame-store windows and 16-bit clips straight into the
+    # patch matrix.  inference.SlidingWindow / score_video, frame_store and the engines ask for exactly these attributes.
+    input_mean = (0.485, 0.456, 0.406)
+    input_std = (0.229, 0.224, 0.225)
+    input_bgr = False
+    t_offset = 0                        # ring-buffer start slot (inference.SlidingWindow)
+
+    def set_input_normalization(self, mean, std, bgr=False):
+        self.input_mean, self.input_std, self.input_bgr = tuple(float(v) for v in mean), tuple(float(v) for v in std), bool(bgr)
+
+    def _check_u8(self, H, W, C):
+        assert C == 3 and H == self.img_size[0] and W == self.img_size[1], \
             f"Input image size ({H}*{W}) doesn't match model ({self.img_size[0]}*{self.img_size[1]})."
+        if ops.get_precision() == "precise":
+            raise TadError('precision "precise" takes the normalised f32 clip (the uint8 input stage feeds the bf16 path)')
+        _no_precise("PatchEmbed")
         if self.patch_size[0] != self.patch_size[1]:
             raise TadError("PatchEmbed: only square patches have a kernel")
-        x = ops.PatchEmbedFn.apply(x.float(), self.proj.weight, self.proj.bias, None, self.tubelet_size, self.patch_size[0])
-        return x.reshape(B, T // self.tubelet_size, -1, x.shape[-1])
+
+    def forward(self, x):
+        w, b, tub, p = self.proj.weight, self.proj.bias, self.tubelet_size, self.patch_size[0]
+        if isinstance(x, FrameWindows):
+            B, T, H, W, C = x.shape
+            self._check_u8(H, W, C)
+            y = ops.PatchEmbedWindowsFn.apply(x.store, x.idx, w, b, None, tub, p, self.input_mean, self.input_std, x.bgr)
+        elif x.dtype == torch.uint8:
+            if x.dim() != 5:
+                raise TadError("PatchEmbed: uint8 frames come as [B,T,H,W,3]")
+            B, T, H, W, C = x.shape
+            self._check_u8(H, W, C)
+            y = ops.PatchEmbedU8Fn.apply(x, w, b, None, tub, p, self.input_mean, self.input_std, self.input_bgr, int(self.t_offset))
+        else:
+            _no_precise("PatchEmbed")
+            if x.dim() != 5 or not x.is_floating_point():
+                raise TadError("PatchEmbed: this family takes clips [B,C,T,H,W] (float, or the 16-bit operand format), uint8 frames "
+                               "[B,T,H,W,3] or frame-store windows")
+            B, C, T, H, W = x.shape
+            assert H == self.img_size[0] and W == self.img_size[1], \
+                f"Input image size ({H}*{W}) doesn't match model ({self.img_size[0]}*{self.img_size[1]})."
+            if self.patch_size[0] != self.patch_size[1]:
+                raise TadError("PatchEmbed: only square patches have a kernel")
+            if x.dtype == ops.K.operand_dtype():
+                y = ops.PatchEmbed16Fn.apply(x, w, b, None, tub, p)
+            else:
+                y = ops.PatchEmbedFn.apply(x.float(), w, b, None, tub, p)
+        return y.reshape(B, T // tub, -1, y.shape[-1])
 
 
 class InternVideo2(nn.Module):
@@ -326,6 +367,10 @@ class InternVideo2(nn.Module):
         self.use_flash_attn = use_flash_attn
         self.embed_dim = embed_dim
         self.num_heads = num_heads
+        # (what inference.score_video / SlidingWindow, explain.token_grid and the engines ask a model: plain attributes, no state)
+        self.num_frames = num_frames
+        self.tubelet_size = tubelet_size
+        self.num_classes = num_classes
         norm_layer_for_blocks = partial(RMSNorm, eps=1e-6)
         self.norm_layer_for_blocks = norm_layer_for_blocks
         self.patch_embed = PatchEmbed(img_size, patch_size, in_chans, embed_dim, num_frames=num_frames, tubelet_size=tubelet_size)
@@ -403,16 +448,39 @@ class InternVideo2(nn.Module):
         pos = self.pos_embed_spatial.repeat(1, T, 1) + torch.repeat_interleave(self.pos_embed_temporal, Hg * Wg, dim=1)
         return torch.cat([self.pos_embed_cls.expand(pos.shape[0], -1, -1), pos], 1)
 
+    def _blocks_eval(self, x):
+        """The blocks without autograd, as one loop that carries (x, xn): the residual stream and its RMSNorm as the next Linear's 16-bit
+        operand.  Each half block ends in ONE launch (kernels.residual_rmsnorm: layer scale, residual, the next norm) where the module
+        route runs a mul, an add and a norm; the arithmetic of x is the module route's (the product and the sum rounded on their own).
+        DropPath is the identity here; a block without LayerScale (init_values=0) has a null gamma."""
+        blocks = self.blocks
+        for blk in blocks:  # (as Block.forward: the 1B and 6B models refuse with the attention route's own error before anything runs)
+            ops.require_attn_head_dim(ops.head_dim_of(blk.attn.qkv.weight, blk.attn.num_heads))
+        gamma = lambda ls: ops._f32c(ls.gamma) if isinstance(ls, LayerScale) else None
+        x = ops._f32c(x)
+        xn = blocks[0].norm1(x, out16=True)
+        for i, blk in enumerate(blocks):
+            nxt = blocks[i + 1].norm1 if i + 1 < len(blocks) else None
+            y = ops._f32c(blk.attn(xn))
+            x, xn = ops.K.residual_rmsnorm(x, y, gamma(blk.ls1), ops._f32c(blk.norm2.weight), blk.norm2.variance_epsilon, out=x if i else None)
+            y = ops._f32c(blk.mlp(xn))
+            x, xn = ops.K.residual_rmsnorm(x, y, gamma(blk.ls2), None if nxt is None else ops._f32c(nxt.weight),
+                                           blk.norm2.variance_epsilon if nxt is None else nxt.variance_epsilon, out=x)
+        return x
+
     def forward(self, x):
         _no_precise("InternVideo2")
-        ops._need_gpu(x, "InternVideo2")
+        ops._need_gpu(x.store if isinstance(x, FrameWindows) else x, "InternVideo2")
         x = self.patch_embed(x)
         B, T, L, C = x.shape
-        x = x.reshape(B, T * L, C)
-        x = torch.cat((self.cls_token.expand(B, -1, -1), x), dim=1)
-        x = x + self._pos_table()
-        for blk in self.blocks:
-            x = blk(x)
+        x = ops.ClassTokenEntryFn.apply(x.reshape(B, T * L, C), self.cls_token, self._pos_table())
+        # (a model left in training mode under no_grad still drops paths: that is the module route's affair)
+        drops = self.training and any(isinstance(m, DropPath) for blk in self.blocks for m in (blk.drop_path1, blk.drop_path2))
+        if not torch.is_grad_enabled() and ops.get_iv2_serve_kernels() and len(self.blocks) and not drops:
+            x = self._blocks_eval(x)
+        else:
+            for blk in self.blocks:
+                x = blk(x)
         x = self.clip_projector(x)
         x = ops.LayerNormFn.apply(x, self.fc_norm.weight, self.fc_norm.bias, self.fc_norm.eps)
         return self.head(self.fc_dropout(x))

@@ -1707,6 +1707,81 @@ def visible_tokens_bwd(g, slot, want_dx=True, want_dpos=True, into=None):
     return dx, dpos
 
 
+# ----------------------------------------------------------------------------- serving ABI (libtad_mi355x_serve.so, tads_*)
+def _serve(name: str):
+    return getattr(_lib.load_serve(), name)
+
+
+def class_token_entry_fwd(patch, cls, pos):
+    """out [B,N+1,D] = cat((cls.expand(B,1,D), patch), 1) + pos: patch [B,N,D] f32, cls [D] f32, pos [N+1,D] f32.  One pass.
+    The serving ABI, include/tad_mi355x_serve.h."""
+    _req(patch, torch.float32, "class_token_entry.patch")
+    _req(cls, torch.float32, "class_token_entry.cls")
+    _req(pos, torch.float32, "class_token_entry.pos")
+    if patch.dim() != 3 or cls.numel() != patch.shape[2] or pos.dim() != 2 or pos.shape != (patch.shape[1] + 1, patch.shape[2]):
+        raise _lib.TadError(f"class_token_entry: inconsistent shapes patch {tuple(patch.shape)}, cls {tuple(cls.shape)}, pos {tuple(pos.shape)}")
+    B, N, D = patch.shape
+    out = torch.empty((B, N + 1, D), dtype=torch.float32, device=patch.device)
+    with _timed("class_token_entry_fwd", 0.0, 4.0 * D * (B * N + N + 2 + B * (N + 1))):
+        _lib.check_serve(_serve("tads_class_token_entry_fwd")(patch.data_ptr(), cls.data_ptr(), pos.data_ptr(), out.data_ptr(), B, N, D, _stream()),
+                         "tads_class_token_entry_fwd")
+    return out
+
+
+def class_token_entry_bwd(g, want_dpatch=True, want_dpos=True, want_dcls=True, into_pos=None, into_cls=None):
+    """(dpatch [B,N,D] | None, dpos [N+1,D] | None, dcls [D] | None) from g [B,N+1,D] f32, one launch.  dpos / dcls sum the clips in the
+    order b = 0, 1, ....  into_pos / into_cls: existing f32 tensors of (N+1)*D / D elements the sums are ADDED to (gradient sinks)
+    instead of fresh ones.  The kernel has ONE accumulate flag: where both sums are wanted, both have a sink or neither has."""
+    _req(g, torch.float32, "class_token_entry_bwd.g")
+    if g.dim() != 3 or g.shape[1] < 2:
+        raise _lib.TadError(f"class_token_entry_bwd: g {tuple(g.shape)} is no [B,N+1,D] gradient")
+    B, N1, D = g.shape
+    N = N1 - 1
+    for t, n, what in ((into_pos, N1 * D, "into_pos"), (into_cls, D, "into_cls")):
+        if t is not None:
+            _req(t, torch.float32, "class_token_entry_bwd." + what)
+            assert t.numel() == n
+    want_dpos, want_dcls = want_dpos or into_pos is not None, want_dcls or into_cls is not None
+    dpatch = torch.empty((B, N, D), dtype=torch.float32, device=g.device) if want_dpatch else None
+    dpos = into_pos if into_pos is not None else (torch.empty((N1, D), dtype=torch.float32, device=g.device) if want_dpos else None)
+    dcls = into_cls if into_cls is not None else (torch.empty(D, dtype=torch.float32, device=g.device) if want_dcls else None)
+    fn = _serve("tads_class_token_entry_bwd")
+    nbytes = 4.0 * D * (B * N1 + (B * N if want_dpatch else 0) + (N1 if dpos is not None else 0))
+    if want_dpos and want_dcls and (into_pos is None) != (into_cls is None):
+        raise _lib.TadError("class_token_entry_bwd: one accumulate flag serves dpos and dcls: give both a sink or neither")
+    with _timed("class_token_entry_bwd", 0.0, nbytes):
+        acc = int(into_pos is not None or into_cls is not None)
+        _lib.check_serve(fn(g.data_ptr(), _p(dpatch), _p(dpos), _p(dcls), acc, B, N, D, _stream()), "tads_class_token_entry_bwd")
+    return dpatch, (dpos if want_dpos else None), (dcls if want_dcls else None)
+
+
+def residual_rmsnorm(x, y, ls_gamma=None, norm_gamma=None, eps: float = 1e-6, out=None, xn_dtype=None):
+    """(x_out f32, xn | None): x_out = x + y * ls_gamma (ls_gamma None: x + y) and, with norm_gamma, xn = RMSNorm(x_out) * norm_gamma in a
+    16-bit operand format (xn_dtype; None = the process-wide one), one pass over the rows.  x, y [..., D] f32; out: where x_out goes (may
+    be x itself, not y; None = a fresh tensor).  Evaluation only: nothing is kept for a backward."""
+    _req(x, torch.float32, "residual_rmsnorm.x")
+    _req(y, torch.float32, "residual_rmsnorm.y")
+    D = x.shape[-1]
+    rows = x.numel() // D
+    if y.shape != x.shape:
+        raise _lib.TadError(f"residual_rmsnorm: x {tuple(x.shape)} and y {tuple(y.shape)} differ")
+    for t, what in ((ls_gamma, "ls_gamma"), (norm_gamma, "norm_gamma")):
+        if t is not None:
+            _req(t, torch.float32, "residual_rmsnorm." + what)
+            assert t.numel() == D
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _req(out, torch.float32, "residual_rmsnorm.out")
+        assert out.shape == x.shape
+    xn = torch.empty(x.shape, dtype=xn_dtype or _op16, device=x.device) if norm_gamma is not None else None
+    with _timed("residual_rmsnorm", 0.0, rows * D * (12.0 + (0 if xn is None else xn.element_size()))):
+        _lib.check_serve(_serve("tads_residual_rmsnorm_fwd")(x.data_ptr(), y.data_ptr(), _p(ls_gamma), _p(norm_gamma), out.data_ptr(), _p(xn),
+                                                             0 if xn is None else _dt(xn), rows, D, float(eps), _stream()),
+                         "tads_residual_rmsnorm_fwd")
+    return out, xn
+
+
 def mae_target(videos, mask_idx, tubelet, patch, mean, std, normalize_target=True):
     """videos [B,3,T,H,W] f32 (normalised) -> labels [B, Nm, tub*p*p*3] f32 for the masked tokens (engine_for_pretraining.py:51-66)"""
     _req(videos, torch.float32, "mae_target.videos")

@@ -1472,6 +1472,69 @@ class VisibleTokensFn(_Fn):
         return dx, (None if dpos is None else dpos.reshape(ctx.pos.shape)), None
 
 
+# The entry of the InternVideo2 encoder and the evaluation tail of its half blocks (internvideo2.py): csrc/iv2_serve.hip through the
+# serving ABI (include/tad_mi355x_serve.h, libtad_mi355x_serve.so).
+_iv2_serve_kernels = True
+
+
+def set_iv2_serve_kernels(enabled: bool):
+    """A/B switch: ClassTokenEntryFn through its HIP kernels, and the InternVideo2 evaluation forward as one loop over fused
+    residual + RMSNorm launches (default); or, off, the torch ``cat`` + add (autograd's dense sums on the way back) and the per-block
+    module route.  Forward bits of the entry are the same either way; the table's and the class token's gradients are summed over the
+    clips in the order b = 0, 1, ... when on and in torch's order when off.  Sampled by each forward; a node's backward follows its own
+    forward."""
+    global _iv2_serve_kernels
+    _iv2_serve_kernels = bool(enabled)
+
+
+def get_iv2_serve_kernels() -> bool:
+    return _iv2_serve_kernels
+
+
+class ClassTokenEntryFn(_Fn):
+    """``cat((cls_token.expand(B, -1, -1), x), 1) + pos``: x [B,N,D] f32, cls_token [1,1,D], pos [1,N+1,D] (a Parameter, or the table
+    composed of the sep_pos_embed parts: any tensor that may want a gradient) -> [B,N+1,D].  Backward, one launch: the patch rows'
+    gradient (requested only if x wants one) and the sums over the clips in the order b = 0, 1, ... for pos and cls_token (each only if
+    wanted; written straight into the gradient sinks where BOTH wanted ones have a sink, else returned as tensors)."""
+
+    @staticmethod
+    def forward(ctx, x, cls_token, pos):
+        _need_gpu(x, "class token entry")
+        xc, cc, pc = _f32c(x), _f32c(cls_token), _f32c(pos)
+        B, N, D = xc.shape
+        if cc.numel() != D or pc.numel() != (N + 1) * D:
+            raise TadError(f"class token entry: x {tuple(x.shape)}, cls_token {tuple(cls_token.shape)} and pos {tuple(pos.shape)} do not belong together")
+        ctx.kernels = _iv2_serve_kernels
+        ctx.need = _needs(ctx, 3)
+        ctx.params = (cls_token, pos)
+        ctx.meta = (B, N, D)
+        if ctx.kernels:
+            return K.class_token_entry_fwd(xc, cc.reshape(D), pc.reshape(N + 1, D))
+        return torch.cat((cc.reshape(1, 1, D).expand(B, -1, -1), xc), dim=1) + pc.reshape(1, N + 1, D)
+
+    @staticmethod
+    def backward(ctx, g):
+        B, N, D = ctx.meta
+        cls_token, pos = ctx.params
+        gc = _f32c(g)
+        need_x, need_cls, need_pos = ctx.need
+        if not ctx.kernels:
+            return ((gc[:, 1:].contiguous() if need_x else None), (gc[:, :1].sum(0, keepdim=True).reshape(cls_token.shape) if need_cls else None),
+                    (gc.sum(0, keepdim=True).reshape(pos.shape) if need_pos else None))
+        if not (need_x or need_cls or need_pos):
+            return None, None, None
+        ent_c, ent_p = (_sink(cls_token) if need_cls else None), (_sink(pos) if need_pos else None)
+        if need_cls and need_pos and (ent_c is None) != (ent_p is None):
+            ent_c = ent_p = None  # (one accumulate flag in the kernel: a lone sink gets its gradient from autograd)
+        dx, dpos, dcls = K.class_token_entry_bwd(gc, want_dpatch=need_x, want_dpos=need_pos, want_dcls=need_cls,
+                                                 into_pos=None if ent_p is None else ent_p[1], into_cls=None if ent_c is None else ent_c[1])
+        for ent, p in ((ent_c, cls_token), (ent_p, pos)):
+            if ent is not None and ent[2] is not None:
+                ent[2](p)
+        return (dx, (None if dcls is None or ent_c is not None else dcls.reshape(cls_token.shape)),
+                (None if dpos is None or ent_p is not None else dpos.reshape(pos.shape)))
+
+
 class MseLossFn(_Fn):
     """nn.MSELoss()(outputs, labels) (engine_for_pretraining.py:27,70): loss and d(loss)/d(outputs) in one pass"""
 
