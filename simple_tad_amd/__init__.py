@@ -14,6 +14,8 @@ from . import sequencing, frame_store, frame_resize, prefetch
 from .prefetch import ClipPrefetcher
 from . import explain
 from .explain import attention_rollout, attention_received, token_rollout, saliency_to_frames
+from .reconstruct import reconstruct, error_to_frames  # (the function takes the module's name in this namespace)
+from .engine_pretrain import evaluate_one_epoch
 from .frame_resize import PadWideClips, resize_frames
 from .frame_store import FrameStore, FrameWindows, StoreViews
 from .mixup import Mixup
@@ -27,4 +29,5 @@ from .modeling_finetune import (VisionTransformer, PatchEmbed, Block, Attention,
                                 get_sinusoid_encoding_table)
 
 __all__ = ["set_precision", "get_precision", "TuningScope", "create_model", "register_model", "list_models", "modeling_finetune", "VisionTransformer", "PatchEmbed", "Block",
-           "Attention", "Mlp", "DropPath", "get_sinusoid_encoding_table", "mixup", "loss", "random_erasing", "rand_augment", "Mixup", "RandomErasing", "RandAugment", "create_random_augment", "rand_augment_transform", "frames_to_clip", "transforms", "GroupMultiScaleCrop", "DataAugmentationForVideoMAE", "DataAugmentationForVideoMAE_LightCrop", "spatial_sampling", "SpatialSampling", "SoftTargetCrossEntropy", "LabelSmoothingCrossEntropy", "FocalLoss", "FocalLoss2", "SmoothAPLoss", "TemporalExponentialLoss", "DoubleBCELoss", "build_criterion", "frame_targets", "grad_norms", "GradNormCollector", "sequencing", "frame_store", "frame_resize", "PadWideClips", "resize_frames", "FrameStore", "FrameWindows", "StoreViews", "prefetch", "ClipPrefetcher", "explain", "attention_rollout", "attention_received", "token_rollout", "saliency_to_frames"]
+           "Attention", "Mlp", "DropPath", "get_sinusoid_encoding_table", "mixup", "loss", "random_erasing", "rand_augment", "Mixup", "RandomErasing", "RandAugment", "create_random_augment", "rand_augment_transform", "frames_to_clip", "transforms", "GroupMultiScaleCrop", "DataAugmentationForVideoMAE", "DataAugmentationForVideoMAE_LightCrop", "spatial_sampling", "SpatialSampling", "SoftTargetCrossEntropy", "LabelSmoothingCrossEntropy", "FocalLoss", "FocalLoss2", "SmoothAPLoss", "TemporalExponentialLoss", "DoubleBCELoss", "build_criterion", "frame_targets", "grad_norms", "GradNormCollector", "sequencing", "frame_store", "frame_resize", "PadWideClips", "resize_frames", "FrameStore", "FrameWindows", "StoreViews", "prefetch", "ClipPrefetcher", "explain", "attention_rollout", "attention_received", "token_rollout", "saliency_to_frames", "reconstruct", "error_to_frames",
+           "evaluate_one_epoch"]

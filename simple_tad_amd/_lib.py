@@ -180,6 +180,16 @@ SERVE_SIGNATURES = {
     "tads_residual_rmsnorm_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _f, _vp]),
 }
 SERVE_ABI_VERSION = 1
+
+# The reconstruction ABI (include/tad_mi355x_recon.h): the fifth surface, tadr_*, in a library of its own -- libtad_mi355x_recon.so, loaded
+# beside the other two (every older surface is held where it is).  It keeps its own error text (tadr_last_error_string; check_recon).
+RECON_LIB_PATH = os.path.join(_HERE, "libtad_mi355x_recon.so")
+RECON_SIGNATURES = {
+    "tadr_abi_version": (_i, []),
+    "tadr_last_error_string": (C.c_char_p, []),
+    "tadr_mae_reconstruct": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _i, _f, _vp]),
+}
+RECON_ABI_VERSION = 1
 LINEAR_PLAN_FIELDS = ("r0", "rows", "kernel", "persistent", "direct", "grid", "block", "group_m", "sk_splits", "sk_mode", "epilogue")
 ATTN_PLAN_FIELDS = ("kernel", "hd", "out16", "qs", "drop", "dma_mode", "skip", "has_lo", "grid", "block")
 ATTN_FWD, ATTN_FWD_Q64, ATTN_BWD_DQ, ATTN_BWD_DKV = range(4)  # the "kernel" field
@@ -240,6 +250,7 @@ def load() -> C.CDLL:
     if v != PRETRAIN_ABI_VERSION:
         raise TadError(f"pre-training ABI mismatch: library reports {v}, binding expects {PRETRAIN_ABI_VERSION}")
     _load_serve()
+    _load_recon()
     _lib = lib
     return lib
 
@@ -279,6 +290,44 @@ def load_serve() -> C.CDLL:
 def check_serve(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = load_serve().tads_last_error_string()
+        raise TadError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
+
+
+_recon = None
+
+
+def _load_recon() -> C.CDLL:
+    global _recon
+    if _recon is not None:
+        return _recon
+    if not os.path.exists(RECON_LIB_PATH):
+        raise TadError(
+            f"{RECON_LIB_PATH} not found: the reconstruction library has not been built. Run `python -m simple_tad_amd.build` "
+            "(or __graft_entry__.build()). There is no CPU fallback for the MI355X path.")
+    lib = C.CDLL(RECON_LIB_PATH)
+    for name, (res, args) in RECON_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:  # pragma: no cover
+            raise TadError(f"{RECON_LIB_PATH} does not export {name}") from e
+        fn.restype = res
+        fn.argtypes = args
+    v = lib.tadr_abi_version()
+    if v != RECON_ABI_VERSION:
+        raise TadError(f"reconstruction ABI mismatch: library reports {v}, binding expects {RECON_ABI_VERSION}")
+    _recon = lib
+    return lib
+
+
+def load_recon() -> C.CDLL:
+    """the reconstruction library (tadr_*); loaded, and checked, together with the first one"""
+    load()
+    return _recon
+
+
+def check_recon(rc: int, what: str = "") -> None:
+    if rc != 0:
+        msg = load_recon().tadr_last_error_string()
         raise TadError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
 
 

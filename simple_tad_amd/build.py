@@ -1,4 +1,4 @@
-"""Build libtad_mi355x.so and libtad_mi355x_serve.so (gfx950) in-tree with hipcc.  `python -m simple_tad_amd.build [--force]`."""
+"""Build libtad_mi355x.so, libtad_mi355x_serve.so and libtad_mi355x_recon.so (gfx950) in-tree with hipcc.  `python -m simple_tad_amd.build [--force]`."""
 import os
 import subprocess
 import sys
@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 # library: without TAD_BUILD_LIB it builds build_exp/libtad_ablation.so in its own object directory.
 _ABLATION = os.environ.get("TAD_BUILD_ABLATION") == "1"
 _LIB_NAME = os.environ.get("TAD_BUILD_LIB", "libtad_ablation.so" if _ABLATION else "libtad_mi355x.so")
-# The production library and the serving library beside it (SERVE_LIB below) are the ONLY built files in the package directory; every experiment / ablation build (and its objects) goes to
+# The production library and the serving and reconstruction libraries beside it (SERVE_LIB, RECON_LIB below) are the ONLY built files in the package directory; every experiment / ablation build (and its objects) goes to
 # <repo>/build_exp/ -- git-ignored like every built artefact, but not gpurun-ignored, so it travels to the GPU box with the snapshot.
 EXP_DIR = os.path.join(os.path.dirname(HERE), "build_exp")
 _PRODUCTION = _LIB_NAME == "libtad_mi355x.so"
@@ -48,6 +48,11 @@ NO_FP_CONTRACT = {"ema.hip", "mixup.hip", "randaug.hip", "multiscale_crop.hip", 
 SERVE_LIB = os.path.join(HERE, "libtad_mi355x_serve.so")
 SERVE_SOURCES = ["iv2_serve.hip"]
 EXTRA_DEPS["iv2_serve.hip"] = ["rownorm.h", "../../include/tad_mi355x_serve.h"]
+# The reconstruction library (include/tad_mi355x_recon.h, tadr_*): the fifth surface, linked apart for the same reason and in the same way
+# (the serving library is held at its one source).  mae.hip's object code is not touched: the statistics are restated in the new source.
+RECON_LIB = os.path.join(HERE, "libtad_mi355x_recon.so")
+RECON_SOURCES = ["mae_reconstruct.hip"]
+EXTRA_DEPS["mae_reconstruct.hip"] = ["../../include/tad_mi355x_recon.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wno-unused-result",
          # keep MFMA accumulators in the (unified) VGPR file: without it the compiler parks them in AGPRs and pays a
          # v_accvgpr_read/write per element around every softmax / epilogue
@@ -70,22 +75,24 @@ def _deps_mtime():
 
 
 def build(force: bool = False, verbose: bool = True) -> str:
-    """build what is stale: the library (returned) and, in a production build, the serving library beside it"""
+    """build what is stale: the library (returned) and, in a production build, the serving and reconstruction libraries beside it"""
     lib = _build_core(force, verbose)
     if _PRODUCTION:
-        _build_serve(force, verbose)
+        _build_side(SERVE_LIB, SERVE_SOURCES, force, verbose)
+        _build_side(RECON_LIB, RECON_SOURCES, force, verbose)
     return lib
 
 
-def _build_serve(force: bool, verbose: bool) -> str:
-    if not force and os.path.exists(SERVE_LIB) and os.path.getmtime(SERVE_LIB) >= _deps_mtime():
-        return SERVE_LIB
+def _build_side(lib: str, sources, force: bool, verbose: bool) -> str:
+    """a self-contained library beside the first one: its own source list, FLAGS plus hidden visibility"""
+    if not force and os.path.exists(lib) and os.path.getmtime(lib) >= _deps_mtime():
+        return lib
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     hipcc = _hipcc()
     headers = [os.path.join(CSRC, "common.h"), os.path.join(os.path.dirname(HERE), "include", "tad_mi355x.h")]
     objs = []
-    for src in SERVE_SOURCES:
+    for src in sources:
         obj, srcp = os.path.join(objdir, src.replace(".hip", ".o")), os.path.join(CSRC, src)
         deps = [srcp, *headers, *[os.path.join(CSRC, d) for d in EXTRA_DEPS.get(src, [])]]
         objs.append(obj)
@@ -95,11 +102,11 @@ def _build_serve(force: bool, verbose: bool) -> str:
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-fvisibility=hidden", "-o", SERVE_LIB, *objs]
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-fvisibility=hidden", "-o", lib, *objs]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.run(cmd, check=True)
-    return SERVE_LIB
+    return lib
 
 
 def _build_core(force: bool = False, verbose: bool = True) -> str:

@@ -15,7 +15,7 @@ import torch
 
 from . import kernels as K
 from . import ops
-from .modeling_pretrain import token_indices
+from .modeling_pretrain import slot_table, token_indices
 from .parallel import DataParallel
 
 IMAGENET_DEFAULT_MEAN = (0.485, 0.456, 0.406)  # timm.data.constants, engine_for_pretraining.py:10
@@ -97,6 +97,35 @@ def _joined_batches(data_loader1, data_loader2, device):
             yield (videos,)
 
 
+def masked_count(bool_masked_pos, who) -> int:
+    """the number of tokens every clip of the batch masks; another count in any clip is refused, naming the counts"""
+    # host-side counts (the mask comes from the loader's generator): one read of all clips' counts where clip 0's was read before
+    counts = torch.as_tensor(bool_masked_pos).flatten(1).to(torch.bool).sum(1).tolist()
+    num_masked = int(counts[0])
+    if any(c != num_masked for c in counts):
+        # token_indices splits every clip at clip 0's count: masked tokens of another clip would land among the visible ones
+        # (the reference's x[~mask].reshape(B, -1, C) usually raises here)
+        raise ValueError(f"{who}: the clips of this batch mask different numbers of tokens {counts}; "
+                         "every clip of a batch must mask the same number")
+    return num_masked
+
+
+def _step_inputs(batch, device, augment_fn, who):
+    """(clips on the device, bool masks [B,N] on the device, masked tokens per clip) of one (clips, masks) or (clips,) batch"""
+    videos = batch[0].to(device, non_blocking=True)
+    bool_masked_pos = batch[1] if len(batch) > 1 else None
+    if augment_fn is not None:
+        augmented = augment_fn(videos)
+        videos, bool_masked_pos = augmented if isinstance(augmented, (tuple, list)) else (augmented, bool_masked_pos)
+    if bool_masked_pos is None:
+        raise ValueError(f"{who}: no masks for this step: the batch holds one item and augment_fn "
+                         + ("returned the clips alone" if augment_fn is not None else "is None")
+                         + " (pass (clips, masks) batches, or an augment_fn that returns (clips, masks))")
+    num_masked = masked_count(bool_masked_pos, who)
+    bool_masked_pos = torch.as_tensor(bool_masked_pos).to(device, non_blocking=True).flatten(1).to(torch.bool)
+    return videos, bool_masked_pos, num_masked
+
+
 def _train_one_epoch(model, data_loader, optimizer, device, epoch, loss_scaler, max_norm, patch_size, normlize_target, start_steps,
                      lr_schedule_values, wd_schedule_values, tubelet_size, log, augment_fn, grad_norms, who="train_one_epoch"):
     """``data_loader``: the step iterator -- anything that yields (clips, masks) or (clips,) batches, one per step"""
@@ -115,24 +144,7 @@ def _train_one_epoch(model, data_loader, optimizer, device, epoch, loss_scaler, 
                     group["lr"] = lr_schedule_values[it] * group.get("lr_scale", 1.0)
                 if wd_schedule_values is not None and group["weight_decay"] > 0:
                     group["weight_decay"] = wd_schedule_values[it]
-        videos = batch[0].to(device, non_blocking=True)
-        bool_masked_pos = batch[1] if len(batch) > 1 else None
-        if augment_fn is not None:
-            augmented = augment_fn(videos)
-            videos, bool_masked_pos = augmented if isinstance(augmented, (tuple, list)) else (augmented, bool_masked_pos)
-        if bool_masked_pos is None:
-            raise ValueError(f"{who}: no masks for this step: the batch holds one item and augment_fn "
-                             + ("returned the clips alone" if augment_fn is not None else "is None")
-                             + " (pass (clips, masks) batches, or an augment_fn that returns (clips, masks))")
-        # host-side counts (the mask comes from the loader's generator): one read of all clips' counts where clip 0's was read before
-        counts = torch.as_tensor(bool_masked_pos).flatten(1).to(torch.bool).sum(1).tolist()
-        num_masked = int(counts[0])
-        if any(c != num_masked for c in counts):
-            # token_indices splits every clip at clip 0's count: masked tokens of another clip would land among the visible ones
-            # (the reference's x[~mask].reshape(B, -1, C) usually raises here)
-            raise ValueError(f"{who}: the clips of this batch mask different numbers of tokens {counts}; "
-                             "every clip of a batch must mask the same number")
-        bool_masked_pos = torch.as_tensor(bool_masked_pos).to(device, non_blocking=True).flatten(1).to(torch.bool)
+        videos, bool_masked_pos, num_masked = _step_inputs(batch, device, augment_fn, who)
         with torch.no_grad():
             labels = reconstruction_target(videos, bool_masked_pos, patch_size, tubelet_size, normlize_target, num_masked)
         outputs = inner(videos, bool_masked_pos, num_masked=num_masked) if dp is None else dp(videos, bool_masked_pos, num_masked=num_masked)
@@ -162,3 +174,40 @@ def _train_one_epoch(model, data_loader, optimizer, device, epoch, loss_scaler, 
     if grad_norms is not None:
         stats["grad_norms"] = grad_norms.result(len(data_loader))
     return stats
+
+
+def evaluate_one_epoch(model: torch.nn.Module, data_loader: Iterable, device: torch.device, patch_size: int = 16, normlize_target: bool = True,
+                       tubelet_size: int = 2, augment_fn=None):
+    """The held-out pass of MAE pre-training (the reference has none): the batches go through the batch handling and the mask-count check
+    of the training step, the model runs in eval mode under ``no_grad``, and no optimizer is involved.  Per batch the loss is the
+    training step's (``reconstruction_target`` and the ``tad_mse_loss`` launch) and the per-token error comes from the reconstruction
+    kernel (``kernels.mae_reconstruct``, err only).  The running sums stay on the device; they are read back once, at the end.
+
+    Returns {"loss": the mean of the batches' losses, "error_grid": f32 [T/tub, H/p, W/p] on the host: per grid position the mean error
+    over the clips that masked it (0 where no clip did)}.  The model's mode is put back afterwards."""
+    inner = model.module if isinstance(model, DataParallel) else model
+    was_training = inner.training
+    inner.eval()
+    sums, steps = None, 0
+    try:
+        with torch.no_grad():
+            for batch in data_loader:
+                videos, bool_masked_pos, num_masked = _step_inputs(batch, device, augment_fn, "evaluate_one_epoch")
+                labels = reconstruction_target(videos, bool_masked_pos, patch_size, tubelet_size, normlize_target, num_masked)
+                outputs = inner(videos, bool_masked_pos, num_masked=num_masked)
+                loss = ops.MseLossFn.apply(outputs, labels)
+                slot, _ = slot_table(bool_masked_pos, num_masked)
+                _, err = K.mae_reconstruct(videos.float().contiguous(), outputs.float().contiguous(), slot, tubelet_size, patch_size,
+                                           IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD, normlize_target, want_frames=False)
+                # one row of running sums: [loss, err per position ..., masked clips per position ...]
+                row = torch.cat([loss.reshape(1), err.sum(0), bool_masked_pos.sum(0).float()])
+                sums = row if sums is None else sums + row
+                steps += 1
+                grid = (videos.shape[2] // tubelet_size, videos.shape[3] // patch_size, videos.shape[4] // patch_size)
+    finally:
+        inner.train(was_training)
+    if sums is None:
+        raise ValueError("evaluate_one_epoch: the loader delivered no batch")
+    host = sums.cpu()
+    n = (host.numel() - 1) // 2
+    return {"loss": host[0].item() / steps, "error_grid": (host[1:1 + n] / host[1 + n:].clamp_min(1.0)).reshape(grid)}

@@ -1797,6 +1797,43 @@ def mae_target(videos, mask_idx, tubelet, patch, mean, std, normalize_target=Tru
     return labels
 
 
+def mae_reconstruct(videos, pred, slot, tubelet, patch, mean, std, normalize_target=True, visible_gain=1.0, want_frames=True,
+                    want_err=True):
+    """(frames uint8 [B,T,H,W,3] | None, err f32 [B,N] | None): the inverse of ``mae_target``, one launch.  videos [B,3,T,H,W] f32
+    (normalised); pred [B, Nm, tub*p*p*3] f32 in mae_target's layout (None or empty: nothing is masked); slot [B,N] int32: the row of
+    pred inside its clip that predicts the token, -1 = visible.  Visible patches are the clip's own pixels times ``visible_gain``,
+    masked ones the prediction, de-standardised with the patch's statistics when ``normalize_target``; err is the token's mean
+    (pred - target)^2, 0 where it is visible.  The reconstruction ABI, include/tad_mi355x_recon.h."""
+    _req(videos, torch.float32, "mae_reconstruct.videos")
+    _idx(slot, "mae_reconstruct.slot")
+    if videos.dim() != 5 or videos.shape[1] != 3:
+        raise _lib.TadError(f"mae_reconstruct: videos {tuple(videos.shape)} is no [B,3,T,H,W] clip")
+    B, _, T, H, W = videos.shape
+    if slot.dim() != 2 or slot.shape[0] != B:
+        raise _lib.TadError(f"mae_reconstruct: slot {tuple(slot.shape)} is no [B={B}, N] table")
+    N = slot.shape[1]
+    Nm = 0
+    if pred is not None and pred.numel():
+        _req(pred, torch.float32, "mae_reconstruct.pred")
+        width = tubelet * patch * patch * 3
+        if pred.numel() % (B * width):
+            raise _lib.TadError(f"mae_reconstruct: pred {tuple(pred.shape)} is no [B={B}, n_mask, {width}] prediction")
+        Nm = pred.numel() // (B * width)
+    else:
+        pred = None
+    if not (want_frames or want_err):
+        raise _lib.TadError("mae_reconstruct: neither frames nor err is wanted")
+    if tubelet > 0 and patch > 0 and (T // tubelet) * (H // patch) * (W // patch) != N:
+        raise _lib.TadError(f"mae_reconstruct: slot has {N} columns, the clip {(T // tubelet) * (H // patch) * (W // patch)} tokens")
+    frames = torch.empty((B, T, H, W, 3), dtype=torch.uint8, device=videos.device) if want_frames else None
+    err = torch.empty((B, N), dtype=torch.float32, device=videos.device) if want_err else None
+    with _timed("mae_reconstruct", 0.0, 4.0 * videos.numel() + 4.0 * B * Nm * tubelet * patch * patch * 3 + (videos.numel() if want_frames else 0)):
+        _lib.check_recon(_lib.load_recon().tadr_mae_reconstruct(videos.data_ptr(), _p(pred), slot.data_ptr(), _p(frames), _p(err), B, Nm, T, H, W,
+                                                                 int(tubelet), int(patch), _f3(mean), _f3(std), int(bool(normalize_target)),
+                                                                 float(visible_gain), _stream()), "tadr_mae_reconstruct")
+    return frames, err
+
+
 def mse_loss(pred, target, want_grad=True):
     """returns (loss scalar tensor, grad|None) of nn.MSELoss()(pred, target)"""
     _req(pred, torch.float32, "mse.pred")

@@ -59,6 +59,18 @@ def token_indices(mask: torch.Tensor, num_masked=None):
     return order[:, :nv].contiguous(), order[:, nv:].contiguous()
 
 
+def slot_table(mask: torch.Tensor, num_masked=None):
+    """bool mask [B,N] (True = masked) -> (slot int32 [B,N], mask_tok int32 [B,Nm]): slot[b, tok] is the row of the clip's prediction
+    that belongs to token tok -- the position of tok in ``token_indices``' ascending masked list, the order the model's output rows come
+    in -- and -1 where the token is visible.  A ``scatter_`` of ``arange`` into a table of -1: no device sync when ``num_masked`` is given."""
+    _, mask_tok = token_indices(mask, num_masked)
+    B, N = mask.shape
+    Nm = mask_tok.shape[1]
+    slot = torch.full((B, N), -1, dtype=torch.int32, device=mask.device)
+    slot.scatter_(1, mask_tok.long(), torch.arange(Nm, dtype=torch.int32, device=mask.device).expand(B, Nm))
+    return slot, mask_tok
+
+
 class PretrainVisionTransformerEncoder(nn.Module):
     """modeling_pretrain.py:27-113"""
 
