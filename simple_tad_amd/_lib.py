@@ -190,6 +190,18 @@ RECON_SIGNATURES = {
     "tadr_mae_reconstruct": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _i, _f, _vp]),
 }
 RECON_ABI_VERSION = 1
+
+# The stream-bank ABI (include/tad_mi355x_bank.h): the sixth surface, tadb_*, in a library of its own -- libtad_mi355x_bank.so, loaded
+# beside the other three.  It keeps its own error text (tadb_last_error_string; check_bank).
+BANK_LIB_PATH = os.path.join(_HERE, "libtad_mi355x_bank.so")
+BANK_SIGNATURES = {
+    "tadb_abi_version": (_i, []),
+    "tadb_last_error_string": (C.c_char_p, []),
+    "tadb_ingest_plan_check": (_i, [_vp, _i64, _i, _i, _i, _i64, _i64, _i, _i]),
+    "tadb_ingest_frames": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
+}
+BANK_ABI_VERSION = 1
+BANK_ROW_WORDS, BANK_MAX_FRAMES, BANK_MAX_SETS, BANK_MAX_EXTENT, BANK_SWAP_RB = 8, 4096, 64, 32768, 1
 LINEAR_PLAN_FIELDS = ("r0", "rows", "kernel", "persistent", "direct", "grid", "block", "group_m", "sk_splits", "sk_mode", "epilogue")
 ATTN_PLAN_FIELDS = ("kernel", "hd", "out16", "qs", "drop", "dma_mode", "skip", "has_lo", "grid", "block")
 ATTN_FWD, ATTN_FWD_Q64, ATTN_BWD_DQ, ATTN_BWD_DKV = range(4)  # the "kernel" field
@@ -251,6 +263,7 @@ def load() -> C.CDLL:
         raise TadError(f"pre-training ABI mismatch: library reports {v}, binding expects {PRETRAIN_ABI_VERSION}")
     _load_serve()
     _load_recon()
+    _load_bank()
     _lib = lib
     return lib
 
@@ -328,6 +341,44 @@ def load_recon() -> C.CDLL:
 def check_recon(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = load_recon().tadr_last_error_string()
+        raise TadError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
+
+
+_bank = None
+
+
+def _load_bank() -> C.CDLL:
+    global _bank
+    if _bank is not None:
+        return _bank
+    if not os.path.exists(BANK_LIB_PATH):
+        raise TadError(
+            f"{BANK_LIB_PATH} not found: the stream-bank library has not been built. Run `python -m simple_tad_amd.build` "
+            "(or __graft_entry__.build()). There is no CPU fallback for the MI355X path.")
+    lib = C.CDLL(BANK_LIB_PATH)
+    for name, (res, args) in BANK_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:  # pragma: no cover
+            raise TadError(f"{BANK_LIB_PATH} does not export {name}") from e
+        fn.restype = res
+        fn.argtypes = args
+    v = lib.tadb_abi_version()
+    if v != BANK_ABI_VERSION:
+        raise TadError(f"stream-bank ABI mismatch: library reports {v}, binding expects {BANK_ABI_VERSION}")
+    _bank = lib
+    return lib
+
+
+def load_bank() -> C.CDLL:
+    """the stream-bank library (tadb_*); loaded, and checked, together with the first one"""
+    load()
+    return _bank
+
+
+def check_bank(rc: int, what: str = "") -> None:
+    if rc != 0:
+        msg = load_bank().tadb_last_error_string()
         raise TadError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
 
 

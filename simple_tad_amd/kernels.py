@@ -1520,6 +1520,62 @@ def frame_resize(x, table, n_vsets: int, S_h: int, S_w: int, mean=None, std=None
     return out
 
 
+# ----------------------------------------------------------------------------- ragged ingest: K frames of K sizes into K slots of a frame store
+def ingest_table(rows, hsets, vsets, src_bytes: int, F: int, S_h: int, S_w: int):
+    """Host-side table of ingest_frames (include/tad_mi355x_bank.h): ``rows`` = one (src_off, h, w, slot, hset, vset, flags) per frame;
+    ``hsets`` / ``vsets`` = [(in, first [out], k [out][4])] towards S_w / S_h outputs, one per distinct width / height
+    (``frame_resize.cubic_coeffs``).  Returns the int32 CPU tensor, checked by tadb_ingest_plan_check (word count, frames inside
+    ``src_bytes`` at multiples of 4, every slot inside [0, F) and named once, sets stated for the extents they serve, taps next to their
+    source, sum |k| <= 2818, known flags); runs without a GPU."""
+    import numpy as np
+    lib = _lib.load_bank()
+    K, nh, nv = len(rows), len(hsets), len(vsets)
+    if not (1 <= K <= _lib.BANK_MAX_FRAMES and 1 <= nh <= _lib.BANK_MAX_SETS and 1 <= nv <= _lib.BANK_MAX_SETS):
+        raise _lib.TadError(f"ingest_table: {K} frames (1 .. {_lib.BANK_MAX_FRAMES}), {nh} horizontal and {nv} vertical sets (1 .. {_lib.BANK_MAX_SETS} each)")
+    if int(S_h) < 1 or int(S_w) < 1:
+        raise _lib.TadError(f"ingest_table: S_h={S_h} S_w={S_w} must be positive")
+    tab = np.zeros(K * _lib.BANK_ROW_WORDS + nh * (_lib.FR_SET_HEAD + 5 * S_w) + nv * (_lib.FR_SET_HEAD + 5 * S_h), dtype=np.int32)
+    r = np.asarray(rows, dtype=np.int64).reshape(K, 7)
+    if (np.abs(r) >= 2 ** 31).any():
+        raise _lib.TadError("ingest_table: a row does not fit 32 bits")
+    tab[:K * _lib.BANK_ROW_WORDS].reshape(K, _lib.BANK_ROW_WORDS)[:, :7] = r
+    at = K * _lib.BANK_ROW_WORDS
+    for sets, out in ((hsets, S_w), (vsets, S_h)):
+        for n_in, first, kk in sets:
+            first, kk = np.asarray(first, dtype=np.int32), np.asarray(kk, dtype=np.int32)
+            if first.shape != (out,) or kk.shape != (out, 4):
+                raise _lib.TadError(f"ingest_table: a set with first {first.shape} and k {kk.shape} for {out} outputs")
+            tab[at:at + 2] = n_in, out
+            tab[at + _lib.FR_SET_HEAD:at + _lib.FR_SET_HEAD + out] = first
+            tab[at + _lib.FR_SET_HEAD + out:at + _lib.FR_SET_HEAD + 5 * out] = kk.reshape(-1)
+            at += _lib.FR_SET_HEAD + 5 * out
+    _lib.check_bank(lib.tadb_ingest_plan_check(tab.ctypes.data, tab.size, K, nh, nv, int(src_bytes), int(F), int(S_h), int(S_w)),
+                    "tadb_ingest_plan_check")
+    return torch.from_numpy(tab)
+
+
+def ingest_frames(src, src_bytes: int, store, table, K: int, n_hsets: int, n_vsets: int):
+    """Resize the K packed uint8 frames of ``src`` (1-D uint8 on the GPU; frame k is [h_k, w_k, 3] at the multiple of 4 its row of the
+    table names) to the store's S_h x S_w and write each to the slot its row names, as the device table ``table`` (a copy of
+    ingest_table()'s) says: tadb_ingest_frames, ONE launch for frames of any mix of sizes.  ``src`` must hold ``src_bytes`` rounded up to a
+    multiple of 4 (pixels come in as the aligned words that hold them).  store: contiguous uint8 [F,S_h,S_w,3], written in the named slots
+    only.  Returns store."""
+    _req(src, torch.uint8, "ingest_frames.src")
+    _req(store, torch.uint8, "ingest_frames.store")
+    _req(table, torch.int32, "ingest_frames.table")
+    if store.dim() != 4 or store.shape[-1] != 3 or store.numel() == 0:
+        raise _lib.TadError(f"ingest_frames.store: expected a uint8 frame store [F,S_h,S_w,3], got {tuple(store.shape)}")
+    if src.dim() != 1 or table.dim() != 1 or src.device != store.device or table.device != store.device:
+        raise _lib.TadError(f"ingest_frames: src and table must be 1-D tensors on {store.device}")
+    if int(src_bytes) < 1 or src.numel() < (int(src_bytes) + 3) // 4 * 4:
+        raise _lib.TadError(f"ingest_frames.src: {src.numel()} bytes do not hold src_bytes={src_bytes} rounded up to a multiple of 4")
+    F, S_h, S_w, _ = store.shape
+    with _timed("ingest_frames", 0.0, float(src_bytes + K * S_h * S_w * 3)):
+        _lib.check_bank(_lib.load_bank().tadb_ingest_frames(src.data_ptr(), int(src_bytes), store.data_ptr(), F, table.data_ptr(), table.numel(),
+                                                            int(K), int(n_hsets), int(n_vsets), S_h, S_w, _stream()), "tadb_ingest_frames")
+    return store
+
+
 # ----------------------------------------------------------------------------- fine-tune spatial sampling: window, bilinear resize, crop, flip
 def spatial_sample_table(rows, B: int, T: int, H: int, W: int, S: int):
     """Host-side table of spatial_sample (include/tad_mi355x.h): ``rows`` = one (sample, i, j, h, w, rh, rw, oy, ox, flip) per (clip,
