@@ -19,7 +19,7 @@ from .engine_pretrain import evaluate_one_epoch
 from .frame_resize import PadWideClips, resize_frames
 from .frame_store import FrameStore, FrameWindows, StoreViews
 from . import stream_bank
-from .stream_bank import StreamBank
+from .stream_bank import StreamBank, YuvFrame
 from .mixup import Mixup
 from .random_erasing import RandomErasing
 from .rand_augment import RandAugment, create_random_augment, frames_to_clip, rand_augment_transform
@@ -31,5 +31,5 @@ from .modeling_finetune import (VisionTransformer, PatchEmbed, Block, Attention,
                                 get_sinusoid_encoding_table)
 
 __all__ = ["set_precision", "get_precision", "TuningScope", "create_model", "register_model", "list_models", "modeling_finetune", "VisionTransformer", "PatchEmbed", "Block",
-           "Attention", "Mlp", "DropPath", "get_sinusoid_encoding_table", "mixup", "loss", "random_erasing", "rand_augment", "Mixup", "RandomErasing", "RandAugment", "create_random_augment", "rand_augment_transform", "frames_to_clip", "transforms", "GroupMultiScaleCrop", "DataAugmentationForVideoMAE", "DataAugmentationForVideoMAE_LightCrop", "spatial_sampling", "SpatialSampling", "SoftTargetCrossEntropy", "LabelSmoothingCrossEntropy", "FocalLoss", "FocalLoss2", "SmoothAPLoss", "TemporalExponentialLoss", "DoubleBCELoss", "build_criterion", "frame_targets", "grad_norms", "GradNormCollector", "sequencing", "frame_store", "frame_resize", "PadWideClips", "resize_frames", "FrameStore", "FrameWindows", "StoreViews", "prefetch", "ClipPrefetcher", "explain", "attention_rollout", "attention_received", "token_rollout", "saliency_to_frames", "reconstruct", "error_to_frames", "stream_bank", "StreamBank",
+           "Attention", "Mlp", "DropPath", "get_sinusoid_encoding_table", "mixup", "loss", "random_erasing", "rand_augment", "Mixup", "RandomErasing", "RandAugment", "create_random_augment", "rand_augment_transform", "frames_to_clip", "transforms", "GroupMultiScaleCrop", "DataAugmentationForVideoMAE", "DataAugmentationForVideoMAE_LightCrop", "spatial_sampling", "SpatialSampling", "SoftTargetCrossEntropy", "LabelSmoothingCrossEntropy", "FocalLoss", "FocalLoss2", "SmoothAPLoss", "TemporalExponentialLoss", "DoubleBCELoss", "build_criterion", "frame_targets", "grad_norms", "GradNormCollector", "sequencing", "frame_store", "frame_resize", "PadWideClips", "resize_frames", "FrameStore", "FrameWindows", "StoreViews", "prefetch", "ClipPrefetcher", "explain", "attention_rollout", "attention_received", "token_rollout", "saliency_to_frames", "reconstruct", "error_to_frames", "stream_bank", "StreamBank", "YuvFrame",
            "evaluate_one_epoch"]

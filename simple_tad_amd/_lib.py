@@ -202,6 +202,18 @@ BANK_SIGNATURES = {
 }
 BANK_ABI_VERSION = 1
 BANK_ROW_WORDS, BANK_MAX_FRAMES, BANK_MAX_SETS, BANK_MAX_EXTENT, BANK_SWAP_RB = 8, 4096, 64, 32768, 1
+
+# The YUV-ingest ABI (include/tad_mi355x_yuv.h): the seventh surface, tady_*, in a library of its own -- libtad_mi355x_yuv.so, loaded
+# beside the other four.  It keeps its own error text (tady_last_error_string; check_yuv).
+YUV_LIB_PATH = os.path.join(_HERE, "libtad_mi355x_yuv.so")
+YUV_SIGNATURES = {
+    "tady_abi_version": (_i, []),
+    "tady_last_error_string": (C.c_char_p, []),
+    "tady_ingest_plan_check": (_i, [_vp, _i64, _i, _i, _i, _i, _i64, _i64, _i, _i]),
+    "tady_ingest_yuv": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp]),
+}
+YUV_ABI_VERSION = 1
+YUV_ROW_WORDS, YUV_CSET_WORDS, YUV_MAX_FRAMES, YUV_MAX_SETS, YUV_MAX_CSETS, YUV_MAX_EXTENT, YUV_BGR = 16, 8, 4096, 64, 16, 32768, 1
 LINEAR_PLAN_FIELDS = ("r0", "rows", "kernel", "persistent", "direct", "grid", "block", "group_m", "sk_splits", "sk_mode", "epilogue")
 ATTN_PLAN_FIELDS = ("kernel", "hd", "out16", "qs", "drop", "dma_mode", "skip", "has_lo", "grid", "block")
 ATTN_FWD, ATTN_FWD_Q64, ATTN_BWD_DQ, ATTN_BWD_DKV = range(4)  # the "kernel" field
@@ -264,6 +276,7 @@ def load() -> C.CDLL:
     _load_serve()
     _load_recon()
     _load_bank()
+    _load_yuv()
     _lib = lib
     return lib
 
@@ -379,6 +392,44 @@ def load_bank() -> C.CDLL:
 def check_bank(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = load_bank().tadb_last_error_string()
+        raise TadError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
+
+
+_yuv = None
+
+
+def _load_yuv() -> C.CDLL:
+    global _yuv
+    if _yuv is not None:
+        return _yuv
+    if not os.path.exists(YUV_LIB_PATH):
+        raise TadError(
+            f"{YUV_LIB_PATH} not found: the YUV-ingest library has not been built. Run `python -m simple_tad_amd.build` "
+            "(or __graft_entry__.build()). There is no CPU fallback for the MI355X path.")
+    lib = C.CDLL(YUV_LIB_PATH)
+    for name, (res, args) in YUV_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:  # pragma: no cover
+            raise TadError(f"{YUV_LIB_PATH} does not export {name}") from e
+        fn.restype = res
+        fn.argtypes = args
+    v = lib.tady_abi_version()
+    if v != YUV_ABI_VERSION:
+        raise TadError(f"YUV-ingest ABI mismatch: library reports {v}, binding expects {YUV_ABI_VERSION}")
+    _yuv = lib
+    return lib
+
+
+def load_yuv() -> C.CDLL:
+    """the YUV-ingest library (tady_*); loaded, and checked, together with the first one"""
+    load()
+    return _yuv
+
+
+def check_yuv(rc: int, what: str = "") -> None:
+    if rc != 0:
+        msg = load_yuv().tady_last_error_string()
         raise TadError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
 
 

@@ -1,4 +1,4 @@
-"""Build libtad_mi355x.so, libtad_mi355x_serve.so, libtad_mi355x_recon.so and libtad_mi355x_bank.so (gfx950) in-tree with hipcc.  `python -m simple_tad_amd.build [--force]`."""
+"""Build libtad_mi355x.so, libtad_mi355x_serve.so, libtad_mi355x_recon.so, libtad_mi355x_bank.so and libtad_mi355x_yuv.so (gfx950) in-tree with hipcc.  `python -m simple_tad_amd.build [--force]`."""
 import os
 import subprocess
 import sys
@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 # library: without TAD_BUILD_LIB it builds build_exp/libtad_ablation.so in its own object directory.
 _ABLATION = os.environ.get("TAD_BUILD_ABLATION") == "1"
 _LIB_NAME = os.environ.get("TAD_BUILD_LIB", "libtad_ablation.so" if _ABLATION else "libtad_mi355x.so")
-# The production library and the serving, reconstruction and stream-bank libraries beside it (SERVE_LIB, RECON_LIB, BANK_LIB below) are the ONLY built files in the package directory; every experiment / ablation build (and its objects) goes to
+# The production library and the serving, reconstruction, stream-bank and YUV-ingest libraries beside it (SERVE_LIB, RECON_LIB, BANK_LIB, YUV_LIB below) are the ONLY built files in the package directory; every experiment / ablation build (and its objects) goes to
 # <repo>/build_exp/ -- git-ignored like every built artefact, but not gpurun-ignored, so it travels to the GPU box with the snapshot.
 EXP_DIR = os.path.join(os.path.dirname(HERE), "build_exp")
 _PRODUCTION = _LIB_NAME == "libtad_mi355x.so"
@@ -58,6 +58,11 @@ EXTRA_DEPS["mae_reconstruct.hip"] = ["../../include/tad_mi355x_recon.h"]
 BANK_LIB = os.path.join(HERE, "libtad_mi355x_bank.so")
 BANK_SOURCES = ["stream_bank.hip"]
 EXTRA_DEPS["stream_bank.hip"] = ["frame_io.h", "../../include/tad_mi355x_bank.h"]
+# The YUV-ingest library (include/tad_mi355x_yuv.h, tady_*): the seventh surface, linked apart for the same reason and in the same way.
+# stream_bank.hip's object code is not touched: the resize arithmetic is restated in the new source (integers only: no contraction flag).
+YUV_LIB = os.path.join(HERE, "libtad_mi355x_yuv.so")
+YUV_SOURCES = ["yuv_ingest.hip"]
+EXTRA_DEPS["yuv_ingest.hip"] = ["frame_io.h", "../../include/tad_mi355x_yuv.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wno-unused-result",
          # keep MFMA accumulators in the (unified) VGPR file: without it the compiler parks them in AGPRs and pays a
          # v_accvgpr_read/write per element around every softmax / epilogue
@@ -80,12 +85,13 @@ def _deps_mtime():
 
 
 def build(force: bool = False, verbose: bool = True) -> str:
-    """build what is stale: the library (returned) and, in a production build, the serving, reconstruction and stream-bank libraries beside it"""
+    """build what is stale: the library (returned) and, in a production build, the serving, reconstruction, stream-bank and YUV-ingest libraries beside it"""
     lib = _build_core(force, verbose)
     if _PRODUCTION:
         _build_side(SERVE_LIB, SERVE_SOURCES, force, verbose)
         _build_side(RECON_LIB, RECON_SOURCES, force, verbose)
         _build_side(BANK_LIB, BANK_SOURCES, force, verbose)
+        _build_side(YUV_LIB, YUV_SOURCES, force, verbose)
     return lib
 
 

@@ -1576,6 +1576,65 @@ def ingest_frames(src, src_bytes: int, store, table, K: int, n_hsets: int, n_vse
     return store
 
 
+def ingest_yuv_table(rows, hsets, vsets, csets, src_bytes: int, F: int, S_h: int, S_w: int):
+    """Host-side table of ingest_yuv (include/tad_mi355x_yuv.h): ``rows`` = one (y_off, y_pitch, u_off, v_off, c_pitch, c_step, h, w,
+    slot, hset, vset, cset, flags) per frame; ``hsets`` / ``vsets`` as for ingest_table; ``csets`` = [(y_off, cy, cvr, cug, cvg, cub)]
+    (``stream_bank.colour_set``).  Returns the int32 CPU tensor, checked by tady_ingest_plan_check (word count, every plane inside
+    ``src_bytes`` with pitches that hold its rows, every slot inside [0, F) and named once, sets stated for the extents they serve, taps
+    next to their source, sum |k| <= 2818, colour sets inside the int32 bound, known flags); runs without a GPU."""
+    import numpy as np
+    lib = _lib.load_yuv()
+    K, nh, nv, nc = len(rows), len(hsets), len(vsets), len(csets)
+    if not (1 <= K <= _lib.YUV_MAX_FRAMES and 1 <= nh <= _lib.YUV_MAX_SETS and 1 <= nv <= _lib.YUV_MAX_SETS and 1 <= nc <= _lib.YUV_MAX_CSETS):
+        raise _lib.TadError(f"ingest_yuv_table: {K} frames (1 .. {_lib.YUV_MAX_FRAMES}), {nh} horizontal and {nv} vertical sets (1 .. {_lib.YUV_MAX_SETS} each), "
+                            f"{nc} colour sets (1 .. {_lib.YUV_MAX_CSETS})")
+    if int(S_h) < 1 or int(S_w) < 1:
+        raise _lib.TadError(f"ingest_yuv_table: S_h={S_h} S_w={S_w} must be positive")
+    R = _lib.YUV_ROW_WORDS
+    tab = np.zeros(K * R + nh * (_lib.FR_SET_HEAD + 5 * S_w) + nv * (_lib.FR_SET_HEAD + 5 * S_h) + nc * _lib.YUV_CSET_WORDS, dtype=np.int32)
+    r = np.asarray(rows, dtype=np.int64).reshape(K, 13)
+    c = np.asarray(csets, dtype=np.int64).reshape(nc, 6)
+    if (np.abs(r) >= 2 ** 31).any() or (np.abs(c) >= 2 ** 31).any():
+        raise _lib.TadError("ingest_yuv_table: a row or a colour set does not fit 32 bits")
+    tab[:K * R].reshape(K, R)[:, :13] = r
+    at = K * R
+    for sets, out in ((hsets, S_w), (vsets, S_h)):
+        for n_in, first, kk in sets:
+            first, kk = np.asarray(first, dtype=np.int32), np.asarray(kk, dtype=np.int32)
+            if first.shape != (out,) or kk.shape != (out, 4):
+                raise _lib.TadError(f"ingest_yuv_table: a set with first {first.shape} and k {kk.shape} for {out} outputs")
+            tab[at:at + 2] = n_in, out
+            tab[at + _lib.FR_SET_HEAD:at + _lib.FR_SET_HEAD + out] = first
+            tab[at + _lib.FR_SET_HEAD + out:at + _lib.FR_SET_HEAD + 5 * out] = kk.reshape(-1)
+            at += _lib.FR_SET_HEAD + 5 * out
+    tab[at:].reshape(nc, _lib.YUV_CSET_WORDS)[:, :6] = c
+    _lib.check_yuv(lib.tady_ingest_plan_check(tab.ctypes.data, tab.size, K, nh, nv, nc, int(src_bytes), int(F), int(S_h), int(S_w)),
+                   "tady_ingest_plan_check")
+    return torch.from_numpy(tab)
+
+
+def ingest_yuv(src, src_bytes: int, store, table, K: int, n_hsets: int, n_vsets: int, n_csets: int):
+    """Convert the K packed 4:2:0 YUV frames of ``src`` (1-D uint8 on the GPU; the planes of frame k lie where its row of the table
+    says) to 8-bit RGB by the table's colour sets, resize each to the store's S_h x S_w and write it to the slot its row names, as the
+    device table ``table`` (a copy of ingest_yuv_table()'s) says: tady_ingest_yuv, ONE launch for frames of any mix of sizes and
+    layouts.  ``src`` must hold ``src_bytes`` rounded up to a multiple of 4 (samples come in as the aligned words that hold them).
+    store: contiguous uint8 [F,S_h,S_w,3], written in the named slots only.  Returns store."""
+    _req(src, torch.uint8, "ingest_yuv.src")
+    _req(store, torch.uint8, "ingest_yuv.store")
+    _req(table, torch.int32, "ingest_yuv.table")
+    if store.dim() != 4 or store.shape[-1] != 3 or store.numel() == 0:
+        raise _lib.TadError(f"ingest_yuv.store: expected a uint8 frame store [F,S_h,S_w,3], got {tuple(store.shape)}")
+    if src.dim() != 1 or table.dim() != 1 or src.device != store.device or table.device != store.device:
+        raise _lib.TadError(f"ingest_yuv: src and table must be 1-D tensors on {store.device}")
+    if int(src_bytes) < 1 or src.numel() < (int(src_bytes) + 3) // 4 * 4:
+        raise _lib.TadError(f"ingest_yuv.src: {src.numel()} bytes do not hold src_bytes={src_bytes} rounded up to a multiple of 4")
+    F, S_h, S_w, _ = store.shape
+    with _timed("ingest_yuv", 0.0, float(src_bytes + K * S_h * S_w * 3)):
+        _lib.check_yuv(_lib.load_yuv().tady_ingest_yuv(src.data_ptr(), int(src_bytes), store.data_ptr(), F, table.data_ptr(), table.numel(),
+                                                       int(K), int(n_hsets), int(n_vsets), int(n_csets), S_h, S_w, _stream()), "tady_ingest_yuv")
+    return store
+
+
 # ----------------------------------------------------------------------------- fine-tune spatial sampling: window, bilinear resize, crop, flip
 def spatial_sample_table(rows, B: int, T: int, H: int, W: int, S: int):
     """Host-side table of spatial_sample (include/tad_mi355x.h): ``rows`` = one (sample, i, j, h, w, rh, rw, oy, ox, flip) per (clip,

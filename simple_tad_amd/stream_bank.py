@@ -8,6 +8,9 @@ different frame sizes.  ``StreamBank`` keeps S rings in ONE uint8 store ``[S*T, 
   push_raw(ids, frames)   the K newest frames, of ANY mix of sizes, packed into one pinned buffer at 4-byte aligned offsets; ONE copy of
                           the bytes, one of the table, ONE launch (``kernels.ingest_frames``, include/tad_mi355x_bank.h) that resizes each
                           frame (the loader's cv2 INTER_CUBIC resize, ``frame_resize``'s contract bit for bit) into its stream's ring slot
+  push_yuv(ids, frames)   the same for cameras that deliver 4:2:0 YUV surfaces (``YuvFrame``: NV12, NV21, I420, pitched or not): the planes
+                          are packed as they come -- half the bytes of RGB, no conversion on the host -- and converted inside the
+                          resize launch (``kernels.ingest_yuv``, include/tad_mi355x_yuv.h) by a colour set the host states
   predict()               the ready streams as one batch: an ``[A, T]`` table of slots in temporal order, ``model(FrameWindows(store,
                           table))`` -- the route ``score_video`` takes, so both model families are served with no family branch
 
@@ -31,7 +34,7 @@ from . import _lib
 from ._lib import TadError
 from .inference import IMAGENET_MEAN, IMAGENET_STD
 
-__all__ = ["StreamBank", "StreamRings", "plan_ingest"]
+__all__ = ["StreamBank", "StreamRings", "plan_ingest", "YuvFrame", "plan_ingest_yuv", "colour_set", "COLOUR_SETS"]
 
 _HEAD = 64  # slack in front of the first frame and behind the last one in the staging buffers (bytes, a multiple of 4)
 _PRECISE = 'precision "precise" takes the normalised f32 clip (the uint8 input stage feeds the bf16 path)'
@@ -123,6 +126,150 @@ def plan_ingest(extents, slots, swaps, S_h: int, S_w: int, F: int, cache: Option
     return table, offsets, at, len(hsets), len(vsets)
 
 
+# ---------------------------------------------------------------------------------------------------------------- 4:2:0 YUV frames
+# The colour sets {y_off, cy, cvr, cug, cvg, cub} of include/tad_mi355x_yuv.h, 20-bit fixed point.  The kernel knows no colour standard:
+# these integers are what the host states.  "bt601" is the set OpenCV's 8-bit YUV420 -> RGB conversion documents, taken literally (it is
+# rounded from the three-digit matrix 1.164, 1.596, 0.391, 0.813, 2.018, so it is NOT what the derivation below gives for BT.601's luma
+# weights: (16, 1220945, 1673555, -410793, -852458, 2115221)); the other three come from the derivation.
+_KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
+_OPENCV_BT601 = (16, 1220542, 1673527, -409993, -852492, 2116026)
+
+
+def derive_colour_set(kr: float, kb: float, full_range: bool):
+    """The usual Y'CbCr -> R'G'B' matrix of the luma weights (kr, kb) in fp64, times 2^20, rounded to nearest: R = Y + 2 (1 - kr) V',
+    B = Y + 2 (1 - kb) U', G = Y - (2 kb (1 - kb) / kg) U' - (2 kr (1 - kr) / kg) V' with kg = 1 - kr - kb.  Limited range scales luma
+    by 255 / 219 behind an offset of 16 and chroma by 255 / 224; full range by 1 behind no offset."""
+    kg = 1.0 - kr - kb
+    ys, cs = (1.0, 1.0) if full_range else (255.0 / 219.0, 255.0 / 224.0)
+    q = lambda v: int(np.rint(np.float64(v) * (1 << 20)))
+    return (0 if full_range else 16, q(ys), q(2.0 * (1.0 - kr) * cs), q(-2.0 * kb * (1.0 - kb) / kg * cs), q(-2.0 * kr * (1.0 - kr) / kg * cs),
+            q(2.0 * (1.0 - kb) * cs))
+
+
+COLOUR_SETS = {"bt601": _OPENCV_BT601,
+               "bt709": derive_colour_set(*_KR_KB["bt709"], False),
+               "bt601-full": derive_colour_set(*_KR_KB["bt601"], True),
+               "bt709-full": derive_colour_set(*_KR_KB["bt709"], True)}
+
+
+def colour_set_bound(cset) -> int:
+    """the largest magnitude an int32 sum of the conversion can reach under this set: it must stay below 2^31"""
+    _, cy, cvr, cug, cvg, cub = (int(v) for v in cset)
+    return 255 * cy + 128 * max(abs(cvr), abs(cub), abs(cug) + abs(cvg)) + (1 << 19)
+
+
+def colour_set(matrix):
+    """the six integers of a colour set: a name of COLOUR_SETS, or six integers of the caller's own (checked against the int32 bound)"""
+    if isinstance(matrix, str):
+        if matrix not in COLOUR_SETS:
+            raise TadError(f"colour_set: unknown matrix {matrix!r}: one of {sorted(COLOUR_SETS)} or six integers")
+        return COLOUR_SETS[matrix]
+    c = tuple(int(v) for v in matrix)
+    if len(c) != 6:
+        raise TadError(f"colour_set: a set is six integers (y_off, cy, cvr, cug, cvg, cub), got {len(c)}")
+    if not 0 <= c[0] <= 255 or c[1] < 0 or colour_set_bound(c) >= 1 << 31:
+        raise TadError(f"colour_set: {c}: y_off must be in [0, 255], cy non-negative and 255 * cy + 128 * max|c| + 2^19 = {colour_set_bound(c)} below 2^31")
+    return c
+
+
+_FORMATS = ("nv12", "nv21", "i420")
+
+
+class YuvFrame:
+    """One 4:2:0 YUV frame as a camera or a decoder hands it over: ``data`` a uint8 array (numpy or a CPU tensor) of any shape whose
+    bytes, in order, are the surface -- ``h`` luma rows of ``y_pitch`` bytes (default ``w``), then the chroma: for "nv12" / "nv21"
+    ``(h + 1) // 2`` rows of ``c_pitch`` bytes (default ``2 * ((w + 1) // 2)``) of interleaved U V / V U pairs, for "i420" the U plane
+    and then the V plane, each ``(h + 1) // 2`` rows of ``c_pitch`` bytes (default ``(w + 1) // 2``).  The last row of the last plane may
+    stop at its last live byte.  ``matrix``: a name of ``COLOUR_SETS`` or six integers.  Nothing is copied or converted here."""
+
+    def __init__(self, data, h: int, w: int, format: str = "nv12", y_pitch: Optional[int] = None, c_pitch: Optional[int] = None, matrix="bt601"):
+        t = torch.from_numpy(np.ascontiguousarray(data)) if isinstance(data, np.ndarray) else data
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.is_cuda:
+            got = f"{t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else type(data).__name__
+            raise TypeError(f"YuvFrame: data must be a uint8 numpy array or CPU tensor, but got {got}")
+        if format not in _FORMATS:
+            raise TadError(f"YuvFrame: format {format!r} must be one of {_FORMATS}")
+        h, w = int(h), int(w)
+        if not (1 <= h <= _lib.YUV_MAX_EXTENT and 1 <= w <= _lib.YUV_MAX_EXTENT):
+            raise TadError(f"YuvFrame: a frame of {h} x {w} pixels must have 1 .. {_lib.YUV_MAX_EXTENT} per side")
+        ch, cw = (h + 1) // 2, (w + 1) // 2
+        step = 1 if format == "i420" else 2
+        y_pitch = w if y_pitch is None else int(y_pitch)
+        c_pitch = cw * step if c_pitch is None else int(c_pitch)
+        if y_pitch < w:
+            raise TadError(f"YuvFrame: y_pitch={y_pitch} is below the {w} bytes of a luma row")
+        if c_pitch < cw * step:
+            raise TadError(f"YuvFrame: c_pitch={c_pitch} is below the {cw * step} bytes of a {format} chroma row")
+        self.data = t.contiguous().reshape(-1)
+        self.h, self.w, self.format, self.y_pitch, self.c_pitch, self.c_step = h, w, format, y_pitch, c_pitch, step
+        self.cset = colour_set(matrix)
+        c_at = h * y_pitch
+        if format == "i420":
+            self.u_at, self.v_at = c_at, c_at + ch * c_pitch
+            self.nbytes = self.v_at + (ch - 1) * c_pitch + cw
+        else:
+            self.u_at, self.v_at = (c_at, c_at + 1) if format == "nv12" else (c_at + 1, c_at)
+            self.nbytes = c_at + (ch - 1) * c_pitch + 2 * cw
+        if self.data.numel() < self.nbytes:
+            raise TadError(f"YuvFrame: {self.data.numel()} bytes do not hold a {format} frame of {h} x {w} with y_pitch={y_pitch}, c_pitch={c_pitch} "
+                           f"({self.nbytes} bytes)")
+
+    @property
+    def layout(self):
+        """what a table is planned from (the bytes themselves are not part of it)"""
+        return (self.h, self.w, self.y_pitch, self.u_at, self.v_at, self.c_pitch, self.c_step, self.nbytes, self.cset)
+
+    @classmethod
+    def of(cls, f, k: int = 0):
+        """a YuvFrame as it is; a bare uint8 [h * 3 / 2, w] array (even h and w) as a contiguous NV12 frame, BT.601 limited range"""
+        if isinstance(f, cls):
+            return f
+        t = torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 2 or t.shape[0] < 3 or t.shape[0] % 3 or t.shape[1] % 2 or t.shape[1] < 2:
+            got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(f).__name__
+            raise TypeError(f"Input {k} must be a YuvFrame or a uint8 array of shape {('h * 3 / 2', 'w')} with even h and w, but got {got}")
+        return cls(t, t.shape[0] // 3 * 2, t.shape[1])
+
+
+def plan_ingest_yuv(layouts, slots, bgrs, S_h: int, S_w: int, F: int, cache: Optional[dict] = None):
+    """The table of one YUV ingest launch: frame k is ``layouts[k]`` (``YuvFrame.layout``), goes to store slot ``slots[k]`` and is
+    written B first if ``bgrs[k]``.  The surfaces are laid out back to back, as they come, at 4-byte aligned offsets behind ``_HEAD``
+    bytes of slack; there is one horizontal set per distinct w, one vertical set per distinct h and one colour set per distinct set of
+    integers.  Returns ``(table int32 CPU tensor, offsets, src_bytes, n_hsets, n_vsets, n_csets)``; the table has passed
+    tady_ingest_plan_check.  ``cache``: as for ``plan_ingest`` -- between ticks of one fleet only the slot column changes.  Host only."""
+    from . import kernels as K
+    from .frame_resize import cubic_coeffs
+    layouts = [tuple(l) for l in layouts]
+    key = ("yuv", tuple(layouts), tuple(bool(b) for b in bgrs), int(S_h), int(S_w))
+    hit = cache.get(key) if cache is not None else None
+    R = _lib.YUV_ROW_WORDS
+    if hit is not None:
+        proto, offsets, at, nh, nv, nc = hit
+        table = proto.clone()
+        k = len(offsets)
+        table[:k * R].view(k, R)[:, 8] = torch.as_tensor([int(v) for v in slots], dtype=torch.int32)
+        _lib.check_yuv(_lib.load_yuv().tady_ingest_plan_check(table.data_ptr(), table.numel(), k, nh, nv, nc, at, int(F), int(S_h), int(S_w)),
+                       "tady_ingest_plan_check")
+        return table, offsets, at, nh, nv, nc
+    hsets, vsets, csets, rows, offsets = {}, {}, {}, [], []
+    at = _HEAD
+    for (h, w, y_pitch, u_at, v_at, c_pitch, c_step, nbytes, cset), slot, bgr in zip(layouts, slots, bgrs):
+        rows.append((at, y_pitch, at + u_at, at + v_at, c_pitch, c_step, h, w, int(slot), hsets.setdefault(w, len(hsets)),
+                     vsets.setdefault(h, len(vsets)), csets.setdefault(tuple(cset), len(csets)), _lib.YUV_BGR if bgr else 0))
+        offsets.append(at)
+        at += (nbytes + 3) // 4 * 4
+    if len(hsets) > _lib.YUV_MAX_SETS or len(vsets) > _lib.YUV_MAX_SETS or len(csets) > _lib.YUV_MAX_CSETS:
+        raise TadError(f"plan_ingest_yuv: {len(hsets)} distinct widths and {len(vsets)} distinct heights in one call, at most {_lib.YUV_MAX_SETS} each, "
+                       f"and {len(csets)} colour sets, at most {_lib.YUV_MAX_CSETS}")
+    table = K.ingest_yuv_table(rows, [(w, *cubic_coeffs(w, S_w)) for w in hsets], [(h, *cubic_coeffs(h, S_h)) for h in vsets], list(csets), at, F,
+                               S_h, S_w)
+    if cache is not None:
+        if len(cache) >= 16:
+            cache.clear()
+        cache[key] = (table.clone(), offsets, at, len(hsets), len(vsets), len(csets))
+    return table, offsets, at, len(hsets), len(vsets), len(csets)
+
+
 class _Staging:
     """one pinned host buffer and its device twin, grown geometrically and kept between ticks; ``free`` is recorded behind the copy that
     reads the host side, and waited for before the host side is written again"""
@@ -175,6 +322,7 @@ class StreamBank:
         self._tables = [_Staging(torch.int32), _Staging(torch.int32)]
         self._tick = 0
         self._plans = {}  # plan_ingest's cache: the tables of the last mixes of sizes
+        self._yuv_plans = {}  # plan_ingest_yuv's
         # use_graph: one captured graph per batch size A (the store and a static slot table are its inputs; the table is refilled by a
         # copy outside the graph), built lazily on a stream of this object's own and sharing one pool -- SlidingWindow's scheme, with A
         # in the place of the ring offset
@@ -266,6 +414,42 @@ class StreamBank:
                 if f.is_cuda:
                     sb.dev[at:at + f.numel()].copy_(f.reshape(-1), non_blocking=True)
             K.ingest_frames(sb.dev, nbytes, self.store, st.dev[:table.numel()], len(ids), nh, nv)
+        self.rings.count, self.rings.start = trial.count, trial.start
+
+    def push_yuv(self, ids, frames: Sequence) -> None:
+        """K 4:2:0 YUV frames of ANY sizes and layouts, as the cameras or decoders deliver them (``YuvFrame``: NV12, NV21 or I420,
+        pitched or not; a bare uint8 [h * 3 / 2, w] array is a contiguous NV12 frame), one for each of the K distinct streams ``ids``:
+        the planes are packed as they come (one copy, no conversion on the host), converted to RGB and resized on the device into the
+        ring slots ``push_raw`` would have written, ONE launch (``kernels.ingest_yuv``, include/tad_mi355x_yuv.h).  The channel order is
+        the store's own, so a bank can take ``push_raw`` from some cameras and ``push_yuv`` from others.  Everything is checked before
+        the state moves or anything is launched."""
+        if ops_precise():
+            raise TadError(_PRECISE)
+        ids = self.rings.check_ids(ids, "StreamBank.push_yuv")
+        if len(frames) != len(ids):
+            raise TadError(f"StreamBank.push_yuv: {len(ids)} stream ids and {len(frames)} frames")
+        fs = [YuvFrame.of(f, k) for k, f in enumerate(frames)]
+        if not ids:
+            return
+        trial = StreamRings(self.S, self.T)
+        trial.count, trial.start = list(self.rings.count), list(self.rings.start)
+        slots = trial.assign(ids)
+        table, offsets, nbytes, nh, nv, nc = plan_ingest_yuv([f.layout for f in fs], slots, [self.store_bgr] * len(fs), self.H, self.W,
+                                                             self.S * self.T, self._yuv_plans)
+        from . import kernels as K
+        with torch.cuda.device(self.device):
+            sb, st = self._bytes[self._tick & 1], self._tables[self._tick & 1]
+            self._tick += 1
+            total = nbytes + _HEAD  # (slack behind the last frame as in front of the first)
+            sb.reserve(total, self.device)
+            st.reserve(table.numel(), self.device)
+            host = sb.host.numpy()
+            for f, at in zip(fs, offsets):
+                host[at:at + f.nbytes] = f.data.numpy()[:f.nbytes]
+            st.host[:table.numel()].copy_(table)
+            sb.upload(total)
+            st.upload(table.numel())
+            K.ingest_yuv(sb.dev, nbytes, self.store, st.dev[:table.numel()], len(ids), nh, nv, nc)
         self.rings.count, self.rings.start = trial.count, trial.start
 
     def push(self, ids, frames) -> None:
