@@ -273,164 +273,63 @@ def load() -> C.CDLL:
     v = lib.tadp_abi_version()
     if v != PRETRAIN_ABI_VERSION:
         raise TadError(f"pre-training ABI mismatch: library reports {v}, binding expects {PRETRAIN_ABI_VERSION}")
-    _load_serve()
-    _load_recon()
-    _load_bank()
-    _load_yuv()
+    for key in SIDE_LIBS:
+        _load_side(key)
     _lib = lib
     return lib
 
 
-_serve = None
+# The libraries beside the first one: key -> (path, signatures, prefix of its entry points, expected <prefix>_abi_version, its name in messages)
+SIDE_LIBS = {
+    "serve": (SERVE_LIB_PATH, SERVE_SIGNATURES, "tads", SERVE_ABI_VERSION, "serving"),
+    "recon": (RECON_LIB_PATH, RECON_SIGNATURES, "tadr", RECON_ABI_VERSION, "reconstruction"),
+    "bank": (BANK_LIB_PATH, BANK_SIGNATURES, "tadb", BANK_ABI_VERSION, "stream-bank"),
+    "yuv": (YUV_LIB_PATH, YUV_SIGNATURES, "tady", YUV_ABI_VERSION, "YUV-ingest"),
+}
+_sides = {}
 
 
-def _load_serve() -> C.CDLL:
-    global _serve
-    if _serve is not None:
-        return _serve
-    if not os.path.exists(SERVE_LIB_PATH):
+def _load_side(key: str) -> C.CDLL:
+    if key in _sides:
+        return _sides[key]
+    path, signatures, prefix, abi, human = SIDE_LIBS[key]
+    if not os.path.exists(path):
         raise TadError(
-            f"{SERVE_LIB_PATH} not found: the serving library has not been built. Run `python -m simple_tad_amd.build` "
+            f"{path} not found: the {human} library has not been built. Run `python -m simple_tad_amd.build` "
             "(or __graft_entry__.build()). There is no CPU fallback for the MI355X path.")
-    lib = C.CDLL(SERVE_LIB_PATH)
-    for name, (res, args) in SERVE_SIGNATURES.items():
+    lib = C.CDLL(path)
+    for name, (res, args) in signatures.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover
-            raise TadError(f"{SERVE_LIB_PATH} does not export {name}") from e
+            raise TadError(f"{path} does not export {name}") from e
         fn.restype = res
         fn.argtypes = args
-    v = lib.tads_abi_version()
-    if v != SERVE_ABI_VERSION:
-        raise TadError(f"serving ABI mismatch: library reports {v}, binding expects {SERVE_ABI_VERSION}")
-    _serve = lib
+    v = getattr(lib, prefix + "_abi_version")()
+    if v != abi:
+        raise TadError(f"{human} ABI mismatch: library reports {v}, binding expects {abi}")
+    _sides[key] = lib
     return lib
 
 
-def load_serve() -> C.CDLL:
-    """the serving library (tads_*); loaded, and checked, together with the first one"""
-    load()
-    return _serve
+def _side_api(key: str):
+    """(load_X, check_X) of a side library: loaded, and checked, together with the first one; it keeps its own error text"""
+    def load_side() -> C.CDLL:
+        load()
+        return _sides[key]
+
+    def check_side(rc: int, what: str = "") -> None:
+        if rc != 0:
+            msg = getattr(load_side(), SIDE_LIBS[key][2] + "_last_error_string")()
+            raise TadError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
+
+    return load_side, check_side
 
 
-def check_serve(rc: int, what: str = "") -> None:
-    if rc != 0:
-        msg = load_serve().tads_last_error_string()
-        raise TadError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
-
-
-_recon = None
-
-
-def _load_recon() -> C.CDLL:
-    global _recon
-    if _recon is not None:
-        return _recon
-    if not os.path.exists(RECON_LIB_PATH):
-        raise TadError(
-            f"{RECON_LIB_PATH} not found: the reconstruction library has not been built. Run `python -m simple_tad_amd.build` "
-            "(or __graft_entry__.build()). There is no CPU fallback for the MI355X path.")
-    lib = C.CDLL(RECON_LIB_PATH)
-    for name, (res, args) in RECON_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:  # pragma: no cover
-            raise TadError(f"{RECON_LIB_PATH} does not export {name}") from e
-        fn.restype = res
-        fn.argtypes = args
-    v = lib.tadr_abi_version()
-    if v != RECON_ABI_VERSION:
-        raise TadError(f"reconstruction ABI mismatch: library reports {v}, binding expects {RECON_ABI_VERSION}")
-    _recon = lib
-    return lib
-
-
-def load_recon() -> C.CDLL:
-    """the reconstruction library (tadr_*); loaded, and checked, together with the first one"""
-    load()
-    return _recon
-
-
-def check_recon(rc: int, what: str = "") -> None:
-    if rc != 0:
-        msg = load_recon().tadr_last_error_string()
-        raise TadError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
-
-
-_bank = None
-
-
-def _load_bank() -> C.CDLL:
-    global _bank
-    if _bank is not None:
-        return _bank
-    if not os.path.exists(BANK_LIB_PATH):
-        raise TadError(
-            f"{BANK_LIB_PATH} not found: the stream-bank library has not been built. Run `python -m simple_tad_amd.build` "
-            "(or __graft_entry__.build()). There is no CPU fallback for the MI355X path.")
-    lib = C.CDLL(BANK_LIB_PATH)
-    for name, (res, args) in BANK_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:  # pragma: no cover
-            raise TadError(f"{BANK_LIB_PATH} does not export {name}") from e
-        fn.restype = res
-        fn.argtypes = args
-    v = lib.tadb_abi_version()
-    if v != BANK_ABI_VERSION:
-        raise TadError(f"stream-bank ABI mismatch: library reports {v}, binding expects {BANK_ABI_VERSION}")
-    _bank = lib
-    return lib
-
-
-def load_bank() -> C.CDLL:
-    """the stream-bank library (tadb_*); loaded, and checked, together with the first one"""
-    load()
-    return _bank
-
-
-def check_bank(rc: int, what: str = "") -> None:
-    if rc != 0:
-        msg = load_bank().tadb_last_error_string()
-        raise TadError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
-
-
-_yuv = None
-
-
-def _load_yuv() -> C.CDLL:
-    global _yuv
-    if _yuv is not None:
-        return _yuv
-    if not os.path.exists(YUV_LIB_PATH):
-        raise TadError(
-            f"{YUV_LIB_PATH} not found: the YUV-ingest library has not been built. Run `python -m simple_tad_amd.build` "
-            "(or __graft_entry__.build()). There is no CPU fallback for the MI355X path.")
-    lib = C.CDLL(YUV_LIB_PATH)
-    for name, (res, args) in YUV_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:  # pragma: no cover
-            raise TadError(f"{YUV_LIB_PATH} does not export {name}") from e
-        fn.restype = res
-        fn.argtypes = args
-    v = lib.tady_abi_version()
-    if v != YUV_ABI_VERSION:
-        raise TadError(f"YUV-ingest ABI mismatch: library reports {v}, binding expects {YUV_ABI_VERSION}")
-    _yuv = lib
-    return lib
-
-
-def load_yuv() -> C.CDLL:
-    """the YUV-ingest library (tady_*); loaded, and checked, together with the first one"""
-    load()
-    return _yuv
-
-
-def check_yuv(rc: int, what: str = "") -> None:
-    if rc != 0:
-        msg = load_yuv().tady_last_error_string()
-        raise TadError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
+load_serve, check_serve = _side_api("serve")  # tads_*
+load_recon, check_recon = _side_api("recon")  # tadr_*
+load_bank, check_bank = _side_api("bank")     # tadb_*
+load_yuv, check_yuv = _side_api("yuv")        # tady_*
 
 
 def check(rc: int, what: str = "") -> None:

@@ -32,7 +32,7 @@ NO_VGPR_FORM = {"gemm_w4.hip"}
 # is f32 only
 EXTRA_DEPS = {"gemm.hip": ["gemm_kernels.h", "gemm_plan.h"], "gemm_w4.hip": ["gemm_kernels.h", "gemm_plan.h"], "gemm_plan.hip": ["gemm_plan.h", "knob.h"],
               "attn_fwd.hip": ["attn_plan.h"], "attn_bwd.hip": ["attn_plan.h"], "attn_plan.hip": ["attn_plan.h", "knob.h"],
-              "multiscale_crop.hip": ["frame_io.h"], "frame_resize.hip": ["frame_io.h"], "spatial_sample.hip": ["frame_io.h"], "randaug.hip": ["frame_io.h"],
+              "multiscale_crop.hip": ["frame_io.h"], "frame_resize.hip": ["frame_io.h", "cubic_resize.h"], "spatial_sample.hip": ["frame_io.h"], "randaug.hip": ["frame_io.h"],
               "layernorm.hip": ["rownorm.h"], "rmsnorm.hip": ["rownorm.h", "../../include/tad_mi355x_ext.h"],
               "visible_tokens.hip": ["../../include/tad_mi355x_pretrain.h"]}
 # ema.hip and mixup.hip must round like torch (a product, a product, a sum: three roundings) and are compiled without FMA contraction;
@@ -42,27 +42,17 @@ EXTRA_DEPS = {"gemm.hip": ["gemm_kernels.h", "gemm_plan.h"], "gemm_w4.hip": ["ge
 # frame_resize.hip fades a reflected pad band with one f32 product rounded on its own (cv2.addWeighted) and writes frames_to_clip's f32 values.
 # A `#pragma clang fp contract(off)` is not enough: -ffp-contract=fast also lets the code generator fuse fmul + fadd by itself.
 NO_FP_CONTRACT = {"ema.hip", "mixup.hip", "randaug.hip", "multiscale_crop.hip", "spatial_sample.hip", "frame_resize.hip"}
-# The serving library (include/tad_mi355x_serve.h, tads_*): libtad_mi355x.so is held at its three surfaces, so the fourth is linked apart, from
-# its own source list, with the same FLAGS plus hidden visibility (its entry points alone are exported: nothing in it can bind to or shadow
-# the first library's C++ symbols).  Built after the first library by build(); experiment and ablation builds do not build it.
-SERVE_LIB = os.path.join(HERE, "libtad_mi355x_serve.so")
-SERVE_SOURCES = ["iv2_serve.hip"]
-EXTRA_DEPS["iv2_serve.hip"] = ["rownorm.h", "../../include/tad_mi355x_serve.h"]
-# The reconstruction library (include/tad_mi355x_recon.h, tadr_*): the fifth surface, linked apart for the same reason and in the same way
-# (the serving library is held at its one source).  mae.hip's object code is not touched: the statistics are restated in the new source.
-RECON_LIB = os.path.join(HERE, "libtad_mi355x_recon.so")
-RECON_SOURCES = ["mae_reconstruct.hip"]
-EXTRA_DEPS["mae_reconstruct.hip"] = ["../../include/tad_mi355x_recon.h"]
-# The stream-bank library (include/tad_mi355x_bank.h, tadb_*): the sixth surface, linked apart for the same reason and in the same way.
-# frame_resize.hip's object code is not touched: the resize arithmetic is restated in the new source (integers only: no contraction flag).
-BANK_LIB = os.path.join(HERE, "libtad_mi355x_bank.so")
-BANK_SOURCES = ["stream_bank.hip"]
-EXTRA_DEPS["stream_bank.hip"] = ["frame_io.h", "../../include/tad_mi355x_bank.h"]
-# The YUV-ingest library (include/tad_mi355x_yuv.h, tady_*): the seventh surface, linked apart for the same reason and in the same way.
-# stream_bank.hip's object code is not touched: the resize arithmetic is restated in the new source (integers only: no contraction flag).
-YUV_LIB = os.path.join(HERE, "libtad_mi355x_yuv.so")
-YUV_SOURCES = ["yuv_ingest.hip"]
-EXTRA_DEPS["yuv_ingest.hip"] = ["frame_io.h", "../../include/tad_mi355x_yuv.h"]
+# The libraries beside the first one, one per surface added since libtad_mi355x.so was held at its three (include/tad_mi355x_serve.h
+# tads_*, _recon.h tadr_*, _bank.h tadb_*, _yuv.h tady_*): each linked apart from ONE source, with the same FLAGS plus hidden visibility
+# (its entry points alone are exported: nothing in it can bind to or shadow another library's C++ symbols; csrc/side_library.h).  Built
+# after the first library by build(); experiment and ablation builds do not build them.  _SIDE: name -> (source, the headers it
+# includes beside side_library.h and its own ABI header); SIDE_LIBS: name -> (library, source list)
+_SIDE = {"serve": ("iv2_serve.hip", ["rownorm.h"]), "recon": ("mae_reconstruct.hip", []),
+         "bank": ("stream_bank.hip", ["frame_io.h", "cubic_resize.h"]), "yuv": ("yuv_ingest.hip", ["frame_io.h", "cubic_resize.h"])}
+SIDE_LIBS = {name: (os.path.join(HERE, f"libtad_mi355x_{name}.so"), [src]) for name, (src, _) in _SIDE.items()}
+for _name, (_src, _deps) in _SIDE.items():
+    EXTRA_DEPS[_src] = [*_deps, "side_library.h", f"../../include/tad_mi355x_{_name}.h"]
+(SERVE_LIB, SERVE_SOURCES), (RECON_LIB, RECON_SOURCES), (BANK_LIB, BANK_SOURCES), (YUV_LIB, YUV_SOURCES) = SIDE_LIBS.values()
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wno-unused-result",
          # keep MFMA accumulators in the (unified) VGPR file: without it the compiler parks them in AGPRs and pays a
          # v_accvgpr_read/write per element around every softmax / epilogue
@@ -88,10 +78,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
     """build what is stale: the library (returned) and, in a production build, the serving, reconstruction, stream-bank and YUV-ingest libraries beside it"""
     lib = _build_core(force, verbose)
     if _PRODUCTION:
-        _build_side(SERVE_LIB, SERVE_SOURCES, force, verbose)
-        _build_side(RECON_LIB, RECON_SOURCES, force, verbose)
-        _build_side(BANK_LIB, BANK_SOURCES, force, verbose)
-        _build_side(YUV_LIB, YUV_SOURCES, force, verbose)
+        for side, sources in SIDE_LIBS.values():
+            _build_side(side, sources, force, verbose)
     return lib
 
 

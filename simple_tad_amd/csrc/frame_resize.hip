@@ -8,73 +8,34 @@
 // 0}, one horizontal set and n_vsets vertical sets, each {in, out, 0, 0}, first[out], k[out][4].  The table is only read.
 //
 // Arithmetic -- the contract: OpenCV's GENERIC INTEGER formulation of the 8-bit cubic resize, not the bytes of one OpenCV build (the
-// vector path of a build finishes the vertical pass in float and can differ from this by one grey level).  Per output four taps
-// first .. first + 3, each clamped to the source (replicate border), 11-bit coefficients that are NOT renormalised; two passes in
-// int32 with no rounding in between:
-//   h[row][d] = sum_j src[row][tap_j] * kx[d][j];      byte = clip((sum_j h[tap_j][d] * ky[r][j] + (1 << 21)) >> 22, 0, 255)
-// 255 * 2818 * 2818 + 2^21 < 2^31 (sum |k| <= 2818 per output, which tad_frame_resize_plan_check holds the table to).  All float work
-// (the sample positions, Keys' weights with A = -0.75, their rounding) stays on the host.
+// vector path of a build finishes the vertical pass in float and can differ from this by one grey level): the two int32 passes of
+// cubic_resize.h, which also describes the tile, its LDS and the vertical pass.  All float work (the sample positions, Keys' weights
+// with A = -0.75, their rounding) stays on the host.
 //
 // Padding is a VIRTUAL source of pad_top + H + pad_bottom rows that the vertical taps index; no padded frame exists.  The horizontal
-// pass maps each virtual row it needs to a frame row (reflect, replicate), or to the band's colour.  A reflected band byte is faded
-// towards black: rint((float)p * alpha), the product on its own -- cv2.addWeighted(reflect, a, black, 1 - a, 0) in float; the file is
-// compiled without floating-point contraction (build.py).  The fused f32 value is frames_to_clip's: normalize_u8 (common.h).
-//
-// Shape: a workgroup of 256 threads owns FRAME_TR x FRAME_TC outputs of one frame (frame_io.h).  It stages the tile's taps and
-// coefficients in LDS, runs the horizontal pass over the virtual rows the tile's vertical taps name into int32 LDS planes (one per row and channel), then the
-// vertical pass out of LDS.  The rows are held densely (slot = row - lowest row) when the taps of the tile span at most 4 rows per
-// output row -- upscales and shrinks up to 4 -- and as four slots per output row otherwise, so only rows under taps are ever read.
-// The four pixels under an output's horizontal taps are 12 contiguous bytes at no particular alignment (W * 3 breaks every one): they come
-// in as aligned words and a funnel shift (fr_load12); where a tap clamps at a border, byte by byte.  A thread's outputs in the vertical
-// pass are four neighbouring columns, written by the clip and frame writers of frame_io.h, which describes the output path.
-#include "frame_io.h"
+// pass -- this file's own -- maps each virtual row it needs to a frame row (reflect, replicate), or to the band's colour.  A reflected
+// band byte is faded towards black: rint((float)p * alpha), the product on its own -- cv2.addWeighted(reflect, a, black, 1 - a, 0) in
+// float; the file is compiled without floating-point contraction (build.py).  The four pixels under an output's horizontal taps are 12
+// contiguous bytes at no particular alignment (W * 3 breaks every one): cubic_load12; where a tap clamps at a border, byte by byte.  The
+// fused f32 value is frames_to_clip's: frame_norm8 in front of store_clip_f32x4 (frame_io.h).
+#include "cubic_resize.h"
 #include <string.h>
 #include <type_traits>
 
 TAD_NAMESPACE_BEGIN
 
-constexpr int FR_SLOTS = 4 * FRAME_TR;  // virtual rows a tile can need: four taps per output row
-static_assert(FR_SLOTS * 3 * FRAME_TC * 4 + (FRAME_TC + FRAME_TR) * 5 * 4 <= 64 * 1024, "static LDS stays at or below 64 KB");
-
-__host__ __device__ __forceinline__ int64_t fr_set_words(int out) { return TAD_FR_SET_HEAD + (int64_t)out * 5; }
 __host__ __device__ __forceinline__ int64_t fr_table_words(int B, int nv, int Sh, int Sw) {
-  return (int64_t)B * TAD_FR_ROW_WORDS + fr_set_words(Sw) + nv * fr_set_words(Sh);
+  return (int64_t)B * TAD_FR_ROW_WORDS + cubic_set_words(Sw) + nv * cubic_set_words(Sh);
 }
 
 // a reflected band byte faded towards black: rint((float)p * alpha), the product on its own, cut to a byte
 __device__ __forceinline__ int fr_fade(int b, float alpha) { return frame_clamp(__float2int_rn(__fmul_rn((float)b, alpha)), 0, 255); }
 
-// the 12 bytes from p (any alignment) as three words: aligned 4-byte loads and a funnel shift.  Only the aligned words that hold one of
-// the 12 bytes are loaded -- three when p is aligned, else four -- so no load leaves the pages of the bytes asked for; the up to three
-// bytes to either side that share a word with them are shifted out
-__device__ __forceinline__ void fr_load12(const uint8_t* p, uint32_t w[3]) {
-  const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3);
-  const uint32_t* q = static_cast<const uint32_t*>(__builtin_assume_aligned(p - sh, 4));  // (derived from p: stays a global pointer)
-  const uint32_t d0 = q[0], d1 = q[1], d2 = q[2], d3 = sh ? q[3] : 0u;
-  w[0] = __builtin_amdgcn_alignbyte(d1, d0, sh);
-  w[1] = __builtin_amdgcn_alignbyte(d2, d1, sh);
-  w[2] = __builtin_amdgcn_alignbyte(d3, d2, sh);
-}
-
-// first tap and coefficients of `n` outputs from output `o0` of a set, staged in LDS (slots past n: tap 0, coefficients 0)
-__device__ __forceinline__ void fr_stage(const int32_t* __restrict__ set, int out_size, int o0, int n, int* first, int (*kk)[4], int slots) {
-  const int32_t* f = set + TAD_FR_SET_HEAD;
-  const int32_t* k = f + out_size;
-  for (int i = threadIdx.x; i < slots * 5; i += FRAME_THREADS) {
-    const int o = i / 5, j = i - o * 5;
-    if (j == 4)
-      first[o] = o < n ? f[o0 + o] : 0;
-    else
-      kk[o][j] = o < n ? k[(int64_t)(o0 + o) * 4 + j] : 0;
-  }
-}
-
 template <bool F32>
 __global__ __launch_bounds__(FRAME_THREADS) void frame_resize_kernel(const uint8_t* __restrict__ x, void* __restrict__ out,
                                                                  const int32_t* __restrict__ tab, ClipNorm nm, int B, int T, int H, int W, int Sh,
                                                                  int Sw, int nv, int tiles_x) {
-  __shared__ __attribute__((aligned(16))) int hp[FR_SLOTS][3][FRAME_TC];  // (read back four columns at a time)
-  __shared__ int hf[FRAME_TC], hk[FRAME_TC][4], vf[FRAME_TR], vk[FRAME_TR][4];
+  CUBIC_TILE_LDS;
   const int32_t* r = tab + (int64_t)blockIdx.z * TAD_FR_ROW_WORDS;
   const int sample = r[0];
   if (sample < 0 || sample >= B) return;  // (the same for every thread of the workgroup)
@@ -87,21 +48,13 @@ __global__ __launch_bounds__(FRAME_THREADS) void frame_resize_kernel(const uint8
   const uint32_t colour = (uint32_t)r[5];
   const int Hv = pt + H + pb;
   const int32_t* hset = tab + (int64_t)B * TAD_FR_ROW_WORDS;
-  const int32_t* vset = hset + fr_set_words(Sw) + frame_clamp(r[6], 0, nv - 1) * fr_set_words(Sh);
+  const int32_t* vset = hset + cubic_set_words(Sw) + frame_clamp(r[6], 0, nv - 1) * cubic_set_words(Sh);
   const int c0 = tx * FRAME_TC, o0 = ty * FRAME_TR;
   const int nc = Sw - c0 < FRAME_TC ? Sw - c0 : FRAME_TC, nr = Sh - o0 < FRAME_TR ? Sh - o0 : FRAME_TR;
-  fr_stage(hset, Sw, c0, nc, hf, hk, FRAME_TC);
-  fr_stage(vset, Sh, o0, nr, vf, vk, FRAME_TR);
+  cubic_stage(hset, Sw, c0, nc, W, hf, hk, FRAME_TC);
+  cubic_stage(vset, Sh, o0, nr, Hv, vf, vk, FRAME_TR);
   __syncthreads();
-
-  // the virtual rows under the tile's vertical taps: [lo, hi], held densely when that is no more rows than four per output row
-  int lo = Hv - 1, hi = 0;
-  for (int i = 0; i < nr; ++i) {
-    const int a = frame_clamp(vf[i], 0, Hv - 1), b = frame_clamp(vf[i] + 3, 0, Hv - 1);
-    lo = a < lo ? a : lo, hi = b > hi ? b : hi;
-  }
-  const bool dense = hi - lo + 1 <= 4 * nr;
-  const int nslots = dense ? hi - lo + 1 : 4 * nr;
+  const CubicSpan span = cubic_span(vf, nr, Hv);  // (of virtual rows)
 
   // horizontal pass: an item is one column of one virtual row, all three channels; a thread keeps its column and walks the rows.  The
   // fade of a reflected band is compiled into the pass of the clips that reflect alone (the mode is the workgroup's)
@@ -110,8 +63,8 @@ __global__ __launch_bounds__(FRAME_THREADS) void frame_resize_kernel(const uint8
     constexpr bool REFLECT = decltype(reflect)::value;
     const int c = tid & (FRAME_TC - 1);
     if (c >= nc) return;
-    for (int slot = tid / FRAME_TC; slot < nslots; slot += FRAME_THREADS / FRAME_TC) {
-      const int v = dense ? lo + slot : frame_clamp(vf[slot >> 2] + (slot & 3), 0, Hv - 1);
+    for (int slot = tid / FRAME_TC; slot < span.nslots; slot += FRAME_THREADS / FRAME_TC) {
+      const int v = cubic_slot_row(span, vf, slot, Hv);
       // the row map: inside the frame the row itself; in a band its mirror image (faded), the edge row, or the colour
       int fr = v - pt;
       bool band = false;
@@ -129,7 +82,7 @@ __global__ __launch_bounds__(FRAME_THREADS) void frame_resize_kernel(const uint8
       const int f0 = hf[c];
       if (!constant && f0 >= 0 && f0 + 3 <= W - 1) {  // no tap clamps: the four pixels are 12 contiguous bytes
         uint32_t w[3];
-        fr_load12(row + (int64_t)f0 * 3, w);
+        cubic_load12(row + (int64_t)f0 * 3, w);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int k = hk[c][j];
@@ -163,27 +116,10 @@ __global__ __launch_bounds__(FRAME_THREADS) void frame_resize_kernel(const uint8
     hpass(std::false_type{});
   __syncthreads();
 
-  // vertical pass: a thread owns four columns of one output row, all three channels
-  const int orow = tid / FRAME_CG, cg = tid - orow * FRAME_CG;
-  const int col = c0 + cg * 4, valid = Sw - col < 4 ? Sw - col : 4;
-  if (orow >= nr || valid <= 0) return;
+  CubicOut at;
   int acc[3][4];
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc[ch][q] = 1 << 21;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int v = frame_clamp(vf[orow] + j, 0, Hv - 1);
-    const int slot = frame_clamp(dense ? v - lo : orow * 4 + j, 0, FR_SLOTS - 1);
-    const int k = vk[orow][j];
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      const int4 h = *reinterpret_cast<const int4*>(&hp[slot][ch][cg * 4]);
-      acc[ch][0] += h.x * k, acc[ch][1] += h.y * k, acc[ch][2] += h.z * k, acc[ch][3] += h.w * k;
-    }
-  }
-  const int oy = o0 + orow;
+  if (!cubic_vpass(hp, vf, vk, span, Hv, c0, nr, Sw, false, at, acc)) return;
+  const int oy = o0 + at.orow, col = at.col, valid = at.valid;
   if (F32) {
     float* o = static_cast<float*>(out) + (((int64_t)sample * 3 * T + t) * Sh + oy) * Sw + col;  // channel ch: + ch * T * Sh * Sw
     const int64_t plane = (int64_t)T * Sh * Sw;
@@ -215,23 +151,6 @@ extern "C" size_t tad_frame_resize_workspace_bytes(int B, int n_vsets, int S_h, 
   return (size_t)fr_table_words(B, n_vsets, S_h, S_w) * 4;
 }
 
-static int fr_check_set(const int32_t* set, int out_size, const char* axis, int index) {
-  const int in = set[0];
-  TAD_REQUIRE(set[1] == out_size, "frame_resize_plan_check: %s set %d: output extent %d, expected %d", axis, index, set[1], out_size);
-  const int32_t* f = set + TAD_FR_SET_HEAD;
-  const int32_t* k = f + out_size;
-  for (int o = 0; o < out_size; ++o) {
-    // s = first + 1 = floor of a sample position that lies within half a source step of the source: s in [-1, in - 1]
-    TAD_REQUIRE(f[o] >= -2 && f[o] <= in - 2, "frame_resize_plan_check: %s set %d: output %d has its taps at [%d, %d], outside the %d samples of the source",
-                axis, index, o, f[o], f[o] + 3, in);
-    int64_t mag = 0;
-    for (int j = 0; j < 4; ++j) mag += k[4 * o + j] < 0 ? -(int64_t)k[4 * o + j] : (int64_t)k[4 * o + j];
-    TAD_REQUIRE(mag <= TAD_FR_MAX_ABS_SUM, "frame_resize_plan_check: %s set %d: output %d: sum |k| = %lld is above %d (the int32 passes would overflow)",
-                axis, index, o, (long long)mag, TAD_FR_MAX_ABS_SUM);
-  }
-  return TAD_OK;
-}
-
 extern "C" int tad_frame_resize_plan_check(const int32_t* table_host, int64_t n_words, int B, int n_vsets, int H, int W, int S_h, int S_w) {
   TAD_REQUIRE(table_host, "frame_resize_plan_check: null pointer");
   if (int rc = fr_shape_ok(B, n_vsets, H, W, S_h, S_w, "frame_resize_plan_check")) return rc;
@@ -240,13 +159,14 @@ extern "C" int tad_frame_resize_plan_check(const int32_t* table_host, int64_t n_
               (long long)want);
   const int32_t* hset = table_host + (int64_t)B * TAD_FR_ROW_WORDS;
   TAD_REQUIRE(hset[0] == W, "frame_resize_plan_check: horizontal set: input extent %d, the source has %d columns", hset[0], W);
-  if (int rc = fr_check_set(hset, S_w, "horizontal", 0)) return rc;
-  const int32_t* vsets = hset + fr_set_words(S_w);
+  // (a set's input extent is checked here, against the frame, under this check's own words: W, and H plus two pads of at most H)
+  if (int rc = cubic_check_set("frame_resize_plan_check", hset, S_w, "horizontal", 0, W)) return rc;
+  const int32_t* vsets = hset + cubic_set_words(S_w);
   for (int i = 0; i < n_vsets; ++i) {
-    const int32_t* set = vsets + i * fr_set_words(S_h);
+    const int32_t* set = vsets + i * cubic_set_words(S_h);
     TAD_REQUIRE(set[0] >= H && (int64_t)set[0] <= (int64_t)3 * H,
                 "frame_resize_plan_check: vertical set %d: virtual height %d is not the %d rows of the source plus two pads of at most %d", i, set[0], H, H);
-    if (int rc = fr_check_set(set, S_h, "vertical", i)) return rc;
+    if (int rc = cubic_check_set("frame_resize_plan_check", set, S_h, "vertical", i, 3 * H)) return rc;
   }
   SeenSamples seen;  // (B <= 65535)
   for (int k = 0; k < B; ++k) {
@@ -265,8 +185,8 @@ extern "C" int tad_frame_resize_plan_check(const int32_t* table_host, int64_t n_
     }
     TAD_REQUIRE((r[5] & ~0xffffff) == 0, "frame_resize_plan_check: row %d: colour word 0x%x holds more than three bytes", k, (unsigned)r[5]);
     TAD_REQUIRE(0 <= vs && vs < n_vsets, "frame_resize_plan_check: row %d: vertical set %d outside [0, %d)", k, vs, n_vsets);
-    TAD_REQUIRE(vsets[vs * fr_set_words(S_h)] == pt + H + pb, "frame_resize_plan_check: row %d: its vertical set is stated for %d rows, the padded frame has %d",
-                k, vsets[vs * fr_set_words(S_h)], pt + H + pb);
+    TAD_REQUIRE(vsets[vs * cubic_set_words(S_h)] == pt + H + pb, "frame_resize_plan_check: row %d: its vertical set is stated for %d rows, the padded frame has %d",
+                k, vsets[vs * cubic_set_words(S_h)], pt + H + pb);
   }
   return TAD_OK;
 }

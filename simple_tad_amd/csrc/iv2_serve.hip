@@ -7,36 +7,13 @@
 //                       per lane and read once, four rows per block, the instance chosen by ROWNORM_SWITCH_NV over rownorm_nv(D).  The
 //                       loads of a row (x, y and the two gammas) are requested in one batch before any arithmetic (layernorm.hip's notes
 //                       on load batching).  Evaluation only: no statistics are kept.
-// The library is self-contained: built with -fvisibility=hidden (simple_tad_amd/build.py: SERVE_FLAGS), it defines the error text and
-// the launch check that common.h declares for itself (capi.hip's are another library's and are neither used nor shadowed) and exports
-// the tads_* entry points alone.  Compiled ONCE: the 16-bit format is a run-time argument that selects a template instance.
-#include <stdarg.h>
+// The library is self-contained (side_library.h) and exports the tads_* entry points alone.  Compiled ONCE: the 16-bit format is a
+// run-time argument that selects a template instance.
+#include "side_library.h"
 #include "rownorm.h"
 #pragma GCC visibility push(default)
 #include "../../include/tad_mi355x_serve.h"
 #pragma GCC visibility pop
-
-namespace tad {
-
-static thread_local char g_serve_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_serve_err, sizeof(g_serve_err), fmt, ap);
-  va_end(ap);
-}
-
-int check_launch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: %s", what, hipGetErrorString(e));
-    return TAD_ELAUNCH;
-  }
-  return TAD_OK;
-}
-
-}  // namespace tad
 
 TAD_NAMESPACE_BEGIN
 
@@ -164,7 +141,7 @@ extern "C" {
 
 int tads_abi_version(void) { return TADS_ABI_VERSION; }
 
-const char* tads_last_error_string(void) { return tad::g_serve_err; }
+const char* tads_last_error_string(void) { return tad::side_last_error(); }
 
 int tads_class_token_entry_fwd(const float* patch, const float* cls, const float* pos, float* out, int B, int N, int D,
                                tad_stream_t stream) {

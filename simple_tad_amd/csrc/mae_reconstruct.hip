@@ -11,35 +11,11 @@
 // channel at byte pix*3 + c, and after a barrier all four waves write the patch's tub*p rows of 3p bytes each as whole 4-byte words where
 // the row's address allows and as single bytes at its two ends.  Every byte is written by exactly one lane; no address of a store depends
 // on slot.
-// The library is self-contained: built with -fvisibility=hidden (simple_tad_amd/build.py), it defines the error text and the launch
-// check that common.h declares for itself and exports the tadr_* entry points alone.
-#include <stdarg.h>
-#include "common.h"
+// The library is self-contained (side_library.h) and exports the tadr_* entry points alone.
+#include "side_library.h"
 #pragma GCC visibility push(default)
 #include "../../include/tad_mi355x_recon.h"
 #pragma GCC visibility pop
-
-namespace tad {
-
-static thread_local char g_recon_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_recon_err, sizeof(g_recon_err), fmt, ap);
-  va_end(ap);
-}
-
-int check_launch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: %s", what, hipGetErrorString(e));
-    return TAD_ELAUNCH;
-  }
-  return TAD_OK;
-}
-
-}  // namespace tad
 
 TAD_NAMESPACE_BEGIN
 
@@ -193,7 +169,7 @@ extern "C" {
 
 int tadr_abi_version(void) { return TADR_ABI_VERSION; }
 
-const char* tadr_last_error_string(void) { return tad::g_recon_err; }
+const char* tadr_last_error_string(void) { return tad::side_last_error(); }
 
 int tadr_mae_reconstruct(const float* videos, const float* pred, const int32_t* slot, uint8_t* frames, float* err, int B, int n_mask,
                          int T, int H, int W, int tubelet, int patch, const float* mean3, const float* std3, int normalize_target,

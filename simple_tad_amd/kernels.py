@@ -1466,6 +1466,22 @@ def multiscale_crop(x, table, n_hsets: int, n_vsets: int, S_h: int, S_w: int, me
 
 
 # ----------------------------------------------------------------------------- the loader's cubic resize of uint8 frames, behind pad_wide_clips
+def _write_cubic_sets(who: str, tab, at: int, groups) -> int:
+    """The cubic sets of ``groups`` = ((sets, out), ...), each set (in, first [out], k [out][4]), into the int32 table ``tab`` from word
+    ``at``, back to back as csrc/cubic_resize.h lays them out: {in, out, 0, 0}, first, k.  Returns the word behind the last one."""
+    import numpy as np
+    for sets, out in groups:
+        for n_in, first, kk in sets:
+            first, kk = np.asarray(first, dtype=np.int32), np.asarray(kk, dtype=np.int32)
+            if first.shape != (out,) or kk.shape != (out, 4):
+                raise _lib.TadError(f"{who}: a set with first {first.shape} and k {kk.shape} for {out} outputs")
+            tab[at:at + 2] = n_in, out
+            tab[at + _lib.FR_SET_HEAD:at + _lib.FR_SET_HEAD + out] = first
+            tab[at + _lib.FR_SET_HEAD + out:at + _lib.FR_SET_HEAD + 5 * out] = kk.reshape(-1)
+            at += _lib.FR_SET_HEAD + 5 * out
+    return at
+
+
 def frame_resize_table(rows, hset, vsets, B: int, H: int, W: int, S_h: int, S_w: int):
     """Host-side table of frame_resize (include/tad_mi355x.h): ``rows`` = one (sample, mode, pad_top, pad_bottom, alpha, colour, vset)
     per clip, alpha a float and colour three bytes (one per stored channel); ``hset`` = (in, first [S_w], k [S_w][4]) and ``vsets`` =
@@ -1487,16 +1503,7 @@ def frame_resize_table(rows, hset, vsets, B: int, H: int, W: int, S_h: int, S_w:
         if any(abs(w) >= 2 ** 31 for w in words):
             raise _lib.TadError(f"frame_resize_table: row {i} does not fit 32 bits")
         head[i, :7] = words
-    at = B * _lib.FR_ROW_WORDS
-    for sets, out in (([hset], S_w), (vsets, S_h)):
-        for n_in, first, kk in sets:
-            first, kk = np.asarray(first, dtype=np.int32), np.asarray(kk, dtype=np.int32)
-            if first.shape != (out,) or kk.shape != (out, 4):
-                raise _lib.TadError(f"frame_resize_table: a set with first {first.shape} and k {kk.shape} for {out} outputs")
-            tab[at:at + 2] = n_in, out
-            tab[at + _lib.FR_SET_HEAD:at + _lib.FR_SET_HEAD + out] = first
-            tab[at + _lib.FR_SET_HEAD + out:at + _lib.FR_SET_HEAD + 5 * out] = kk.reshape(-1)
-            at += _lib.FR_SET_HEAD + 5 * out
+    _write_cubic_sets("frame_resize_table", tab, B * _lib.FR_ROW_WORDS, (([hset], S_w), (vsets, S_h)))
     check(lib.tad_frame_resize_plan_check(tab.ctypes.data, tab.size, B, nv, H, W, S_h, S_w), "tad_frame_resize_plan_check")
     return torch.from_numpy(tab)
 
@@ -1539,19 +1546,24 @@ def ingest_table(rows, hsets, vsets, src_bytes: int, F: int, S_h: int, S_w: int)
     if (np.abs(r) >= 2 ** 31).any():
         raise _lib.TadError("ingest_table: a row does not fit 32 bits")
     tab[:K * _lib.BANK_ROW_WORDS].reshape(K, _lib.BANK_ROW_WORDS)[:, :7] = r
-    at = K * _lib.BANK_ROW_WORDS
-    for sets, out in ((hsets, S_w), (vsets, S_h)):
-        for n_in, first, kk in sets:
-            first, kk = np.asarray(first, dtype=np.int32), np.asarray(kk, dtype=np.int32)
-            if first.shape != (out,) or kk.shape != (out, 4):
-                raise _lib.TadError(f"ingest_table: a set with first {first.shape} and k {kk.shape} for {out} outputs")
-            tab[at:at + 2] = n_in, out
-            tab[at + _lib.FR_SET_HEAD:at + _lib.FR_SET_HEAD + out] = first
-            tab[at + _lib.FR_SET_HEAD + out:at + _lib.FR_SET_HEAD + 5 * out] = kk.reshape(-1)
-            at += _lib.FR_SET_HEAD + 5 * out
+    _write_cubic_sets("ingest_table", tab, K * _lib.BANK_ROW_WORDS, ((hsets, S_w), (vsets, S_h)))
     _lib.check_bank(lib.tadb_ingest_plan_check(tab.ctypes.data, tab.size, K, nh, nv, int(src_bytes), int(F), int(S_h), int(S_w)),
                     "tadb_ingest_plan_check")
     return torch.from_numpy(tab)
+
+
+def _ingest_args(who: str, src, src_bytes: int, store, table):
+    """the tensors of a ragged ingest launch; returns the store's (F, S_h, S_w)"""
+    _req(src, torch.uint8, f"{who}.src")
+    _req(store, torch.uint8, f"{who}.store")
+    _req(table, torch.int32, f"{who}.table")
+    if store.dim() != 4 or store.shape[-1] != 3 or store.numel() == 0:
+        raise _lib.TadError(f"{who}.store: expected a uint8 frame store [F,S_h,S_w,3], got {tuple(store.shape)}")
+    if src.dim() != 1 or table.dim() != 1 or src.device != store.device or table.device != store.device:
+        raise _lib.TadError(f"{who}: src and table must be 1-D tensors on {store.device}")
+    if int(src_bytes) < 1 or src.numel() < (int(src_bytes) + 3) // 4 * 4:
+        raise _lib.TadError(f"{who}.src: {src.numel()} bytes do not hold src_bytes={src_bytes} rounded up to a multiple of 4")
+    return store.shape[:3]
 
 
 def ingest_frames(src, src_bytes: int, store, table, K: int, n_hsets: int, n_vsets: int):
@@ -1560,16 +1572,7 @@ def ingest_frames(src, src_bytes: int, store, table, K: int, n_hsets: int, n_vse
     ingest_table()'s) says: tadb_ingest_frames, ONE launch for frames of any mix of sizes.  ``src`` must hold ``src_bytes`` rounded up to a
     multiple of 4 (pixels come in as the aligned words that hold them).  store: contiguous uint8 [F,S_h,S_w,3], written in the named slots
     only.  Returns store."""
-    _req(src, torch.uint8, "ingest_frames.src")
-    _req(store, torch.uint8, "ingest_frames.store")
-    _req(table, torch.int32, "ingest_frames.table")
-    if store.dim() != 4 or store.shape[-1] != 3 or store.numel() == 0:
-        raise _lib.TadError(f"ingest_frames.store: expected a uint8 frame store [F,S_h,S_w,3], got {tuple(store.shape)}")
-    if src.dim() != 1 or table.dim() != 1 or src.device != store.device or table.device != store.device:
-        raise _lib.TadError(f"ingest_frames: src and table must be 1-D tensors on {store.device}")
-    if int(src_bytes) < 1 or src.numel() < (int(src_bytes) + 3) // 4 * 4:
-        raise _lib.TadError(f"ingest_frames.src: {src.numel()} bytes do not hold src_bytes={src_bytes} rounded up to a multiple of 4")
-    F, S_h, S_w, _ = store.shape
+    F, S_h, S_w = _ingest_args("ingest_frames", src, src_bytes, store, table)
     with _timed("ingest_frames", 0.0, float(src_bytes + K * S_h * S_w * 3)):
         _lib.check_bank(_lib.load_bank().tadb_ingest_frames(src.data_ptr(), int(src_bytes), store.data_ptr(), F, table.data_ptr(), table.numel(),
                                                             int(K), int(n_hsets), int(n_vsets), S_h, S_w, _stream()), "tadb_ingest_frames")
@@ -1597,16 +1600,7 @@ def ingest_yuv_table(rows, hsets, vsets, csets, src_bytes: int, F: int, S_h: int
     if (np.abs(r) >= 2 ** 31).any() or (np.abs(c) >= 2 ** 31).any():
         raise _lib.TadError("ingest_yuv_table: a row or a colour set does not fit 32 bits")
     tab[:K * R].reshape(K, R)[:, :13] = r
-    at = K * R
-    for sets, out in ((hsets, S_w), (vsets, S_h)):
-        for n_in, first, kk in sets:
-            first, kk = np.asarray(first, dtype=np.int32), np.asarray(kk, dtype=np.int32)
-            if first.shape != (out,) or kk.shape != (out, 4):
-                raise _lib.TadError(f"ingest_yuv_table: a set with first {first.shape} and k {kk.shape} for {out} outputs")
-            tab[at:at + 2] = n_in, out
-            tab[at + _lib.FR_SET_HEAD:at + _lib.FR_SET_HEAD + out] = first
-            tab[at + _lib.FR_SET_HEAD + out:at + _lib.FR_SET_HEAD + 5 * out] = kk.reshape(-1)
-            at += _lib.FR_SET_HEAD + 5 * out
+    at = _write_cubic_sets("ingest_yuv_table", tab, K * R, ((hsets, S_w), (vsets, S_h)))
     tab[at:].reshape(nc, _lib.YUV_CSET_WORDS)[:, :6] = c
     _lib.check_yuv(lib.tady_ingest_plan_check(tab.ctypes.data, tab.size, K, nh, nv, nc, int(src_bytes), int(F), int(S_h), int(S_w)),
                    "tady_ingest_plan_check")
@@ -1619,16 +1613,7 @@ def ingest_yuv(src, src_bytes: int, store, table, K: int, n_hsets: int, n_vsets:
     device table ``table`` (a copy of ingest_yuv_table()'s) says: tady_ingest_yuv, ONE launch for frames of any mix of sizes and
     layouts.  ``src`` must hold ``src_bytes`` rounded up to a multiple of 4 (samples come in as the aligned words that hold them).
     store: contiguous uint8 [F,S_h,S_w,3], written in the named slots only.  Returns store."""
-    _req(src, torch.uint8, "ingest_yuv.src")
-    _req(store, torch.uint8, "ingest_yuv.store")
-    _req(table, torch.int32, "ingest_yuv.table")
-    if store.dim() != 4 or store.shape[-1] != 3 or store.numel() == 0:
-        raise _lib.TadError(f"ingest_yuv.store: expected a uint8 frame store [F,S_h,S_w,3], got {tuple(store.shape)}")
-    if src.dim() != 1 or table.dim() != 1 or src.device != store.device or table.device != store.device:
-        raise _lib.TadError(f"ingest_yuv: src and table must be 1-D tensors on {store.device}")
-    if int(src_bytes) < 1 or src.numel() < (int(src_bytes) + 3) // 4 * 4:
-        raise _lib.TadError(f"ingest_yuv.src: {src.numel()} bytes do not hold src_bytes={src_bytes} rounded up to a multiple of 4")
-    F, S_h, S_w, _ = store.shape
+    F, S_h, S_w = _ingest_args("ingest_yuv", src, src_bytes, store, table)
     with _timed("ingest_yuv", 0.0, float(src_bytes + K * S_h * S_w * 3)):
         _lib.check_yuv(_lib.load_yuv().tady_ingest_yuv(src.data_ptr(), int(src_bytes), store.data_ptr(), F, table.data_ptr(), table.numel(),
                                                        int(K), int(n_hsets), int(n_vsets), int(n_csets), S_h, S_w, _stream()), "tady_ingest_yuv")

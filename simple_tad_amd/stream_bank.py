@@ -90,6 +90,35 @@ class StreamRings:
         self.start[s] = 0
 
 
+def _pack(sizes):
+    """frames of ``sizes`` bytes back to back at 4-byte aligned offsets behind ``_HEAD`` bytes of slack: (offsets, src_bytes)"""
+    offsets, at = [], _HEAD
+    for n in sizes:
+        offsets.append(at)
+        at += (n + 3) // 4 * 4
+    return offsets, at
+
+
+def _cached_plan(cache: Optional[dict], key, slots, row_words: int, slot_word: int, recheck, build):
+    """What the two planners share around a table: ``build()`` makes ``(table, offsets, src_bytes, *set counts)``, the table checked.
+    ``cache`` keeps the last 16 of them by ``key``; on a hit the table is the kept one with word ``slot_word`` of its rows of
+    ``row_words`` words rewritten to ``slots``, and ``recheck(table, K, src_bytes, counts)`` checks it again all the same."""
+    hit = cache.get(key) if cache is not None else None
+    if hit is not None:
+        proto, offsets, at, *counts = hit
+        table = proto.clone()
+        k = len(offsets)
+        table[:k * row_words].view(k, row_words)[:, slot_word] = torch.as_tensor([int(v) for v in slots], dtype=torch.int32)
+        recheck(table, k, at, counts)
+        return (table, offsets, at, *counts)
+    plan = build()
+    if cache is not None:
+        if len(cache) >= 16:
+            cache.clear()
+        cache[key] = (plan[0].clone(), *plan[1:])
+    return plan
+
+
 def plan_ingest(extents, slots, swaps, S_h: int, S_w: int, F: int, cache: Optional[dict] = None):
     """The table of one ingest launch: frame k is ``extents[k]`` = (h, w), goes to store slot ``slots[k]`` and has its channels 0 and 2
     swapped on the way if ``swaps[k]``.  The frames are laid out back to back at 4-byte aligned offsets behind ``_HEAD`` bytes of slack;
@@ -99,31 +128,24 @@ def plan_ingest(extents, slots, swaps, S_h: int, S_w: int, F: int, cache: Option
     same).  Host only."""
     from . import kernels as K
     from .frame_resize import cubic_coeffs
-    key = (tuple((int(h), int(w)) for h, w in extents), tuple(bool(b) for b in swaps), int(S_h), int(S_w))
-    hit = cache.get(key) if cache is not None else None
-    if hit is not None:
-        proto, offsets, at, nh, nv = hit
-        table = proto.clone()
-        k = len(offsets)
-        table[:k * _lib.BANK_ROW_WORDS].view(k, _lib.BANK_ROW_WORDS)[:, 3] = torch.as_tensor([int(v) for v in slots], dtype=torch.int32)
-        _lib.check_bank(_lib.load_bank().tadb_ingest_plan_check(table.data_ptr(), table.numel(), k, nh, nv, at, int(F), int(S_h), int(S_w)),
+    extents = [(int(h), int(w)) for h, w in extents]
+
+    def recheck(table, k, at, counts):
+        _lib.check_bank(_lib.load_bank().tadb_ingest_plan_check(table.data_ptr(), table.numel(), k, *counts, at, int(F), int(S_h), int(S_w)),
                         "tadb_ingest_plan_check")
-        return table, offsets, at, nh, nv
-    hsets, vsets, rows, offsets = {}, {}, [], []
-    at = _HEAD
-    for (h, w), slot, swap in zip(extents, slots, swaps):
-        h, w = int(h), int(w)
-        rows.append((at, h, w, int(slot), hsets.setdefault(w, len(hsets)), vsets.setdefault(h, len(vsets)), _lib.BANK_SWAP_RB if swap else 0))
-        offsets.append(at)
-        at += (h * w * 3 + 3) // 4 * 4
-    if len(hsets) > _lib.BANK_MAX_SETS or len(vsets) > _lib.BANK_MAX_SETS:
-        raise TadError(f"plan_ingest: {len(hsets)} distinct widths and {len(vsets)} distinct heights in one call, at most {_lib.BANK_MAX_SETS} each")
-    table = K.ingest_table(rows, [(w, *cubic_coeffs(w, S_w)) for w in hsets], [(h, *cubic_coeffs(h, S_h)) for h in vsets], at, F, S_h, S_w)
-    if cache is not None:
-        if len(cache) >= 16:
-            cache.clear()
-        cache[key] = (table.clone(), offsets, at, len(hsets), len(vsets))
-    return table, offsets, at, len(hsets), len(vsets)
+
+    def build():
+        offsets, at = _pack(h * w * 3 for h, w in extents)
+        hsets, vsets = {}, {}
+        rows = [(off, h, w, int(slot), hsets.setdefault(w, len(hsets)), vsets.setdefault(h, len(vsets)), _lib.BANK_SWAP_RB if swap else 0)
+                for off, (h, w), slot, swap in zip(offsets, extents, slots, swaps)]
+        if len(hsets) > _lib.BANK_MAX_SETS or len(vsets) > _lib.BANK_MAX_SETS:
+            raise TadError(f"plan_ingest: {len(hsets)} distinct widths and {len(vsets)} distinct heights in one call, at most {_lib.BANK_MAX_SETS} each")
+        table = K.ingest_table(rows, [(w, *cubic_coeffs(w, S_w)) for w in hsets], [(h, *cubic_coeffs(h, S_h)) for h in vsets], at, F, S_h, S_w)
+        return table, offsets, at, len(hsets), len(vsets)
+
+    key = (tuple(extents), tuple(bool(b) for b in swaps), int(S_h), int(S_w))
+    return _cached_plan(cache, key, slots, _lib.BANK_ROW_WORDS, 3, recheck, build)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4:2:0 YUV frames
@@ -240,34 +262,26 @@ def plan_ingest_yuv(layouts, slots, bgrs, S_h: int, S_w: int, F: int, cache: Opt
     from . import kernels as K
     from .frame_resize import cubic_coeffs
     layouts = [tuple(l) for l in layouts]
-    key = ("yuv", tuple(layouts), tuple(bool(b) for b in bgrs), int(S_h), int(S_w))
-    hit = cache.get(key) if cache is not None else None
-    R = _lib.YUV_ROW_WORDS
-    if hit is not None:
-        proto, offsets, at, nh, nv, nc = hit
-        table = proto.clone()
-        k = len(offsets)
-        table[:k * R].view(k, R)[:, 8] = torch.as_tensor([int(v) for v in slots], dtype=torch.int32)
-        _lib.check_yuv(_lib.load_yuv().tady_ingest_plan_check(table.data_ptr(), table.numel(), k, nh, nv, nc, at, int(F), int(S_h), int(S_w)),
+
+    def recheck(table, k, at, counts):
+        _lib.check_yuv(_lib.load_yuv().tady_ingest_plan_check(table.data_ptr(), table.numel(), k, *counts, at, int(F), int(S_h), int(S_w)),
                        "tady_ingest_plan_check")
-        return table, offsets, at, nh, nv, nc
-    hsets, vsets, csets, rows, offsets = {}, {}, {}, [], []
-    at = _HEAD
-    for (h, w, y_pitch, u_at, v_at, c_pitch, c_step, nbytes, cset), slot, bgr in zip(layouts, slots, bgrs):
-        rows.append((at, y_pitch, at + u_at, at + v_at, c_pitch, c_step, h, w, int(slot), hsets.setdefault(w, len(hsets)),
-                     vsets.setdefault(h, len(vsets)), csets.setdefault(tuple(cset), len(csets)), _lib.YUV_BGR if bgr else 0))
-        offsets.append(at)
-        at += (nbytes + 3) // 4 * 4
-    if len(hsets) > _lib.YUV_MAX_SETS or len(vsets) > _lib.YUV_MAX_SETS or len(csets) > _lib.YUV_MAX_CSETS:
-        raise TadError(f"plan_ingest_yuv: {len(hsets)} distinct widths and {len(vsets)} distinct heights in one call, at most {_lib.YUV_MAX_SETS} each, "
-                       f"and {len(csets)} colour sets, at most {_lib.YUV_MAX_CSETS}")
-    table = K.ingest_yuv_table(rows, [(w, *cubic_coeffs(w, S_w)) for w in hsets], [(h, *cubic_coeffs(h, S_h)) for h in vsets], list(csets), at, F,
-                               S_h, S_w)
-    if cache is not None:
-        if len(cache) >= 16:
-            cache.clear()
-        cache[key] = (table.clone(), offsets, at, len(hsets), len(vsets), len(csets))
-    return table, offsets, at, len(hsets), len(vsets), len(csets)
+
+    def build():
+        offsets, at = _pack(l[7] for l in layouts)
+        hsets, vsets, csets = {}, {}, {}
+        rows = [(off, y_pitch, off + u_at, off + v_at, c_pitch, c_step, h, w, int(slot), hsets.setdefault(w, len(hsets)),
+                 vsets.setdefault(h, len(vsets)), csets.setdefault(tuple(cset), len(csets)), _lib.YUV_BGR if bgr else 0)
+                for off, (h, w, y_pitch, u_at, v_at, c_pitch, c_step, _, cset), slot, bgr in zip(offsets, layouts, slots, bgrs)]
+        if len(hsets) > _lib.YUV_MAX_SETS or len(vsets) > _lib.YUV_MAX_SETS or len(csets) > _lib.YUV_MAX_CSETS:
+            raise TadError(f"plan_ingest_yuv: {len(hsets)} distinct widths and {len(vsets)} distinct heights in one call, at most {_lib.YUV_MAX_SETS} each, "
+                           f"and {len(csets)} colour sets, at most {_lib.YUV_MAX_CSETS}")
+        table = K.ingest_yuv_table(rows, [(w, *cubic_coeffs(w, S_w)) for w in hsets], [(h, *cubic_coeffs(h, S_h)) for h in vsets], list(csets), at,
+                                   F, S_h, S_w)
+        return table, offsets, at, len(hsets), len(vsets), len(csets)
+
+    key = ("yuv", tuple(layouts), tuple(bool(b) for b in bgrs), int(S_h), int(S_w))
+    return _cached_plan(cache, key, slots, _lib.YUV_ROW_WORDS, 8, recheck, build)
 
 
 class _Staging:
@@ -378,25 +392,23 @@ class StreamBank:
             raise TadError(f"Input {k}: a frame of {t.shape[0]} x {t.shape[1]} pixels is above {_lib.BANK_MAX_EXTENT} per side")
         return t
 
-    def push_raw(self, ids, frames: Sequence) -> None:
-        """K frames uint8 [h_k, w_k, 3] of ANY sizes, as decoded (numpy arrays or tensors; device tensors are copied in), one for each of
-        the K distinct streams ``ids``: resized on the device into the ring slots ``SlidingWindow.push_raw`` would have written, ONE
-        launch.  Everything is checked before the state moves or anything is launched."""
+    def _push(self, who: str, ids, frames: Sequence, of, plan, launch, stage, after=None) -> None:
+        """What push_raw and push_yuv share.  ``of(f, k)`` validates frame k; ``plan(fs, ids, slots)`` is the planner's tuple ``(table,
+        offsets, src_bytes, *set counts)``; ``stage(host, f, at)`` copies a frame into the pinned bytes, ``after(dev, f, at)`` into their
+        device twin behind the upload; ``launch`` is the kernel's binding.  Everything is checked before the state moves or anything is
+        launched."""
         if ops_precise():
             raise TadError(_PRECISE)
-        ids = self.rings.check_ids(ids, "StreamBank.push_raw")
+        ids = self.rings.check_ids(ids, who)
         if len(frames) != len(ids):
-            raise TadError(f"StreamBank.push_raw: {len(ids)} stream ids and {len(frames)} frames")
-        fs = [self._frame(f, k) for k, f in enumerate(frames)]
+            raise TadError(f"{who}: {len(ids)} stream ids and {len(frames)} frames")
+        fs = [of(f, k) for k, f in enumerate(frames)]
         if not ids:
             return
         # the slots these frames will take, worked out on a copy: the rings move only once the table has passed its check
         trial = StreamRings(self.S, self.T)
         trial.count, trial.start = list(self.rings.count), list(self.rings.start)
-        slots = trial.assign(ids)
-        table, offsets, nbytes, nh, nv = plan_ingest([tuple(f.shape[:2]) for f in fs], slots, [self.swap[s] for s in ids], self.H, self.W,
-                                                    self.S * self.T, self._plans)
-        from . import kernels as K
+        table, offsets, nbytes, *counts = plan(fs, ids, trial.assign(ids))
         with torch.cuda.device(self.device):
             sb, st = self._bytes[self._tick & 1], self._tables[self._tick & 1]
             self._tick += 1
@@ -405,16 +417,34 @@ class StreamBank:
             st.reserve(table.numel(), self.device)
             host = sb.host.numpy()
             for f, at in zip(fs, offsets):
-                if not f.is_cuda:
-                    host[at:at + f.numel()] = f.contiguous().numpy().reshape(-1)
+                stage(host, f, at)
             st.host[:table.numel()].copy_(table)
             sb.upload(total)
             st.upload(table.numel())
-            for f, at in zip(fs, offsets):
-                if f.is_cuda:
-                    sb.dev[at:at + f.numel()].copy_(f.reshape(-1), non_blocking=True)
-            K.ingest_frames(sb.dev, nbytes, self.store, st.dev[:table.numel()], len(ids), nh, nv)
+            if after is not None:
+                for f, at in zip(fs, offsets):
+                    after(sb.dev, f, at)
+            launch(sb.dev, nbytes, self.store, st.dev[:table.numel()], len(ids), *counts)
         self.rings.count, self.rings.start = trial.count, trial.start
+
+    def push_raw(self, ids, frames: Sequence) -> None:
+        """K frames uint8 [h_k, w_k, 3] of ANY sizes, as decoded (numpy arrays or tensors; device tensors are copied in), one for each of
+        the K distinct streams ``ids``: resized on the device into the ring slots ``SlidingWindow.push_raw`` would have written, ONE
+        launch.  Everything is checked before the state moves or anything is launched."""
+        from . import kernels as K
+
+        def plan(fs, ids, slots):
+            return plan_ingest([tuple(f.shape[:2]) for f in fs], slots, [self.swap[s] for s in ids], self.H, self.W, self.S * self.T, self._plans)
+
+        def stage(host, f, at):
+            if not f.is_cuda:
+                host[at:at + f.numel()] = f.contiguous().numpy().reshape(-1)
+
+        def after(dev, f, at):
+            if f.is_cuda:
+                dev[at:at + f.numel()].copy_(f.reshape(-1), non_blocking=True)
+
+        self._push("StreamBank.push_raw", ids, frames, self._frame, plan, K.ingest_frames, stage, after)
 
     def push_yuv(self, ids, frames: Sequence) -> None:
         """K 4:2:0 YUV frames of ANY sizes and layouts, as the cameras or decoders deliver them (``YuvFrame``: NV12, NV21 or I420,
@@ -423,34 +453,15 @@ class StreamBank:
         ring slots ``push_raw`` would have written, ONE launch (``kernels.ingest_yuv``, include/tad_mi355x_yuv.h).  The channel order is
         the store's own, so a bank can take ``push_raw`` from some cameras and ``push_yuv`` from others.  Everything is checked before
         the state moves or anything is launched."""
-        if ops_precise():
-            raise TadError(_PRECISE)
-        ids = self.rings.check_ids(ids, "StreamBank.push_yuv")
-        if len(frames) != len(ids):
-            raise TadError(f"StreamBank.push_yuv: {len(ids)} stream ids and {len(frames)} frames")
-        fs = [YuvFrame.of(f, k) for k, f in enumerate(frames)]
-        if not ids:
-            return
-        trial = StreamRings(self.S, self.T)
-        trial.count, trial.start = list(self.rings.count), list(self.rings.start)
-        slots = trial.assign(ids)
-        table, offsets, nbytes, nh, nv, nc = plan_ingest_yuv([f.layout for f in fs], slots, [self.store_bgr] * len(fs), self.H, self.W,
-                                                             self.S * self.T, self._yuv_plans)
         from . import kernels as K
-        with torch.cuda.device(self.device):
-            sb, st = self._bytes[self._tick & 1], self._tables[self._tick & 1]
-            self._tick += 1
-            total = nbytes + _HEAD  # (slack behind the last frame as in front of the first)
-            sb.reserve(total, self.device)
-            st.reserve(table.numel(), self.device)
-            host = sb.host.numpy()
-            for f, at in zip(fs, offsets):
-                host[at:at + f.nbytes] = f.data.numpy()[:f.nbytes]
-            st.host[:table.numel()].copy_(table)
-            sb.upload(total)
-            st.upload(table.numel())
-            K.ingest_yuv(sb.dev, nbytes, self.store, st.dev[:table.numel()], len(ids), nh, nv, nc)
-        self.rings.count, self.rings.start = trial.count, trial.start
+
+        def plan(fs, ids, slots):
+            return plan_ingest_yuv([f.layout for f in fs], slots, [self.store_bgr] * len(fs), self.H, self.W, self.S * self.T, self._yuv_plans)
+
+        def stage(host, f, at):
+            host[at:at + f.nbytes] = f.data.numpy()[:f.nbytes]
+
+        self._push("StreamBank.push_yuv", ids, frames, YuvFrame.of, plan, K.ingest_yuv, stage)
 
     def push(self, ids, frames) -> None:
         """frames: uint8 [K,H,W,3] (numpy or tensor, host or device), already at the model's input size, frame k for stream ``ids[k]``:

@@ -168,7 +168,7 @@ def test_plan_check_refuses_malformed_tables():
     bad = good.copy(); bad[hset + _lib.FR_SET_HEAD] = -3
     refused(bad, "outside the 13 samples")
     bad = good.copy(); bad[vset0 + _lib.FR_SET_HEAD + 2] = good[vset0] - 1
-    refused(bad, "vertical set 0: output 2 has its taps")
+    refused(bad, "vertical set 0: output 2 has its first tap at")
     bad = good.copy(); bad[hset + _lib.FR_SET_HEAD + S_w + 4 * 3 + 1] = 2819       # |k| sums over the bound
     refused(bad, "sum |k|")
     bad = good.copy(); bad[vset0 + _lib.FR_SET_HEAD + S_h + 2] = -2819
